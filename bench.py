@@ -9,11 +9,17 @@ the restated find_samples_new (seed 1769, Philox keyed by global ray id) BEFORE 
 region (reported apart, `ic_sampling_s`) and copied to host arrays.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--config flat|gr]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it samples the inputs, runs W warmup and
+K timed steps of the host path, writes the last step's outputs if --dump-outputs is given and
+prints the result line. --full adds the side figures, each of which takes runs of its own: the
+device-resident passes and the CPU baselines.
 
 The timed region is BASELINE.md §2 / SURVEY §8(d)'s: H2D + kernels + D2H. Each step hands
 the batch to art_propagate_host_flux as pageable host arrays (what a Julia ccall from
 MainRunner.jl:179-190 passes) and gets every output back in host arrays, so `value` is the
-drop-in rate. The same passes on device-resident inputs are reported as side figures
+drop-in rate. With --full the same passes on device-resident inputs are reported as side figures
 (`device_resident`, and `device_resident_in_flight` with several batches on as many streams).
 
 N > 1: launched by torch.distributed.run, one rank per GPU; the R rays are sharded in
@@ -157,6 +163,34 @@ def host_arrays(inp, n):
     return h, out
 
 
+DUMP_RAYS = 131072  # rays of a larger batch that --dump-outputs keeps (about 23 MB as float64)
+
+
+def dump_outputs(path, out, flux, n, lo, seed, rank, world):
+    """--dump-outputs: what the last timed host call handed back to its caller, as
+    DIR/<name>.npy in float64 (integer outputs too: exact). Of a batch of more than DUMP_RAYS
+    rays, a fixed sample drawn with the run's seed is kept (the same rays for the same
+    arguments); `ray_index` holds their global ray ids. The per-component arrays are stored
+    as (3, rays). The crossing slots (xc_*) of a ray with no recorded crossing (n_cross = 0),
+    which the library fills with NaN, are stored as 0, so that two dumps compare with plain
+    equality; a NaN anywhere else stays. Rank 0 also writes the all-reduced flux histogram; with N > 1 every rank
+    writes its own shard's sample, the file names suffixed with its rank."""
+    os.makedirs(path, exist_ok=True)
+    if n > DUMP_RAYS:
+        idx = np.sort(np.random.default_rng(seed).choice(n, DUMP_RAYS, replace=False))
+    else:
+        idx = np.arange(n)
+    sfx = f".rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"ray_index{sfx}.npy"), (idx + lo).astype(np.float64))
+    for k, a in out.items():
+        a = a.reshape(3, n)[:, idx] if a.size == 3 * n else a[idx]
+        if k.startswith("xc_"):
+            a = np.where(out["n_cross"][idx] > 0, a, 0.0)  # (no crossing recorded: the slot holds NaN)
+        np.save(os.path.join(path, f"{k}{sfx}.npy"), np.ascontiguousarray(a, np.float64))
+    if rank == 0:
+        np.save(os.path.join(path, "flux_hist.npy"), np.asarray(flux, np.float64).reshape(-1))
+
+
 def timed(run, steps, warmup, world, sync, drain=lambda: None):
     """W untimed warmup steps, then EXACTLY `steps` steps bracketed by a barrier and a device
     synchronize on both sides; returns this rank's elapsed seconds. `drain` completes the steps
@@ -204,8 +238,14 @@ def main():
     ap.add_argument("--inflight", type=int, default=0,
                     help="host calls in flight per rank (art_propagate_host_flux_async: the next batch's uploads and "
                          "first rays overlap this one's drain); 0: 1 for per-GPU batches of >= 8e6 rays, else 2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-device", action="store_true", help="skip the device-resident side figures")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side figures that take runs of their own: the device-resident passes "
+                         "and the CPU baselines (a plain run times the host path only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64; a seeded sample of "
+                         f"{DUMP_RAYS} rays of a larger batch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-device", action="store_true", help="with --full: skip the device-resident side figures")
     ap.add_argument("--no-pcie", action="store_true", help="(compat) same as --no-device")
     args = ap.parse_args()
     n_shard = args.rays // max(1, int(os.environ.get("WORLD_SIZE", "1")))  # this rank's share (to within one ray)
@@ -330,10 +370,14 @@ def main():
     host_steps_total, host_t_max, total_rays = reduce_totals(host_stats["accepted"] * args.steps, host_s, n, world,
                                                              device=eng.device if hist_dev else None)
     host_status = hout["status"].copy()
+    if args.dump_outputs:
+        fx = flux_red["host"]
+        dump_outputs(args.dump_outputs, hout, fx.cpu().numpy() if hasattr(fx, "cpu") else fx, n, lo, args.seed, rank,
+                     world)
 
     # ---- side figure: the same passes on device-resident inputs (art_propagate_device) ----
     dev = None
-    if not (args.no_device or args.no_pcie):
+    if args.full and not (args.no_device or args.no_pcie):
         donate = args.donate if args.donate >= 0 else (16 if args.streams > 1 else 0)
 
         def device_run(nstreams, donate_lanes, steps, warmup):
@@ -497,7 +541,7 @@ def main():
                 line["device_resident_in_flight"] = dev_obj(
                     dev["many"], f"inputs in HBM, {dev['many']['streams']} batches in flight on as many HIP streams "
                                  "(tail donation); a throughput figure, not one batch's latency")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = int(os.environ.get("ART_CPU_THREADS", str(host_cores())))
 
             def sample(m):

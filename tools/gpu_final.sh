@@ -28,16 +28,16 @@ run_step() {
     pmc)
       bash tools/pmc_passes.sh ${O}_pmc 10000000 > ${O}_pmc.log 2>&1 && cp ${O}_pmc/pmc_summary.json profiles/pmc_summary.json ;;
     bench)
-      timeout -k 10 600 python3 -u bench.py > ${O}_bench_flat1e7.json 2> ${O}_bench.err ;;
+      timeout -k 10 600 python3 -u bench.py --full > ${O}_bench_flat1e7.json 2> ${O}_bench.err ;;
     rocprof)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d ${O}_prof -o prof --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > ${O}_bench_prof.json 2> ${O}_prof.err ;;
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d ${O}_prof -o prof --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > ${O}_bench_prof.json 2> ${O}_prof.err ;;
     rocprof_copies)
       timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace --stats -d ${O}_profmc -o prof --output-format csv -- python3 bench.py --steps 5 --no-cpu-baseline --no-device > ${O}_bench_profmc.json 2> ${O}_profmc.err ;;
     shard)
-      timeout -k 10 300 python3 -u bench.py --rays 1250000 --steps 20 --warmup 5 --no-cpu-baseline > ${O}_bench_1250000.json 2> ${O}_shard.err &&
+      timeout -k 10 300 python3 -u bench.py --full --rays 1250000 --steps 20 --warmup 5 --no-cpu-baseline > ${O}_bench_1250000.json 2> ${O}_shard.err &&
       timeout -k 10 300 python3 -u bench.py --rays 1250000 --steps 20 --warmup 5 --no-cpu-baseline --no-device --inflight 1 > ${O}_bench_1250000_inflight1.json 2>> ${O}_shard.err ;;
     gr)
-      timeout -k 10 600 python3 -u bench.py --config gr --rays 1000000 --steps 5 --no-cpu-baseline > ${O}_bench_gr1e6.json 2> ${O}_gr.err ;;
+      timeout -k 10 600 python3 -u bench.py --full --config gr --rays 1000000 --steps 5 --no-cpu-baseline > ${O}_bench_gr1e6.json 2> ${O}_gr.err ;;
     pmc_gr)
       bash tools/pmc_gr.sh ${O}_pmc_gr > ${O}_pmc_gr.log 2>&1 ;;
     scan)

@@ -159,17 +159,17 @@ run_step() {
     smoke)
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > ${O}_smoke.log 2>&1 ;;
     bench)  # the default bench line (host path, 1e7 flat)
-      timeout -k 10 600 python3 -u bench.py > ${O}_bench_flat1e7.json 2> ${O}_bench.err ;;
+      timeout -k 10 600 python3 -u bench.py --full > ${O}_bench_flat1e7.json 2> ${O}_bench.err ;;
     bench_nocpu)
-      timeout -k 10 600 python3 -u bench.py --no-cpu-baseline --steps 10 --warmup 2 > ${O}_bench_flat1e7_nocpu.json 2> ${O}_bench_nocpu.err ;;
+      timeout -k 10 600 python3 -u bench.py --full --no-cpu-baseline --steps 10 --warmup 2 > ${O}_bench_flat1e7_nocpu.json 2> ${O}_bench_nocpu.err ;;
     rocprof)  # kernel trace of the bench command (no counters)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d ${O}_prof -o prof --output-format csv -- python3 bench.py --steps 5 --no-cpu-baseline > ${O}_bench_prof.json 2> ${O}_prof.err ;;
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d ${O}_prof -o prof --output-format csv -- python3 bench.py --full --steps 5 --no-cpu-baseline > ${O}_bench_prof.json 2> ${O}_prof.err ;;
     rocprof_copies)  # the same with the memory-copy trace: are the pipeline's copies DMA or blit kernels?
       timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace --stats -d ${O}_profmc -o prof --output-format csv -- python3 bench.py --steps 5 --no-cpu-baseline --no-device > ${O}_bench_profmc.json 2> ${O}_profmc.err ;;
     shard)  # the 8-GPU shard size on one GPU, with the host pipeline's trace
-      ART_HOST_TRACE=1 timeout -k 10 300 python3 -u bench.py --rays 1250000 --steps 10 --warmup 2 --no-cpu-baseline > ${O}_bench_1250000.json 2> ${O}_shard_trace.err ;;
+      ART_HOST_TRACE=1 timeout -k 10 300 python3 -u bench.py --full --rays 1250000 --steps 10 --warmup 2 --no-cpu-baseline > ${O}_bench_1250000.json 2> ${O}_shard_trace.err ;;
     shard1)  # the same, one host call at a time
-      timeout -k 10 300 python3 -u bench.py --rays 1250000 --steps 10 --warmup 2 --no-cpu-baseline --inflight 1 > ${O}_bench_1250000_if1.json 2> ${O}_shard1.err ;;
+      timeout -k 10 300 python3 -u bench.py --full --rays 1250000 --steps 10 --warmup 2 --no-cpu-baseline --inflight 1 > ${O}_bench_1250000_if1.json 2> ${O}_shard1.err ;;
     bench_if2)  # the 1e7 headline workload with two host calls in flight
       timeout -k 10 600 python3 -u bench.py --no-cpu-baseline --steps 10 --warmup 2 --inflight 2 --no-device > ${O}_bench_flat1e7_if2.json 2> ${O}_bench_if2.err ;;
     ab_tail)  # tail kernel: wave-uniform branches (this build) against none and against RHS-uniform too
@@ -183,7 +183,7 @@ run_step() {
     sampler)
       timeout -k 10 300 python3 -u tools/exp_sampler_time.py > ${O}_sampler_time.jsonl 2> ${O}_sampler.err ;;
     gr)
-      timeout -k 10 600 python3 -u bench.py --config gr --rays 1000000 --steps 5 --no-cpu-baseline > ${O}_bench_gr1e6.json 2> ${O}_gr.err ;;
+      timeout -k 10 600 python3 -u bench.py --full --config gr --rays 1000000 --steps 5 --no-cpu-baseline > ${O}_bench_gr1e6.json 2> ${O}_gr.err ;;
     tail)  # ray 717277 alone on the tail kernel
       TAIL_DONATE=4 timeout -k 10 300 python3 -u tools/exp_gr_tail.py 1000000 717277 > ${O}_gr_tail.jsonl 2> ${O}_gr_tail.err ;;
     grsmall)  # GR batches between 1024 and ncu x 256 rays, donation 16 vs 0
@@ -194,9 +194,9 @@ run_step() {
     tcc)  # L2 hit/miss of both integrator builds (the fetch question), and FETCH_SIZE twice
       for i in 1 2; do
         ART_HOST_STREAM_SERIAL=1 timeout -s KILL 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum -d ${O}_tcc/hit$i -o p \
-          --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline > ${O}_tcc_hit$i.log 2>&1 || return 1
+          --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > ${O}_tcc_hit$i.log 2>&1 || return 1
         ART_HOST_STREAM_SERIAL=1 timeout -s KILL 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d ${O}_tcc/fetch$i -o p \
-          --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline > ${O}_tcc_fetch$i.log 2>&1 || return 1
+          --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > ${O}_tcc_fetch$i.log 2>&1 || return 1
       done ;;
     pmc_gr)  # configs[3]: bulk, continuation and tail kernels of one batch, and ray 717277 alone
       bash tools/pmc_gr.sh ${O}_pmc_gr > ${O}_pmc_gr.log 2>&1 ;;

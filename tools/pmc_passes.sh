@@ -23,7 +23,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" \
   # integrator and finalizes after it, with no persistent helpers; the integrator's code and
   # traffic are the streamed instantiation's all the same)
   ART_HOST_STREAM_SERIAL=1 timeout -k 10 300 rocprofv3 --kernel-trace --pmc $grp -d "$OUT/kernel/pass$i" -o pass$i \
-    --output-format csv -- python3 bench.py --rays "$RAYS" --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/pass$i.log" 2>&1 \
+    --output-format csv -- python3 bench.py --full --rays "$RAYS" --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/pass$i.log" 2>&1 \
     || { echo "pass $i ($grp) failed"; exit 1; }
 done
 python3 tools/pmc_summary.py "$OUT" "flat:$RAYS" "$OUT/pmc_summary.json"
