@@ -30,6 +30,10 @@ class CrossingBuf(C.Structure):
                 ("t", C.c_void_p), ("dw", C.c_void_p), ("p_nonad", C.c_void_p)]
 
 
+class CyclotronOut(C.Structure):  # include/art.h art_cyclotron_out
+    _fields_ = [("tau", C.c_void_p), ("count", C.c_void_p), ("pos", C.c_void_p), ("ln_t", C.c_void_p)]
+
+
 # name -> (restype, argtypes); the test suite checks this table against include/art.h
 class TreeOpts(C.Structure):  # include/art.h art_tree_opts
     _fields_ = [("num_cutoff", C.c_int32), ("mc_nodes", C.c_int32), ("max_nodes", C.c_int32),
@@ -95,6 +99,11 @@ SIGNATURES = {
     "art_eval_rhs_device": (C.c_int, [_P, _i64, _v, _v, _v, _v, _v, _v]),
     "art_eval_hamiltonian_device": (C.c_int, [_P, _i64, _v, _v, _v, _v, _v, _v, _v, _v, _v]),
     "art_eval_condition_device": (C.c_int, [_P, _i64, _v, _v, _v, _v]),
+    "art_propagate_cyclotron_host": (C.c_int, [_P, _i64, _v, _v, _v, _v, _v, _v, _i32, C.POINTER(SegmentOut),
+                                               C.POINTER(CrossingBuf), C.POINTER(CyclotronOut)]),
+    "art_propagate_cyclotron_device": (C.c_int, [_P, _i64, _v, _v, _v, _v, _v, _v, _i32, C.POINTER(SegmentOut),
+                                                 C.POINTER(CrossingBuf), C.POINTER(CyclotronOut), _v]),
+    "art_eval_cyclotron_device": (C.c_int, [_P, _i64, _v, _v, _v, _v, _v, _v]),
 }
 
 _lib = None

@@ -451,10 +451,13 @@ art::KParams kparams(const art_params& p) {
 hipStream_t pick(DeviceCtx*, void* stream) { return (hipStream_t)stream; }
 
 // saveat outputs (art_propagate_traj_*): ntimes >= 2 points per ray, or none (ntimes = 0)
+// ... or the cyclotron observation's outputs (art_propagate_cyclotron_*; not with saveat)
 struct TrajArgs {
   int32_t ntimes = 0;
   double *traj = nullptr, *t = nullptr;
   int32_t* count = nullptr;
+  const art_cyclotron_out* cyc = nullptr;
+  bool none() const { return ntimes == 0 && !cyc; }
 };
 
 // art_propagate_host_flux: the batch's binned radiated flux (flux_kernel over the outputs while
@@ -483,6 +486,12 @@ int check_segment_args(const art_params* p, int64_t n, const double* x0, const d
     return fail(ART_E_INVALID, "crossing buffer incomplete");
   if (tr.ntimes != 0 && (tr.ntimes < 2 || !tr.traj || !tr.t || !tr.count))
     return fail(ART_E_INVALID, "saveat needs ntimes >= 2 and buffers");
+  if (tr.cyc) {
+    if (!tr.cyc->tau || !tr.cyc->count || !tr.cyc->pos || !tr.cyc->ln_t)
+      return fail(ART_E_INVALID, "cyclotron output buffers must be non-NULL");
+    if (p->integrator != ART_VERN6) return fail(ART_E_INVALID, "the cyclotron observation needs the Vern6 integrator");
+    if (tr.ntimes != 0) return fail(ART_E_INVALID, "the cyclotron observation cannot be combined with saveat");
+  }
   return ART_OK;
 }
 
@@ -508,7 +517,7 @@ int launch_donate(DeviceCtx* c, const LaunchOpts& o, const art_params* p, const 
   if (o.donate >= 0) return o.donate;
   if (c->donate >= 0) return c->donate;
   const bool sch = !p->flat && !(p->bndry_lyr > 0.0) && !p->isotropic;
-  return (sch && p->integrator == ART_VERN6 && tr.ntimes == 0) ? 16 : 0;
+  return (sch && p->integrator == ART_VERN6 && tr.none()) ? 16 : 0;
 }
 
 // A small Vern6 batch without saveat runs every ray on a wave of its own (tail_kernel): the
@@ -516,7 +525,7 @@ int launch_donate(DeviceCtx* c, const LaunchOpts& o, const art_params* p, const 
 // lane of the persistent integrator), bit-identical results. One decision for the launch and
 // for every caller that lays out a launch's scratch ahead of it (the chunked host pipeline).
 bool use_small_tail(const art_params* p, int64_t n, const TrajArgs& tr) {
-  return tr.ntimes == 0 && p->integrator == ART_VERN6 && n <= art::small_tail_limit();
+  return tr.none() && p->integrator == ART_VERN6 && n <= art::small_tail_limit();
 }
 
 // this launch's scratch: [queue head + statistics (256 B) | u0: U0_REC n doubles of fresh state
@@ -598,6 +607,14 @@ int propagate_device_impl(const art_params* p, int64_t n, const double* x0, cons
     so.traj_t = tr.t;
     so.traj_n = tr.count;
   }
+  if (tr.cyc) {  // (the integrator adds to tau and count in place)
+    so.cyc_tau = tr.cyc->tau;
+    so.cyc_count = tr.cyc->count;
+    so.cyc_pos = tr.cyc->pos;
+    so.cyc_lnt = tr.cyc->ln_t;
+    HIP_OK(hipMemsetAsync(so.cyc_tau, 0, (size_t)n * sizeof(double), s));
+    HIP_OK(hipMemsetAsync(so.cyc_count, 0, (size_t)n * sizeof(int32_t), s));
+  }
   so.rec = rec;
   art::HotSide hot;
   if (ncont) {
@@ -607,7 +624,7 @@ int propagate_device_impl(const art_params* p, int64_t n, const double* x0, cons
     so.cont2 = so.cont + ncont * art::CONT_REC;
     so.cont2_count = words + 18;
     so.cont2_queue = words + 19;
-    if (!small_tail && tr.ntimes == 0 && p->integrator == ART_VERN6) {
+    if (!small_tail && tr.none() && p->integrator == ART_VERN6) {
       // graduation of a pass's outlier rays to the tail kernel (ART_GRADUATE attempts, default
       // 2048 -- about 23x the mean GR ray, never reached by a flat one; 0 = off;
       // profiles/r04av_graduation_threshold.txt)
@@ -882,6 +899,17 @@ int art_propagate_device(const art_params* p, int64_t n, const double* x0, const
                          art_segment_out* out, art_crossing_buf* xc, void* stream) {
   std::lock_guard<std::mutex> lk(g_mu);
   return propagate_device_impl(p, n, x0, k0, erg, dw, ln_t0, species, max_crossings, out, xc, stream);
+}
+
+int art_propagate_cyclotron_device(const art_params* p, int64_t n, const double* x0, const double* k0,
+                                   const double* erg, const double* dw, const double* ln_t0, const int8_t* species,
+                                   int32_t max_crossings, art_segment_out* out, art_crossing_buf* xc,
+                                   const art_cyclotron_out* cyc, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!cyc) return fail(ART_E_INVALID, "cyc is NULL");
+  TrajArgs tr;
+  tr.cyc = cyc;
+  return propagate_device_impl(p, n, x0, k0, erg, dw, ln_t0, species, max_crossings, out, xc, stream, tr);
 }
 
 int art_propagate_traj_device(const art_params* p, int64_t n, const double* x0, const double* k0, const double* erg,
@@ -1723,6 +1751,16 @@ int propagate_host_single(DeviceCtx* c, hipStream_t s, PoolVec& pool, size_t pb,
     dtr.t = dtr.traj + 3 * nt;
     dtr.count = (int32_t*)(dtr.t + nt);
   }
+  art_cyclotron_out dcy{};
+  if (htr.cyc) {  // staging (saveat's slot: never both): tau n, pos 3n, ln t n doubles, then count n int32
+    void* dc_ = nullptr;
+    if ((rc = pool_get_v(pool, pb + 3,nd * 5 * sizeof(double) + nd * sizeof(int32_t), &dc_))) return rc;
+    dcy.tau = (double*)dc_;
+    dcy.pos = dcy.tau + nd;
+    dcy.ln_t = dcy.tau + 4 * nd;
+    dcy.count = (int32_t*)(dcy.tau + 5 * nd);
+    dtr.cyc = &dcy;
+  }
   // slots without a crossing come back as NaN, not as whatever the pooled staging buffer last
   // held: finalize_kernel writes them (LaunchOpts::nan_fill)
   LaunchOpts opt;
@@ -1746,6 +1784,12 @@ int propagate_host_single(DeviceCtx* c, hipStream_t s, PoolVec& pool, size_t pb,
     HIP_OK(hipMemcpyAsync(htr.t, dtr.t, nt * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_OK(hipMemcpyAsync(htr.count, dtr.count, nd * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   }
+  if (htr.cyc) {
+    HIP_OK(hipMemcpyAsync(htr.cyc->tau, dcy.tau, nd * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(htr.cyc->count, dcy.count, nd * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(htr.cyc->pos, dcy.pos, nd * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(htr.cyc->ln_t, dcy.ln_t, nd * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
   HIP_OK(hipMemcpyAsync(out->x_end, dso.x_end, nd * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(out->k_end, dso.k_end, nd * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(out->u7_end, dso.u7_end, nd * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1762,6 +1806,13 @@ int propagate_host_single(DeviceCtx* c, hipStream_t s, PoolVec& pool, size_t pb,
     HIP_OK(hipMemcpyAsync(xc->p_nonad, dxb.p_nonad, (size_t)cap * nd * sizeof(double), hipMemcpyDeviceToHost, s));
   }
   HIP_OK(hipStreamSynchronize(s));
+  if (htr.cyc) {  // the host contract: NaN where no crossing was found (the staging held stale values)
+    for (size_t i = 0; i < nd; ++i) {
+      if (htr.cyc->count[i] != 0) continue;
+      htr.cyc->pos[i] = htr.cyc->pos[nd + i] = htr.cyc->pos[2 * nd + i] = NAN;
+      htr.cyc->ln_t[i] = NAN;
+    }
+  }
   return finish_timing_slot(c, L);
 }
 
@@ -1782,7 +1833,7 @@ enum HostPath { HP_STREAM, HP_CHUNKED, HP_SINGLE };
 HostPath host_path(const art_params* p, int64_t n, const TrajArgs& htr) {
   const char* mode_env = std::getenv("ART_HOST_MODE");
   const std::string mode = (mode_env && *mode_env) ? mode_env : "stream";
-  if (htr.ntimes == 0 && n >= env_int("ART_HOST_CHUNK_MIN", 1 << 20)) {
+  if (htr.none() && n >= env_int("ART_HOST_CHUNK_MIN", 1 << 20)) {
     if (mode == "stream" && p->integrator == ART_VERN6) return HP_STREAM;
     if (mode == "chunked") return HP_CHUNKED;
   }
@@ -1978,6 +2029,16 @@ int art_propagate_traj_host(const art_params* p, int64_t n, const double* x0, co
   if (ntimes < 2) return fail(ART_E_INVALID, "ntimes must be >= 2");
   TrajArgs tr;
   tr.ntimes = ntimes; tr.traj = traj; tr.t = traj_t; tr.count = traj_n;
+  return propagate_host_impl(p, n, x0, k0, erg, dw, ln_t0, species, max_crossings, out, xc, tr);
+}
+
+int art_propagate_cyclotron_host(const art_params* p, int64_t n, const double* x0, const double* k0, const double* erg,
+                                 const double* dw, const double* ln_t0, const int8_t* species, int32_t max_crossings,
+                                 art_segment_out* out, art_crossing_buf* xc, const art_cyclotron_out* cyc) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!cyc) return fail(ART_E_INVALID, "cyc is NULL");
+  TrajArgs tr;
+  tr.cyc = cyc;
   return propagate_host_impl(p, n, x0, k0, erg, dw, ln_t0, species, max_crossings, out, xc, tr);
 }
 
@@ -2228,6 +2289,20 @@ int art_eval_condition_device(const art_params* p, int64_t n, const double* u, c
   DeviceCtx* c;
   if ((rc = current_ctx(&c))) return rc;
   HIP_OK(art::launch_eval_condition(art::make_kparams(*p), n, u, tau, out, pick(c, stream)));
+  return ART_OK;
+}
+
+int art_eval_cyclotron_device(const art_params* p, int64_t n, const double* pos, const double* k, const double* t,
+                              double* wc, double* tau, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
+  if (!pos || !k || !t || !wc || !tau) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  HIP_OK(art::launch_eval_cyclotron(art::make_kparams(*p), n, pos, k, t, wc, tau, pick(c, stream)));
   return ART_OK;
 }
 

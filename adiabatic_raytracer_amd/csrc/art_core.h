@@ -1375,6 +1375,77 @@ __host__ __device__ inline T wp_cart(const KParams& P, const T* x) {
 }
 
 // ---------------------------------------------------------------------------
+// Cyclotron resonance of the escaping photons (the reference's dead code cyclotronF / tau_cyc,
+// RayTracer.jl:792-851; its npy columns carry opticalDepth = 0, MainRunner.jl:703-708).
+// ω_c [eV] = κ |B| with the reference's literal κ (:794) and the dipole's
+// |B| = |B0|/2 (rNS/r)³ √β, β = 4a1² + a2² + a3² (dipole_ang; ψ = φ - ωPul t). |B0|: the
+// backtrace passes -B0, and a field strength has no sign.
+constexpr double CYC_KAPPA = 0.3 / 5.11e5 * (1.95e-20 * 1e18);  // eV per gauss
+
+template <class T>
+__host__ __device__ inline T cyclotron_wc(const KParams& P, const T& r, const T& st, const T& ct, const T& sp,
+                                          const T& cp) {
+  const DipoleAng<T> d = dipole_ang(P, st, ct, sp, cp);
+  const T beta = 4.0 * d.a1 * d.a1 + d.a2 * d.a2 + d.a3 * d.a3;
+  return (CYC_KAPPA * mabs(P.Bn_coef)) / (r * r * r) * msqrt(beta);
+}
+
+// g = ln ω_c(u[0..2], t = e^τ) - ln erg: the resonance ω_c = ω is g = 0, ω being the ray's erg
+// (Mvars erg), the frequency its Hamiltonian uses. The dead code compares with Mass_a, from which
+// erg differs by ~3e-7 relative. No gravitational redshift is applied: the resonance lies ~2000
+// rNS out, where rs/r ~ 7e-5.
+template <class T>
+__host__ __device__ inline T cyclotron_g(const KParams& P, const T* u, const T& tau, double erg) {
+  T st, ct, sp, cp;
+  msincos(u[1], st, ct);
+  msincos(psi_of(P, u[2], T(fexp(tau))), sp, cp);
+  return flog(cyclotron_wc(P, u[0], st, ct, sp, cp) / erg);
+}
+
+// ω_c at Cartesian x and time t (the pointwise parity entry, art_eval_cyclotron_device)
+template <class T>
+__host__ __device__ inline T cyclotron_wc_cart(const KParams& P, const T* x, const T& t) {
+  const T rho2 = x[0] * x[0] + x[1] * x[1];
+  const T r = msqrt(rho2 + x[2] * x[2]);
+  const T rho = msqrt(rho2);
+  const T sf = x[1] / rho, cf = x[0] / rho;
+  T sw, cw;
+  msincos(P.omega * t, sw, cw);
+  return cyclotron_wc(P, r, T(rho / r), T(x[2] / r), T(sf * cw - cf * sw), T(cf * cw + sf * sw));
+}
+
+// Optical depth of one crossing of ω_c = ω at Cartesian x with momentum k at time t (:837-842):
+// τ = π ωp² / |k̂·∇ω_c| / (c ħ), ∇ the Cartesian gradient at fixed t (analytic:
+// ∇ω_c = ω_c [-3 r̂/r + (∂θβ θ̂ + ∂φβ φ̂/sinθ) / (2 β r)]), k̂ = k/|k|, ωp the GJ ωp at (x, t)
+// with zeroIn = false (wp_cart's formula at ψ; the boundary-layer term, e^(-huge) out there, is
+// kept for consistency). A ray running along a surface of constant ω_c has a zero denominator
+// and gets τ = +inf by IEEE; that is left as it is.
+template <class T>
+__host__ __device__ inline T cyclotron_tau(const KParams& P, const T* x, const T* k, const T& t) {
+  const T rho2 = x[0] * x[0] + x[1] * x[1];
+  const T r = msqrt(rho2 + x[2] * x[2]);
+  const T rho = msqrt(rho2);
+  const T st = rho / r, ct = x[2] / r, sf = x[1] / rho, cf = x[0] / rho;
+  T sw, cw;
+  msincos(P.omega * t, sw, cw);
+  const T sp = sf * cw - cf * sw, cp = cf * cw + sf * sw;  // ψ = φ - ωPul t
+  const DipoleAng<T> d = dipole_ang(P, st, ct, sp, cp);
+  const T beta = 4.0 * d.a1 * d.a1 + d.a2 * d.a2 + d.a3 * d.a3;
+  const T beta_t = 8.0 * d.a1 * d.a1t + 2.0 * d.a2 * d.a1;  // ∂θ a2 = a1, ∂θ a3 = 0
+  const T beta_p = 8.0 * d.a1 * d.a1p + 2.0 * d.a2 * d.a2p + 2.0 * d.a3 * d.a3p;
+  const T wc = (CYC_KAPPA * mabs(P.Bn_coef)) / (r * r * r) * msqrt(beta);
+  // k along r̂, θ̂, φ̂
+  const T kr = st * (cf * k[0] + sf * k[1]) + ct * k[2];
+  const T kt = ct * (cf * k[0] + sf * k[1]) - st * k[2];
+  const T kp = cf * k[1] - sf * k[0];
+  const T kmag = msqrt(k[0] * k[0] + k[1] * k[1] + k[2] * k[2]);
+  const T dwc_dl = wc / r * (-3.0 * kr + (beta_t * kt + beta_p * kp / st) / (2.0 * beta)) / kmag;
+  T wp = msqrt(P.wp2n / (r * r * r) * mabs(d.b));
+  if (P.bndry_lyr > 0.0 && r >= P.rNS) wp = wp + layer_wp(P, r, P.rmax);
+  return PI * wp * wp / mabs(dwc_dl) / (C_KM * HBAR);
+}
+
+// ---------------------------------------------------------------------------
 // Verner 6(5) "most efficient" pair as used by OrdinaryDiffEq's Vern6 (FSAL: b = A[8,:]).
 // Order conditions verified in tests/test_tableau.py.
 struct Vern6 {

@@ -139,6 +139,13 @@ struct SegOut {
   // their hot test within the first few milliseconds. order_tmp: claim_order_bytes(n) of scratch.
   const int32_t* order;
   void* order_tmp;
+  // The cyclotron-resonance observation (art_propagate_cyclotron_*; null: none): per ray the summed
+  // optical depth of its crossings of ω_c = ω and their number (both zeroed before the launch; the
+  // integrator adds to them in place), and the first crossing's Cartesian position [c * n + ray]
+  // and ln t (unwritten where the count stays 0).
+  double* cyc_tau;
+  int32_t* cyc_count;
+  double *cyc_pos, *cyc_lnt;
 };
 constexpr unsigned long long STREAM_WAIT_TICKS = 200000000ull;  // 2 s at 100 MHz
 constexpr int FLUX_HELPER_BINS = 256;  // flux bins the helpers bin themselves (2 x 256 doubles of LDS)
@@ -203,6 +210,7 @@ using KFn = void (*)(const KParams, const int64_t, const SegIn, const SegOut, co
 using TFn = void (*)(const KParams, const int64_t, const SegIn, const SegOut, const int32_t, const int32_t,
                      unsigned long long*);
 KFn nl_propagate(int integ, int geom, bool save, int don, int wps);
+KFn nl_propagate_cyc(int geom, int don);  // (Vern6 with the cyclotron observation, SegOut::cyc_tau)
 TFn nl_tail(int geom);
 // the sampler (find_samples_new) builds, also in art_kernels_nolicm.hip: wps 2 or 3 waves per SIMD,
 // blocks: the blocks-of-steps line scan
@@ -231,4 +239,6 @@ hipError_t launch_event_weight(const KParams& P, int64_t n, const double* x, con
                                double maxR, double rho, double mcmc, double* out, hipStream_t s);
 hipError_t launch_eval_condition(const KParams& P, int64_t n, const double* u, const double* tau, double* out,
                                  hipStream_t s);
+hipError_t launch_eval_cyclotron(const KParams& P, int64_t n, const double* x, const double* k, const double* t,
+                                 double* wc, double* tau, hipStream_t s);
 }  // namespace art

@@ -695,11 +695,55 @@ __device__ inline bool hot_lags(const SegOut& out, double dtau, double log2_att_
   return dtau < out.hot_dtau + out.hot_slope * log2_att_256;
 }
 
+// One crossing of the cyclotron resonance inside the completed step parked in the lane's LDS slots
+// (0-3: u, f, y, kk; 4: h, τ), g0 and g1 being cyclotron_g at its two ends: the root of g on the
+// step's cubic Hermite interpolant of (r, θ, φ) at time τ + θh by Illinois in θ ∈ [0, 1] (bounded;
+// per lane: it runs about once per ray), the full state there back-transformed to Cartesian as
+// affect does for the plasma crossings, and cyclotron_tau added to the ray's optical depth. The
+// sums live in the ray's own output slots: a ray has one owner at a time, so the donation record
+// carries nothing of this.
+__device__ inline void cyclotron_crossing(const KParams& P, const double* L, double erg, double g0, double g1,
+                                          const SegOut& out, int64_t n, int64_t ray) {
+  const double h = L[(4 * 7 + 0) * BLOCK], tau0 = L[(4 * 7 + 1) * BLOCK];
+  auto at = [&](int c, double th) {
+    return hermite1(L[(0 * 7 + c) * BLOCK], L[(1 * 7 + c) * BLOCK], L[(2 * 7 + c) * BLOCK], L[(3 * 7 + c) * BLOCK], h, th);
+  };
+  double a = 0.0, ga = g0, b = 1.0, gb = g1, th = 0.5;
+  int side = 0;
+#pragma unroll 1
+  for (int it = 0; it < 40; ++it) {
+    th = a - ga * (b - a) / (gb - ga);
+    if (!(th > a && th < b)) th = 0.5 * (a + b);
+    const double ui[3] = {at(0, th), at(1, th), at(2, th)};
+    const double g = cyclotron_g(P, ui, tau0 + th * h, erg);
+    if (!(fabs(g) > 1e-15)) break;  // (a NaN ends the search too)
+    if ((g < 0.0) == (ga < 0.0)) { a = th; ga = g; if (side == -1) gb *= 0.5; side = -1; }
+    else { b = th; gb = g; if (side == 1) ga *= 0.5; side = 1; }
+    if (b - a < 1e-14) break;
+  }
+  double ui[7], x[3], k[3];
+#pragma unroll
+  for (int c = 0; c < 7; ++c) ui[c] = at(c, th);
+  back_transform(P, ui, erg, x, k);
+  const double lnt = tau0 + th * h;
+  const double tc = cyclotron_tau(P, x, k, fexp(lnt));
+  const int cnt = out.cyc_count[ray];
+  out.cyc_tau[ray] += tc;
+  out.cyc_count[ray] = cnt + 1;
+  if (cnt == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out.cyc_pos[c * n + ray] = x[c];
+    out.cyc_lnt[ray] = lnt;
+  }
+}
+
 // DON: the tail-donation instantiations (SegOut::donate / cont_mode honoured); the others
 // carry none of that code, so a lone pass pays nothing for it
 // WPS: waves per SIMD the registers are budgeted for (the default 2; the GR continuation
 // launch, below, uses 1)
-template <int INTEG, int GEOM, bool SAVE, int DON, int WPS = ART_WAVES_PER_SIMD>
+// CYC: the cyclotron-resonance observation (SegOut::cyc_tau ...; Vern6 without saveat, DON 0/1);
+// the other instantiations carry none of its code
+template <int INTEG, int GEOM, bool SAVE, int DON, int WPS = ART_WAVES_PER_SIMD, bool CYC = false>
 __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_in, const int64_t n,
                                                                               const SegIn in, const SegOut out,
                                                                               const int32_t max_crossings,
@@ -760,6 +804,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
   int tick = 0;                          // (DON = 3) iterations, for the flushes of the piece counts
   bool cready = false;                   // (DON = 3) the claimed chunk's fresh state is in
   int save_k = 1;  // SAVE: the next interior saveat index
+  double gprev = 0.0;  // CYC: cyclotron_g at (u, tau), recomputed whenever the lane takes a ray
   bool exhausted = false;
   unsigned s_att = 0, s_acc = 0, s_root = 0, s_scan = 0, s_interp = 0, s_rays = 0, s_cert = 0;
 #ifdef ART_SECTION_TIMING
@@ -811,6 +856,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
         const int rank = __popcll(need & ((1ull << lane) - 1ull));
         const int cnt = __popcll(need);
         const int take = (lim - wnext) < cnt ? (lim - wnext) : cnt;
+        const bool takes = mode == M_IDLE && rank < take;
         if (mode == M_IDLE && rank < take && cont) {
           // a donated ray: its complete state from the tail-donation record
           mode = M_STEP;
@@ -876,6 +922,11 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
           just_evented = false;
           qpow = qpow_init;  // qoldinit = 1e-4
           s_rays += 1;
+        }
+        if constexpr (CYC) {
+          // the start-of-step g is a pure function of the state a ray is taken with (fresh, refilled
+          // or a donated one resumed): never the value the lane's previous ray left behind
+          if (takes) gprev = photon ? cyclotron_g(P, u, tau, erg) : 0.0;
         }
         wnext += take;
         need = __ballot(mode == M_IDLE);
@@ -1483,6 +1534,17 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
       else if (iter >= P.maxiters) finish = ART_STATUS_MAXITERS;
     }
 
+    if constexpr (CYC) {
+      // Cyclotron resonance (cyclotron_g, art_core.h): after every completed step of a photon --
+      // saveat's condition -- the sign of g at the state the next step starts from against g at this
+      // step's start. A passive observation: it reads the step's parked interpolant and writes only
+      // the ray's own cyc_* slots; no step, step size, event or other output depends on it.
+      if (((scan && !hit) || root_done) && photon) {
+        const double g1 = cyclotron_g(P, u, tau, erg);
+        if ((gprev < 0.0 && g1 >= 0.0) || (gprev >= 0.0 && g1 < 0.0)) cyclotron_crossing(P, L, erg, gprev, g1, out, n, ray);
+        gprev = g1;
+      }
+    }
     int fin_piece = -1;  // (DON = 3) the piece of a ray finishing now
     if (finish >= 0) {  // the raw end record; finalize_kernel back-transforms it (RayTracer.jl:393-416)
       if constexpr (DON == 3) fin_piece = ray >> out.piece_shift;
@@ -2587,6 +2649,14 @@ KFn nl_propagate(int integ, int geom, bool save, int don, int wps) {
 #undef ART_NL
   return nullptr;
 }
+// (the cyclotron-observing Vern6 integrators, SegOut::cyc_tau: GR and the general geometry)
+KFn nl_propagate_cyc(int geom, int don) {
+  if (geom == GEOM_GR)
+    return don ? propagate_kernel<ART_VERN6, GEOM_GR, false, 1, ART_WAVES_PER_SIMD, true>
+               : propagate_kernel<ART_VERN6, GEOM_GR, false, 0, ART_WAVES_PER_SIMD, true>;
+  return don ? propagate_kernel<ART_VERN6, GEOM_ANY, false, 1, ART_WAVES_PER_SIMD, true>
+             : propagate_kernel<ART_VERN6, GEOM_ANY, false, 0, ART_WAVES_PER_SIMD, true>;
+}
 TFn nl_tail(int geom) { return geom == GEOM_FLAT ? tail_kernel<GEOM_FLAT> : (geom == GEOM_GR ? tail_kernel<GEOM_GR> : tail_kernel<GEOM_ANY>); }
 #endif  // ART_NOLICM_TU
 
@@ -3426,6 +3496,18 @@ __global__ void eval_condition_kernel(const KParams P, const int64_t n, const do
   outc[i] = condition(P, ui, tau[i]);
 }
 
+// ω_c and the optical depth of a crossing (cyclotron_wc_cart / cyclotron_tau) at n points
+__global__ void eval_cyclotron_kernel(const KParams P, const int64_t n, const double* __restrict__ x,
+                                      const double* __restrict__ k, const double* __restrict__ t,
+                                      double* __restrict__ wc, double* __restrict__ tauc) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double xi[3] = {x[i], x[n + i], x[2 * n + i]};
+  const double ki[3] = {k[i], k[n + i], k[2 * n + i]};
+  wc[i] = cyclotron_wc_cart(P, xi, t[i]);
+  tauc[i] = cyclotron_tau(P, xi, ki, t[i]);
+}
+
 // Event weight of every sampled point (MainRunner.jl:498-557, art_event.h); out: 5n SoA.
 __global__ __launch_bounds__(256) void event_weight_kernel(const KParams P, const int64_t n, const double* __restrict__ x,
                                                            const double* __restrict__ k, const double* __restrict__ v,
@@ -3490,7 +3572,10 @@ int persistent_blocks(const void* func, int64_t work, int block, int fallback_pe
 
 // flat's instantiations live here; every other one comes from art_kernels_nolicm.hip (nl_propagate)
 template <int DON>
-static KFn pick_propagate(bool save, bool rk4, bool flat, bool sch) {
+static KFn pick_propagate(bool save, bool rk4, bool flat, bool sch, bool cyc) {
+  if (cyc)  // the cyclotron observation (Vern6 without saveat: the entry points refuse the rest)
+    return flat ? propagate_kernel<ART_VERN6, GEOM_FLAT, false, DON, ART_WAVES_PER_SIMD, true>
+                : nl_propagate_cyc(sch ? GEOM_GR : GEOM_ANY, DON);
   if (save)  // saveat requested: the saving instantiations
     return (!rk4 && flat) ? propagate_kernel<ART_VERN6, GEOM_FLAT, true, DON>
                           : nl_propagate(rk4 ? ART_RK4 : ART_VERN6, (!rk4 && sch) ? GEOM_GR : GEOM_ANY, true, DON,
@@ -3587,7 +3672,10 @@ hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const 
   // graduation (SegOut::grad) only where the tail kernel runs after the continuation to resume
   // the graduated rays
   SegOut out = out_arg;
-  if (out.small_tail || !(out.donate > 0 && tail_rays() != 0 && !rk4 && out.ntimes < 2 && out.cont2)) {
+  // (saveat and the cyclotron observation: the persistent integrator and its packed continuation
+  // alone -- no tail kernel, graduation, hot side stream or 1-wave build)
+  const bool plain = out.ntimes < 2 && !out.cyc_tau;
+  if (out.small_tail || !(out.donate > 0 && tail_rays() != 0 && !rk4 && plain && out.cont2)) {
     out.grad = nullptr;
     out.graduate = 0;
   }
@@ -3641,13 +3729,13 @@ hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const 
                        (int64_t)-1, 0, stats);
     return hipGetLastError();
   }
-  KFn fn = out.donate > 0 ? pick_propagate<1>(out.ntimes >= 2, rk4, flat, sch)
-                           : pick_propagate<0>(out.ntimes >= 2, rk4, flat, sch);
+  KFn fn = out.donate > 0 ? pick_propagate<1>(out.ntimes >= 2, rk4, flat, sch, out.cyc_tau != nullptr)
+                           : pick_propagate<0>(out.ntimes >= 2, rk4, flat, sch, out.cyc_tau != nullptr);
   // A batch that fits one ray per lane of 1 wave per SIMD runs the 1-wave/SIMD build, which
   // does not spill: lone GR tail ray -3%, flat -4.5% per attempt, bit-identical
   // (profiles/r02j_small_batch_w1_ab.txt, tests/test_edges.py). ART_W1=0 switches it off (A/B).
   bool w1 = false;
-  if (w1_builds() && out.donate <= 0 && out.ntimes < 2 && !rk4 && (flat || sch)) {
+  if (w1_builds() && out.donate <= 0 && plain && !rk4 && (flat || sch)) {
     int dev = 0, ncu = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
@@ -3700,7 +3788,7 @@ hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const 
     // with the tail kernel (ART_TAIL != 0, Vern6 without saveat) the packed continuation donates
     // in its turn: its drained waves' last rays (at most ART_TAIL_DONATE each, default 4) go to
     // the second-level records, and tail_kernel resumes each of those on a wave of its own
-    const bool tail = tail_rays() != 0 && !rk4 && out.ntimes < 2 && out.cont2;
+    const bool tail = tail_rays() != 0 && !rk4 && plain && out.cont2;
     SegOut oc = out;  // (the continuation sends its lagging rays to the hot records too)
     oc.cont_mode = 1;
     oc.cont_src = out.cont;
@@ -3713,7 +3801,7 @@ hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const 
     // GR continuations at 1 wave/SIMD: no spills (68 VGPRs spill to scratch at 2). A/B on the
     // configs[3] bench line: 3.21e8 -> 3.35e8 ray-steps/s, bit-identical
     // (profiles/r02h_continuation_w1_ab.txt); flat stays at 2 (measured -3.5% at 1).
-    const KFn cfn = (w1_builds() && sch && !rk4 && out.ntimes < 2) ? nl_propagate(ART_VERN6, GEOM_GR, false, 1, 1) : fn;
+    const KFn cfn = (w1_builds() && sch && !rk4 && plain) ? nl_propagate(ART_VERN6, GEOM_GR, false, 1, 1) : fn;
     hipLaunchKernelGGL(cfn, dim3(cgrid), dim3(BLOCK), 0, s, P, n, in, oc, max_crossings, queue, stats);
     ART_DBG("continuation")
     if ((e = hipGetLastError()) != hipSuccess) return hot_done(e);
@@ -3842,6 +3930,12 @@ hipError_t launch_event_weight(const KParams& P, int64_t n, const double* x, con
                                double maxR, double rho, double mcmc, double* out, hipStream_t s) {
   hipLaunchKernelGGL(event_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, n, x, k, v, maxR, rho,
                      mcmc, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_eval_cyclotron(const KParams& P, int64_t n, const double* x, const double* k, const double* t,
+                                 double* wc, double* tau, hipStream_t s) {
+  hipLaunchKernelGGL(eval_cyclotron_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, n, x, k, t, wc, tau);
   return hipGetLastError();
 }
 

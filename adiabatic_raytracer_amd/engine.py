@@ -8,7 +8,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import CrossingBuf, SegmentOut, check
+from ._lib import CrossingBuf, CyclotronOut, SegmentOut, check
 from .raytracer import Params
 
 F64 = torch.float64
@@ -66,16 +66,27 @@ class Engine:
                 "xc_dw": nan(capacity * n), "xc_p": nan(capacity * n), "capacity": capacity}
 
     # ---- RT.propagate (RayTracer.jl:171-452), asynchronous on the current stream
-    def propagate(self, inp: dict, out: dict | None = None, max_crossings: int = -1, capacity: int = 1) -> dict:
+    def propagate(self, inp: dict, out: dict | None = None, max_crossings: int = -1, capacity: int = 1,
+                  cyclotron: bool = False) -> dict:
+        """cyclotron (art_propagate_cyclotron_device, Vern6): also each ray's cyclotron-resonance optical
+        depth cyc_tau (n), the number of its crossings of ω_c = ω cyc_count (n), and the first one's
+        cyc_pos (3, n) [km] and cyc_ln_t (n), which stay NaN where there is none."""
         n = inp["erg"].numel()
         out = out or self.alloc_out(n, capacity)
         so = SegmentOut(*[out[k].data_ptr() for k in ("x_end", "k_end", "u7_end", "tau_end", "status", "n_accept",
                                                     "n_reject")])
         xb = CrossingBuf(out["capacity"], *[out[k].data_ptr() for k in ("n_cross", "xc_pos", "xc_k", "xc_t", "xc_dw",
                                                                         "xc_p")])
-        check(self.lib.art_propagate_device(
-            C.byref(self.cp), n, *[_p(inp[k]) for k in ("x0", "k0", "erg", "dw", "ln_t0", "species")],
-            int(max_crossings), C.byref(so), C.byref(xb), _stream()))
+        args = [C.byref(self.cp), n, *[_p(inp[k]) for k in ("x0", "k0", "erg", "dw", "ln_t0", "species")],
+                int(max_crossings), C.byref(so), C.byref(xb)]
+        if cyclotron:
+            if "cyc_tau" not in out:
+                out.update(cyc_tau=self.empty(n), cyc_count=self.empty(n, dtype=torch.int32),
+                           cyc_pos=self.empty(3, n).fill_(float("nan")), cyc_ln_t=self.empty(n).fill_(float("nan")))
+            cy = CyclotronOut(*[out[k].data_ptr() for k in ("cyc_tau", "cyc_count", "cyc_pos", "cyc_ln_t")])
+            check(self.lib.art_propagate_cyclotron_device(*args, C.byref(cy), _stream()))
+        else:
+            check(self.lib.art_propagate_device(*args, _stream()))
         return out
 
     def set_tail_donation(self, lanes: int) -> None:
@@ -144,6 +155,14 @@ class Engine:
         check(self.lib.art_eval_hamiltonian_device(C.byref(self.cp), n, _p(x), _p(k), _p(T), _p(E), _p(H), _p(gx),
                                                    _p(gk), _p(gT), _stream()))
         return H, gx, gk, gT
+
+    def eval_cyclotron(self, pos, k, t):
+        """ω_c [eV] and a crossing's optical depth at Cartesian pos, k (3n SoA) and time t (n)"""
+        n = t.numel()
+        wc, tau = self.empty(n), self.empty(n)
+        check(self.lib.art_eval_cyclotron_device(C.byref(self.cp), n, _p(pos), _p(k), _p(t), _p(wc), _p(tau),
+                                                 _stream()))
+        return wc, tau
 
     def eval_condition(self, u, tau):
         n = tau.numel()

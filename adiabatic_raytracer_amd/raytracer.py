@@ -21,7 +21,8 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _lib
-from ._lib import ART_AXION, ART_PHOTON, ART_RK4, ART_VERN6, ArtParams, CrossingBuf, SegmentOut, check
+from ._lib import (ART_AXION, ART_PHOTON, ART_RK4, ART_VERN6, ArtParams, CrossingBuf, CyclotronOut, SegmentOut,
+                   check)
 
 ART_NO_CALLBACKS = -(2 ** 31)  # include/art.h: max_crossings for make_tree = false
 
@@ -177,15 +178,18 @@ def propagate(x0, k0, nsteps, Mvars, NumerP, rhs=func_photon, make_tree=False, i
 
 
 def propagate_batch(params: Params, x0, k0, erg, dw, ln_t0, species, max_crossings=-1, capacity=1,
-                    ntimes=None, flux_nbins=None) -> dict:
+                    ntimes=None, flux_nbins=None, cyclotron=False) -> dict:
     """Low-level host entry (art_propagate_host): SoA numpy inputs, dict of numpy outputs.
     With ntimes >= 2 (art_propagate_traj_host) also the saved points of RayTracer.jl:176,383:
     traj (3, ntimes, n) Cartesian positions, traj_t (ntimes, n) ln t, traj_n (n) points.
     With flux_nbins (art_propagate_host_flux) also `flux` (2, flux_nbins): the batch's binned
     radiated flux (plot/flux.py:38-48), axions in row 0, photons in row 1. The two are separate
-    entry points of the C ABI: asking for both raises ValueError."""
-    if ntimes and flux_nbins:
-        raise ValueError("ntimes (saveat) and flux_nbins are separate entry points: ask for one of them")
+    With cyclotron (art_propagate_cyclotron_host, Vern6) also each ray's cyclotron-resonance
+    optical depth: cyc_tau (n) summed over its crossings of ω_c = ω, cyc_count (n), and the first
+    crossing's cyc_pos (3, n) [km] and cyc_ln_t (n), NaN where there is none. The three are separate
+    entry points of the C ABI: asking for more than one raises ValueError."""
+    if sum(map(bool, (ntimes, flux_nbins, cyclotron))) > 1:
+        raise ValueError("ntimes (saveat), flux_nbins and cyclotron are separate entry points: ask for one of them")
     lib = _lib.load()
     n = int(np.asarray(erg).size)
     f64 = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
@@ -215,6 +219,13 @@ def propagate_batch(params: Params, x0, k0, erg, dw, ln_t0, species, max_crossin
                                           _ptr(species), int(max_crossings), C.byref(so), C.byref(xb),
                                           int(flux_nbins), _ptr(out["flux"])))
         out["flux"] = out["flux"].reshape(2, int(flux_nbins))
+    elif cyclotron:
+        out.update(cyc_tau=np.zeros(n), cyc_count=np.zeros(n, np.int32), cyc_pos=np.zeros(3 * n), cyc_ln_t=np.zeros(n))
+        cy = CyclotronOut(*[_ptr(out[k]) for k in ("cyc_tau", "cyc_count", "cyc_pos", "cyc_ln_t")])
+        check(lib.art_propagate_cyclotron_host(C.byref(cp), n, _ptr(x0), _ptr(k0), _ptr(erg), _ptr(dw), _ptr(ln_t0),
+                                               _ptr(species), int(max_crossings), C.byref(so), C.byref(xb),
+                                               C.byref(cy)))
+        out["cyc_pos"] = out["cyc_pos"].reshape(3, n)
     else:
         check(lib.art_propagate_host(C.byref(cp), n, _ptr(x0), _ptr(k0), _ptr(erg), _ptr(dw), _ptr(ln_t0),
                                      _ptr(species), int(max_crossings), C.byref(so), C.byref(xb)))

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import TreeOpts, TreeTraj, check
-from .raytracer import Params, event_weight, sample_conversion_points
+from .raytracer import Params, event_weight, propagate_batch, sample_conversion_points
 
 AXION, PHOTON = 0, 1
 
@@ -161,7 +161,7 @@ def save_node(fh, node, tr, q):
 
 def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_DM=0.45, n_maxSample=6,
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
-                     file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None):
+                     file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -183,7 +183,13 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     binned radiated flux of plot/flux.py:38-48 -- np.histogram(φf, nbins, range=(-π, π),
     weights = weight * sln_prob) of the rows, axions in flux[0], photons in flux[1], after
     the f_inx division, binned on the GPU and summed over ranks in the same all-reduce --
-    Σ weight * sln_prob per species and the global row count."""
+    Σ weight * sln_prob per species and the global row count.
+
+    cyclotron (beyond the reference, which writes opticalDepth = 0, MainRunner.jl:703-708): the
+    escaping photons' cyclotron-resonance optical depth τ (cyclotron_optical_depth) goes into
+    column 14 (saveMode > 0) and column 8, the weight (weight_tmp, :707-708), is multiplied by
+    exp(-τ), so the flux of run_info is the absorbed one; columns 13 (the tree weight) and 15
+    (weightC) stay. With the default False every row, file and histogram is unchanged."""
     if saveMode < 3:
         ntimes = 3  # "Times to store in ODE" (MainRunner.jl:379-381): also names the npy file
     import time
@@ -228,14 +234,19 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     θf, ϕf, _ = _angles(fin["k_end"])
     θfX, ϕfX, absfX = _angles(fin["x_end"])
     wgt = fin["weight"] * samp_back_weight[ev]  # tree[ii].weight *= samp_back_weight (:690)
+    wgt_tree = wgt  # column 13
     ident = np.where(fin["species"] == AXION, 0.0, 1.0)
+    tau_c = np.zeros_like(wgt)
+    if cyclotron:
+        tau_c = cyclotron_optical_depth(params, fin, erg[ev])
+        wgt = wgt * np.exp(-tau_c)
     f_inx += int(np.sum(ident == 1.0))
     dω = fin["u7_end"] / params.mass_a + w["vel_eng"][ev]  # (:713)
     photon_trajs = lo + ev + 1.0  # global event number
     cols = [photon_trajs, ident, θf, ϕf, θfX, ϕfX, absfX, w["sln_prob"][ev], wgt, x[ev, 0], x[ev, 1], x[ev, 2], dω]
     if saveMode > 0:
         zero = np.zeros_like(wgt)
-        cols += [wgt, zero, zero + 1.0, k[ev, 0], k[ev, 1], k[ev, 2], w["cos_w"][ev], counts[ev].astype(float),
+        cols += [wgt_tree, zero + tau_c, zero + 1.0, k[ev, 0], k[ev, 1], k[ev, 2], w["cos_w"][ev], counts[ev].astype(float),
                  infos[ev].astype(float), fin["prob"], fin["prob_conv"], fin["prob_conv0"], samp_back_weight[ev],
                  absfX, c_bck[ev].astype(float), prob0[ev]]
     rows = np.stack(cols, axis=1) if len(fin) else np.zeros((0, len(cols)))
@@ -266,6 +277,32 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
         os.makedirs(os.path.dirname(path), exist_ok=True)
         np.save(path, rows)
     return rows
+
+
+def cyclotron_optical_depth(params: Params, fin, erg) -> np.ndarray:
+    """τ of the cyclotron resonance along the last segment of each final node (0 for axions): the
+    photon nodes' segments (x0, k0, t0, dw0) run again in one batch through
+    art_propagate_cyclotron_host, as get_tree ran them (art_forest.cpp: ln t0 = log(max(t0, e^-30)),
+    max_crossings = -1). The observation is passive, so each re-run must end where its node did,
+    bit for bit; that is asserted."""
+    tau = np.zeros(len(fin))
+    ph = np.flatnonzero(fin["species"] == PHOTON)
+    if ph.size == 0:
+        return tau
+    f = fin[ph]
+    dt0 = math.exp(-30.0)
+    lnt = np.array([math.log(max(float(t), dt0)) for t in f["t0"]])
+    res = propagate_batch(params, f["x0"].T, f["k0"].T, np.asarray(erg, np.float64)[ph], f["dw0"], lnt,
+                          np.full(ph.size, PHOTON, np.int8), max_crossings=-1, cyclotron=True)
+    same = (np.array_equal(res["x_end"].reshape(3, -1).T, f["x_end"], equal_nan=True)
+            and np.array_equal(res["k_end"].reshape(3, -1).T, f["k_end"], equal_nan=True)
+            and np.array_equal(res["u7_end"], f["u7_end"], equal_nan=True)
+            and np.array_equal(res["tau_end"], f["tau_end"], equal_nan=True)
+            and np.array_equal(res["status"], f["status"]))
+    if not same:
+        raise AssertionError("the cyclotron re-run of the final photon segments does not reproduce their end states")
+    tau[ph] = res["cyc_tau"]
+    return tau
 
 
 def radiated_flux(phif, ident, weights, nbins=50, range=(-np.pi, np.pi)) -> np.ndarray:

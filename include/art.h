@@ -283,6 +283,34 @@ int art_propagate_traj_device(const art_params* p, int64_t n, const double* x0, 
                               art_crossing_buf* xc, int32_t ntimes, double* traj, double* traj_t,
                               int32_t* traj_n, void* stream);
 
+/* ---- RT.propagate with the cyclotron-resonance optical depth of each ray ----
+ * Beyond the reference: it writes opticalDepth = 0 into every npy row (MainRunner.jl:703-708)
+ * and keeps the formula as dead code (cyclotronF / tau_cyc, RayTracer.jl:792-851). As
+ * art_propagate_*, and while a photon is integrated every crossing of omega_c = omega
+ * (omega_c = 0.3/5.11e5*(1.95e-20*1e18) eV/G * |B| of the rotating dipole, omega the ray's erg) is
+ * located on the step's cubic Hermite interpolant and its optical depth
+ * tau = pi omega_p^2 / |khat . grad omega_c| / (c hbar) added up (khat = k/|k| Cartesian, the GJ
+ * omega_p there; a ray running along a surface of constant omega_c gets +inf). The observation
+ * is passive: every art_segment_out / art_crossing_buf output equals art_propagate_*'s bit for
+ * bit. Vern6 only (RK4: ART_E_INVALID); cyc and its four buffers must be non-NULL.
+ * tau and count are written for every ray (axions: 0); pos and ln_t hold the first crossing and
+ * follow the crossing-buffer convention: the device entry point leaves them unwritten where
+ * count = 0, the host entry point fills NaN there. */
+typedef struct art_cyclotron_out {
+  double*  tau;    /* n   sum of tau over the segment's cyclotron crossings (0 when none) */
+  int32_t* count;  /* n   crossings of omega_c = omega found                              */
+  double*  pos;    /* 3n  Cartesian position of the first one [km], [c*n + i]             */
+  double*  ln_t;   /* n   its ln t                                                        */
+} art_cyclotron_out;
+int art_propagate_cyclotron_host(const art_params* p, int64_t n, const double* x0, const double* k0,
+                                 const double* erg, const double* dw, const double* ln_t0,
+                                 const int8_t* species, int32_t max_crossings, art_segment_out* out,
+                                 art_crossing_buf* xc, const art_cyclotron_out* cyc);
+int art_propagate_cyclotron_device(const art_params* p, int64_t n, const double* x0, const double* k0,
+                                   const double* erg, const double* dw, const double* ln_t0,
+                                   const int8_t* species, int32_t max_crossings, art_segment_out* out,
+                                   art_crossing_buf* xc, const art_cyclotron_out* cyc, void* stream);
+
 /* ---- get_Prob_nonAD (MainRunner.jl:67-124) ----
  * One call of the reference per group: group g covers crossings
  * [group_start[g], group_start[g+1]) and reproduces the reference's column-major
@@ -444,6 +472,10 @@ int art_eval_hamiltonian_device(const art_params* p, int64_t n, const double* x,
 /* resonance condition (RayTracer.jl:254-298): value (n) */
 int art_eval_condition_device(const art_params* p, int64_t n, const double* u,
                               const double* tau, double* out, void* stream);
+/* cyclotron frequency omega_c [eV] (n) and the optical depth tau (n) of a crossing at Cartesian
+ * pos / k (3n SoA) and time t (n) [s] */
+int art_eval_cyclotron_device(const art_params* p, int64_t n, const double* pos, const double* k,
+                              const double* t, double* wc, double* tau, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@ int64_t small_tail_limit() { return 0; }
 int helper_waves_per_simd(const KParams&) { return 2; }
 HFn pick_helper(const KParams&) { return nullptr; }
 KFn nl_propagate(int, int, bool, int, int) { return nullptr; }
+KFn nl_propagate_cyc(int, int) { return nullptr; }
 TFn nl_tail(int) { return nullptr; }
 SFn nl_sample(int, bool) { return nullptr; }
 hipError_t launch_sample(const KParams&, double, uint64_t, int64_t, int64_t, double*, double*, double*, double*, int32_t*,
@@ -40,4 +41,6 @@ hipError_t launch_event_weight(const KParams&, int64_t, const double*, const dou
 hipError_t launch_eval_condition(const KParams&, int64_t, const double*, const double*, double*, hipStream_t) {
   return hipErrorNoDevice;
 }
+hipError_t launch_eval_cyclotron(const KParams&, int64_t, const double*, const double*, const double*, double*, double*,
+                                 hipStream_t) { return hipErrorNoDevice; }
 }  // namespace art

@@ -76,6 +76,22 @@ void cc_exp_fma(const double* x, int64_t n, double* y) {
 void cc_log_fma(const double* x, int64_t n, double* y) {
   for (int64_t i = 0; i < n; ++i) y[i] = log_fma(x[i]);
 }
+// cyclotron_wc_cart / cyclotron_tau (art_core.h) at n points: pos, k 3n SoA, t n
+void cc_cyclotron_wc(const art_params* p, int64_t n, const double* pos, const double* t, double* wc) {
+  KParams K = make_kparams(*p);
+  for (int64_t i = 0; i < n; ++i) {
+    const double x[3] = {pos[i], pos[n + i], pos[2 * n + i]};
+    wc[i] = cyclotron_wc_cart(K, x, t[i]);
+  }
+}
+void cc_cyclotron_tau(const art_params* p, int64_t n, const double* pos, const double* k, const double* t, double* tau) {
+  KParams K = make_kparams(*p);
+  for (int64_t i = 0; i < n; ++i) {
+    const double x[3] = {pos[i], pos[n + i], pos[2 * n + i]};
+    const double kk[3] = {k[i], k[n + i], k[2 * n + i]};
+    tau[i] = cyclotron_tau(K, x, kk, t[i]);
+  }
+}
 void cc_metric_d(double r, double rs, double* out) {
   double gtt, grr, dgtt, dgrr;
   metric_tr_d(r, rs, gtt, grr, dgtt, dgrr);

@@ -130,6 +130,22 @@ def log_fma(x):
     return y
 
 
+def cyclotron_wc(p, pos, t):
+    """ω_c [eV] (cyclotron_wc_cart) at the n Cartesian points pos (3, n) and times t (n)"""
+    pos, t = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(t, np.float64)
+    wc = np.zeros(t.size)
+    lib().cc_cyclotron_wc(C.byref(p), C.c_int64(t.size), P(pos), P(t), P(wc))
+    return wc
+
+
+def cyclotron_tau(p, pos, k, t):
+    """τ of a crossing (cyclotron_tau) at the n Cartesian points pos, momenta k (3, n) and times t (n)"""
+    pos, k, t = (np.ascontiguousarray(a, np.float64) for a in (pos, k, t))
+    tau = np.zeros(t.size)
+    lib().cc_cyclotron_tau(C.byref(p), C.c_int64(t.size), P(pos), P(k), P(t), P(tau))
+    return tau
+
+
 def metric_d(r, rs):
     o = np.zeros(4)
     lib().cc_metric_d(C.c_double(r), C.c_double(rs), P(o))
