@@ -104,7 +104,10 @@ SIGNATURES = {
     "art_propagate_cyclotron_device": (C.c_int, [_P, _i64, _v, _v, _v, _v, _v, _v, _i32, C.POINTER(SegmentOut),
                                                  C.POINTER(CrossingBuf), C.POINTER(CyclotronOut), _v]),
     "art_eval_cyclotron_device": (C.c_int, [_P, _i64, _v, _v, _v, _v, _v, _v]),
+    "art_eval_math_device": (C.c_int, [_i32, _i32, _i64, _v, _v, _v, _v, _v]),
 }
+# include/art.h ART_MATH_*: the function ids of art_eval_math_device
+MATH_FN = {"SINCOS": 0, "EXP": 1, "LOG": 2, "RCP": 3, "POW120": 4, "MAX_ABS": 5, "MIN_Q": 6, "MAX_Q": 7, "RCLAMP": 8}
 
 _lib = None
 

@@ -2306,6 +2306,22 @@ int art_eval_cyclotron_device(const art_params* p, int64_t n, const double* pos,
   return ART_OK;
 }
 
+int art_eval_math_device(int32_t fn, int32_t tu, int64_t n, const double* a, const double* b, double* out0,
+                         double* out1, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (fn < 0 || fn >= ART_MATH_COUNT) return fail(ART_E_INVALID, "unknown fn (ART_MATH_*)");
+  if (tu != 0 && tu != 1) return fail(ART_E_INVALID, "tu must be 0 or 1");
+  if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
+  if (n == 0) return ART_OK;
+  const bool two = fn == ART_MATH_MAX_ABS || fn == ART_MATH_MIN_Q || fn == ART_MATH_MAX_Q || fn == ART_MATH_RCLAMP;
+  if (!a || (two && !b)) return fail(ART_E_INVALID, "NULL operand");
+  DeviceCtx* c;
+  int rc = current_ctx(&c);
+  if (rc) return rc;
+  HIP_OK(art::launch_eval_math(fn, tu, n, a, b, out0, out1, pick(c, stream)));
+  return ART_OK;
+}
+
 // ---- the radiated-flux reduction across ranks: one RCCL all-reduce ----
 // RCCL is opened at first use (dlopen), so libart.so loads and runs single-GPU work where it
 // is absent; a process that already loaded librccl.so.1 (e.g. PyTorch's) shares that copy.

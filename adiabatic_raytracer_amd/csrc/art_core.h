@@ -53,11 +53,20 @@ __host__ __device__ inline double mexp(double x) { return exp(x); }
 __host__ __device__ inline double mabs(double x) { return fabs(x); }
 __host__ __device__ inline double msign(double x) { return copysign(1.0, x); }  // ForwardDiff abs: signbit
 // sin and cos together: FMA Cody-Waite reduction by π/2 (3 parts) + the fdlibm kernels on
-// [-π/4, π/4]; <= 1 ulp against glibc for |x| <= 200 (tests/test_corecheck.py). The ray's
-// angles θ and ψ = φ - ωt stay small, so the large-argument (Payne-Hanek) path that
+// [-π/4, π/4]. Against the true value (mpmath, tests/golden/devmath/sincos.npz: |x| <= 200, ±1e6,
+// the doubles at k π/2 for k <= 100, 1e-300..1e-8) the bound held is 2 ulp; measured 1.25 ulp
+// (sin) and 1.22 ulp (cos), the same on the host compile (tests/test_devmath.py) and on the
+// device (tests/test_gpu_devmath.py). Against glibc, itself within 1 ulp: <= 1 ulp for |x| <= 200
+// (tests/test_corecheck.py). sin is odd and cos even bit for bit, sin(±0) = ±0, NaN gives NaN.
+// The ray's angles θ and ψ = φ - ωt stay small, so the large-argument (Payne-Hanek) path that
 // ocml's sincos carries -- ~200 instructions of code per call site -- is never needed.
-__host__ __device__ inline void msincos(double x, double& s, double& c) {
+__host__ __device__ inline void msincos(double x_in, double& s, double& c) {
   ART_FP_FAST
+  // on |x|, the sign of x going into sin's sign bit below: sin(-x) = -sin(x) and cos(-x) = cos(x)
+  // bit for bit, and sin(-0) = -0 (reduced as it stands, -0 came out as +0: n = -0, and
+  // fma(+0, π/2, -0) = +0). Every step is odd or even in x, rint's ties to even included, so
+  // no other result changes.
+  const double x = fabs(x_in);
   const double n = rint(x * 0.63661977236758134308);
   double r = fma(-n, 1.5707963267948966, x);
   r = fma(-n, 6.123233995736766e-17, r);
@@ -79,14 +88,18 @@ __host__ __device__ inline void msincos(double x, double& s, double& c) {
   const double cc = (q & 1) ? sr : cr;
   // the quadrant's signs by flipping the sign bit (an XOR of the high word instead of a
   // compare and a select of both words): -x exactly
-  const unsigned long long ms = (unsigned long long)(q & 2) << 62, mc = (unsigned long long)((q + 1) & 2) << 62;
+  const unsigned long long sx = __builtin_bit_cast(unsigned long long, x_in) & 0x8000000000000000ull;
+  const unsigned long long ms = ((unsigned long long)(q & 2) << 62) ^ sx, mc = (unsigned long long)((q + 1) & 2) << 62;
   s = __builtin_bit_cast(double, __builtin_bit_cast(unsigned long long, ss) ^ ms);
   c = __builtin_bit_cast(double, __builtin_bit_cast(unsigned long long, cc) ^ mc);
 }
 // max(|a|, |b|), min(a, b) and max(a, b) as one instruction each. LLVM's fmax/fmin in IEEE
 // mode first quiet signaling NaNs with a v_max x, x per operand it cannot prove canonical
 // (anything loaded or passed in); the integrator never holds signaling NaNs, and a quiet NaN
-// operand gives the other operand either way.
+// operand gives the other operand either way (the kernels run in IEEE mode): on the device the
+// three equal numpy's fmax / fmin exactly over all pairs of ±0, ±5e-324, ±1, ±1.5, ±1e308, ±inf,
+// NaN and random pairs, fmax_abs never negative (tests/test_gpu_devmath.py). The error norm relies
+// on it: fmax_abs(u[i], y[i]) with a NaN y leaves EEst2 alone until y's own finiteness check.
 __host__ __device__ inline double fmax_abs(double a, double b) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double r;
@@ -130,9 +143,15 @@ template <class T>
 __host__ __device__ inline T rclamp(const T& r, double rns) {
   return (r < rns) ? T(rns) : r;
 }
-// 1/x from the hardware reciprocal and two Newton steps (~0.5 ulp; 1/0 and 1/inf give NaN,
-// which the integrator reports as a non-finite state either way). The host build, which the
-// CPU tests compare with the oracle, divides.
+// 1/x from the hardware reciprocal and two Newton steps, for 2^-1020 <= |x| <= 2^1020 (its
+// arguments are abstol + |u| reltol, controller factors and radii; subnormal operands and
+// results are not reached and nothing is claimed there). Against the exact quotient (mpmath,
+// tests/golden/devmath/rcp.npz: random mantissas and exponents, 1 ± k ulp, 2 - k ulp, mantissas
+// in [1.99, 2), every fourth power of two, both signs) the bound held is 1 ulp; measured on the
+// device 0.500 ulp, i.e. correctly rounded at every point of the set, powers of two exact and
+// frcp(-x) = -frcp(x) bit for bit (tests/test_gpu_devmath.py). 1/0 and 1/inf give NaN, which the
+// integrator reports as a non-finite state either way. The host build, which the CPU tests
+// compare with the oracle, divides.
 __host__ __device__ inline double frcp(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   double r = __builtin_amdgcn_rcp(x);
@@ -146,9 +165,13 @@ __host__ __device__ inline double frcp(double x) {
 }
 // e^x in 19 FMA-pipe instructions (ocml's exp_f64: 34): Cody-Waite reduction by ln 2 with a
 // two-part constant (the first FMA is exact for |k| < 2^11), the degree-13 Taylor polynomial
-// on |r| <= ln2/2 (truncation < 0.05 ulp) and one ldexp. <= 1 ulp for |x| < 708
-// (tests/test_corecheck.py); no overflow/underflow/NaN special-casing beyond what the
-// arithmetic propagates (the integrator's arguments are moderate ln t and ln EEst values).
+// on |r| <= ln2/2 (truncation < 0.05 ulp) and one ldexp. Against the true value (mpmath,
+// tests/golden/devmath/exp.npz: |x| <= 708, the ln t range [-30, 5], ±1e-3, the reduction's rint
+// ties at (k + 1/2) ln 2) the bound held is 1 ulp; measured 0.825 ulp on the host compile
+// (tests/test_devmath.py) and on the device (tests/test_gpu_devmath.py) alike. Against libm:
+// <= 1 ulp (tests/test_corecheck.py). No overflow/underflow/NaN special-casing beyond what the
+// arithmetic propagates (e^710 = inf, e^-800 = 0, NaN gives NaN; the integrator's arguments are
+// moderate ln t and ln EEst values).
 // Horner step p r + c as one three-operand v_fma_f64 (the backend otherwise picks the two-
 // address v_fmac_f64 with the coefficient copied into the accumulator: a v_mov_b64 per step)
 __host__ __device__ inline double horner_fma(double p, double r, double c) {
@@ -183,7 +206,14 @@ __host__ __device__ inline double exp_fma(double x) {
 }
 // ln x for finite x > 0 (the step-size controller's ln EEst): x = m 2^e with m in
 // [√½, √2), ln m = 2 atanh(s), s = (m - 1)/(m + 1), |s| <= 0.1716, odd series to s^21.
-// ~30 instructions against ocml's 105; <= 2 ulp (tests/test_corecheck.py).
+// ~30 instructions against ocml's 105. Against the true value (mpmath,
+// tests/golden/devmath/log.npz: 1e-300..1e300, [0.5, 2], 1 ± 1e-6, 1 ± 1e-12, the fold at √½ 2^e,
+// subnormals, the largest double) the bound held is 2 ulp; measured 1.71 ulp on the host compile
+// (tests/test_devmath.py), which divides, and 1.90 ulp on the device (tests/test_gpu_devmath.py),
+// whose s comes from the refined hardware reciprocal times f; both maxima lie within 1e-6 of
+// x = 1, where e = 0 and the result is 2s and inherits the roundings of s in full. The controller's
+// fexp(flog(EEst2) * (1.0 / 120.0)): bound 4 ulp over EEst2 in [1e-40, 1e10], measured 1.41 ulp
+// on both. Against libm: <= 2 ulp (tests/test_corecheck.py).
 __host__ __device__ inline double log_fma(double x) {
   int e;
   double m = frexp(x, &e);  // [0.5, 1)

@@ -241,4 +241,10 @@ hipError_t launch_eval_condition(const KParams& P, int64_t n, const double* u, c
                                  hipStream_t s);
 hipError_t launch_eval_cyclotron(const KParams& P, int64_t n, const double* x, const double* k, const double* t,
                                  double* wc, double* tau, hipStream_t s);
+// art_eval_math_device: fn an ART_MATH_* id; tu 0 the kernel of art_kernels.hip, 1 the same one
+// compiled in art_kernels_nolicm.hip (nl_eval_math)
+using MFn = void (*)(const int64_t, const double*, const double*, double*, double*);
+MFn nl_eval_math(int fn);
+hipError_t launch_eval_math(int fn, int tu, int64_t n, const double* a, const double* b, double* out0, double* out1,
+                            hipStream_t s);
 }  // namespace art

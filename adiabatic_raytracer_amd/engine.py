@@ -164,6 +164,19 @@ class Engine:
                                                  _stream()))
         return wc, tau
 
+    def eval_math(self, fn, a, b=None, tu=0):
+        """One of art_core.h's hand-written scalar functions at every element of a (and b)
+        (art_eval_math_device): fn an ART_MATH_* id or its name ("SINCOS", "EXP", "LOG", "RCP",
+        "POW120", "MAX_ABS", "MIN_Q", "MAX_Q", "RCLAMP"); tu the translation unit the kernel was
+        compiled in (0 art_kernels.hip, 1 art_kernels_nolicm.hip). Returns (sin, cos) for SINCOS,
+        else one tensor."""
+        fn = _lib.MATH_FN[fn] if isinstance(fn, str) else int(fn)
+        n = a.numel()
+        out0 = self.empty(n)
+        out1 = self.empty(n) if fn == _lib.MATH_FN["SINCOS"] else None
+        check(self.lib.art_eval_math_device(fn, int(tu), n, _p(a), _p(b), _p(out0), _p(out1), _stream()))
+        return (out0, out1) if out1 is not None else out0
+
     def eval_condition(self, u, tau):
         n = tau.numel()
         c = self.empty(n)

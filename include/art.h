@@ -29,7 +29,9 @@
  *   art_event_weight_*             sln_prob of a sampled point: dwp_ds cos_w + g_det
  *                                  (MainRunner.jl:498-557, RayTracer.jl:734-754,1327-1403)
  *   art_eval_*_device              pointwise physics (func!, func_axion!, hamiltonian,
- *                                  GJ_Model_ωp_vecSPH, condition) for parity tests
+ *                                  GJ_Model_ωp_vecSPH, condition) for parity tests;
+ *                                  art_eval_math_device: the hand-written sincos / exp / log /
+ *                                  reciprocal / min / max themselves, for ulp-level tests
  *
  * Conventions
  *   - All arrays are caller-owned. Position/momentum arrays are structure-of-arrays,
@@ -476,6 +478,26 @@ int art_eval_condition_device(const art_params* p, int64_t n, const double* u,
  * pos / k (3n SoA) and time t (n) [s] */
 int art_eval_cyclotron_device(const art_params* p, int64_t n, const double* pos, const double* k,
                               const double* t, double* wc, double* tau, void* stream);
+/* the hand-written scalar functions of art_core.h themselves, one thread per element, for
+ * ulp-level tests against the true value: out0[i] (and out1[i]) = fn(a[i], b[i]). b is read by
+ * the two-operand ids only, out1 written by ART_MATH_SINCOS only; an output that is NULL is not
+ * written. tu picks the translation unit the kernel was compiled in: 0 art_kernels.hip,
+ * 1 art_kernels_nolicm.hip (the functions must round alike in both). An unknown fn or tu is
+ * ART_E_INVALID. */
+enum {
+  ART_MATH_SINCOS = 0,  /* msincos(a): out0 = sin, out1 = cos */
+  ART_MATH_EXP = 1,     /* fexp(a) */
+  ART_MATH_LOG = 2,     /* flog(a) */
+  ART_MATH_RCP = 3,     /* frcp(a) */
+  ART_MATH_POW120 = 4,  /* fexp(flog(a) * (1.0 / 120.0)), the step-size controller's EEst2^(1/120) */
+  ART_MATH_MAX_ABS = 5, /* fmax_abs(a, b) */
+  ART_MATH_MIN_Q = 6,   /* fmin_q(a, b) */
+  ART_MATH_MAX_Q = 7,   /* fmax_q(a, b) */
+  ART_MATH_RCLAMP = 8,  /* rclamp(a, b): radius a clamped to rNS = b */
+  ART_MATH_COUNT = 9
+};
+int art_eval_math_device(int32_t fn, int32_t tu, int64_t n, const double* a, const double* b,
+                         double* out0, double* out1, void* stream);
 
 #ifdef __cplusplus
 }

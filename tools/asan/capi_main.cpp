@@ -87,6 +87,12 @@ int main() {
   CHECK(art_comm_destroy() == ART_OK);
   double ms[2];
   CHECK(art_recent_kernel_ms(-1, ms) != ART_OK);
+  // the scalar-function entry: an unknown fn or tu is refused before any device call, n = 0 touches nothing
+  CHECK(art_eval_math_device(ART_MATH_COUNT, 0, 4, h, h, h, nullptr, nullptr) == ART_E_INVALID);
+  CHECK(art_eval_math_device(-1, 0, 4, h, h, h, nullptr, nullptr) == ART_E_INVALID);
+  CHECK(art_eval_math_device(ART_MATH_EXP, 2, 4, h, nullptr, h, nullptr, nullptr) == ART_E_INVALID);
+  CHECK(art_eval_math_device(ART_MATH_MAX_Q, 0, 4, h, nullptr, h, nullptr, nullptr) == ART_E_INVALID);
+  CHECK(art_eval_math_device(ART_MATH_EXP, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == ART_OK);
   std::printf("capi OK\n");
   return 0;
 }

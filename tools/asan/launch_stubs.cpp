@@ -43,4 +43,8 @@ hipError_t launch_eval_condition(const KParams&, int64_t, const double*, const d
 }
 hipError_t launch_eval_cyclotron(const KParams&, int64_t, const double*, const double*, const double*, double*, double*,
                                  hipStream_t) { return hipErrorNoDevice; }
+MFn nl_eval_math(int) { return nullptr; }
+hipError_t launch_eval_math(int, int, int64_t, const double*, const double*, double*, double*, hipStream_t) {
+  return hipErrorNoDevice;
+}
 }  // namespace art

@@ -76,6 +76,16 @@ void cc_exp_fma(const double* x, int64_t n, double* y) {
 void cc_log_fma(const double* x, int64_t n, double* y) {
   for (int64_t i = 0; i < n; ++i) y[i] = log_fma(x[i]);
 }
+// the step-size controller's EEst2^(1/120) with the device's exp_fma / log_fma (the host's fexp /
+// flog are libm), the expression as the two controller sites of art_kernels.hip write it
+void cc_pow120(const double* x, int64_t n, double* y) {
+  for (int64_t i = 0; i < n; ++i) y[i] = exp_fma(log_fma(x[i]) * (1.0 / 120.0));
+}
+// fmax_abs / fmin_q / fmax_q / rclamp (the host compile: libm's fmax / fmin); which = 0..3
+void cc_minmax(int which, const double* a, const double* b, int64_t n, double* y) {
+  for (int64_t i = 0; i < n; ++i)
+    y[i] = which == 0 ? fmax_abs(a[i], b[i]) : which == 1 ? fmin_q(a[i], b[i]) : which == 2 ? fmax_q(a[i], b[i]) : rclamp(a[i], b[i]);
+}
 // cyclotron_wc_cart / cyclotron_tau (art_core.h) at n points: pos, k 3n SoA, t n
 void cc_cyclotron_wc(const art_params* p, int64_t n, const double* pos, const double* t, double* wc) {
   KParams K = make_kparams(*p);

@@ -130,6 +130,37 @@ def log_fma(x):
     return y
 
 
+def pow120(x):
+    """exp_fma(log_fma(x) * (1.0 / 120.0)): the controller's EEst2^(1/120) as the device computes it"""
+    x = np.ascontiguousarray(x, np.float64)
+    y = np.zeros_like(x)
+    lib().cc_pow120(P(x), C.c_int64(x.size), P(y))
+    return y
+
+
+def _minmax(which, a, b):
+    a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+    y = np.zeros_like(a)
+    lib().cc_minmax(C.c_int(which), P(a), P(b), C.c_int64(a.size), P(y))
+    return y
+
+
+def fmax_abs(a, b):
+    return _minmax(0, a, b)
+
+
+def fmin_q(a, b):
+    return _minmax(1, a, b)
+
+
+def fmax_q(a, b):
+    return _minmax(2, a, b)
+
+
+def rclamp(r, rns):
+    return _minmax(3, r, rns)
+
+
 def cyclotron_wc(p, pos, t):
     """ω_c [eV] (cyclotron_wc_cart) at the n Cartesian points pos (3, n) and times t (n)"""
     pos, t = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(t, np.float64)
