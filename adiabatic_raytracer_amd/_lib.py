@@ -34,6 +34,11 @@ class CyclotronOut(C.Structure):  # include/art.h art_cyclotron_out
     _fields_ = [("tau", C.c_void_p), ("count", C.c_void_p), ("pos", C.c_void_p), ("ln_t", C.c_void_p)]
 
 
+class SkySpec(C.Structure):  # include/art.h art_sky_spec
+    _fields_ = [("n_theta", C.c_int32), ("n_phi", C.c_int32), ("n_dw", C.c_int32), ("theta_axis", C.c_int32),
+                ("mode", C.c_int32), ("dw_lo", C.c_double), ("dw_hi", C.c_double)]
+
+
 # name -> (restype, argtypes); the test suite checks this table against include/art.h
 class TreeOpts(C.Structure):  # include/art.h art_tree_opts
     _fields_ = [("num_cutoff", C.c_int32), ("mc_nodes", C.c_int32), ("max_nodes", C.c_int32),
@@ -91,6 +96,9 @@ SIGNATURES = {
     "art_set_sampler_waves": (C.c_int, [_i32]),
     "art_flux_histogram_phi_device": (C.c_int, [_i64, _v, _v, _v, _i32, _v, _v]),
     "art_flux_histogram_phi_range_device": (C.c_int, [_i64, _v, _v, _v, _i32, _d, _d, _v, _v]),
+    "art_histogram3_device": (C.c_int, [_i64, _v, _v, _v, _v, _v, C.POINTER(_i32), C.POINTER(_d), C.POINTER(_d), _i32, _v,
+                                        _v]),
+    "art_sky_map_segments_device": (C.c_int, [_P, C.POINTER(SkySpec), _i64, _v, _v, _v, _v, _v, _v, _v, _v, _v, _v]),
     "art_comm_unique_id": (C.c_int, [_v]),
     "art_comm_init": (C.c_int, [_i32, _i32, _v]),
     "art_flux_allreduce": (C.c_int, [_v, _i64, _v]),
@@ -108,6 +116,9 @@ SIGNATURES = {
 }
 # include/art.h ART_MATH_*: the function ids of art_eval_math_device
 MATH_FN = {"SINCOS": 0, "EXP": 1, "LOG": 2, "RCP": 3, "POW120": 4, "MAX_ABS": 5, "MIN_Q": 6, "MAX_Q": 7, "RCLAMP": 8}
+
+# the sky maps' θ axis (art_sky_spec.theta_axis) and its range
+THETA_AXIS = {"theta": 0, "cos": 1}
 
 _lib = None
 

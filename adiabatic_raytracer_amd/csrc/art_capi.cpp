@@ -2256,6 +2256,73 @@ int art_flux_histogram_phi_range_device(int64_t n, const double* phi, const int8
   return ART_OK;
 }
 
+// The argument checks the two sky-map entry points share (no device is touched): the axes of a
+// table of at most SKY_MAX_DOUBLES doubles, and a mode the table allows.
+static int sky_axes(const int32_t nbins[3], const double lo[3], const double hi[3], bool c_all, int32_t mode,
+                    art::SkyAxes* A) {
+  if (mode < 0 || mode > 2) return fail(ART_E_INVALID, "sky map mode must be 0 (auto), 1 (LDS table) or 2 (global adds)");
+  int64_t table = 2;
+  for (int d = 0; d < 3; ++d) {
+    if (nbins[d] < 1) return fail(ART_E_INVALID, "sky map bin counts must be >= 1");
+    if (nbins[d] > art::SKY_MAX_DOUBLES / table) return fail(ART_E_INVALID, "sky map table exceeds 2^26 doubles");
+    table *= nbins[d];
+    A->n[d] = nbins[d];
+    if (d == 2 && c_all) {
+      A->lo[d] = A->hi[d] = 0.0;
+      continue;
+    }
+    if (!std::isfinite(lo[d]) || !std::isfinite(hi[d]) || !(lo[d] < hi[d]))
+      return fail(ART_E_INVALID, "sky map ranges need finite lo < hi");
+    A->lo[d] = lo[d];
+    A->hi[d] = hi[d];
+  }
+  A->c_all = c_all;
+  if (mode == 1 && table > art::SKY_LDS_DOUBLES)
+    return fail(ART_E_INVALID, "sky map mode 1: the table exceeds the LDS budget of 8192 doubles");
+  return ART_OK;
+}
+
+int art_histogram3_device(int64_t n, const double* a, const double* b, const double* c, const int8_t* species,
+                          const double* w, const int32_t nbins[3], const double lo[3], const double hi[3], int32_t mode,
+                          double* hist, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
+  if (!nbins || !lo || !hi) return fail(ART_E_INVALID, "NULL nbins, lo or hi");
+  art::SkyAxes A;
+  int rc = sky_axes(nbins, lo, hi, false, mode, &A);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  if (!a || !b || !c || !hist) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  HIP_OK(art::launch_sky_map(n, a, b, c, species, w, A, mode, hist, pick(ctx, stream)));
+  return ART_OK;
+}
+
+int art_sky_map_segments_device(const art_params* p, const art_sky_spec* spec, int64_t n, const double* x_end,
+                                const double* k_end, const double* u7_end, const int32_t* status, const int8_t* species,
+                                const double* w, const double* dw_offset, double* hist, int32_t* bin_out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
+  if (!spec) return fail(ART_E_INVALID, "NULL spec");
+  if (spec->theta_axis != 0 && spec->theta_axis != 1)
+    return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
+  const int32_t nbins[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
+  const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
+  const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
+  art::SkyAxes A;
+  if ((rc = sky_axes(nbins, lo, hi, spec->n_dw == 1, spec->mode, &A))) return rc;
+  if (n == 0) return ART_OK;
+  if (!x_end || !k_end || !u7_end || !status || !hist) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  HIP_OK(art::launch_sky_map_segments(art::make_kparams(*p), n, x_end, k_end, u7_end, status, species, w, dw_offset, A,
+                                      spec->theta_axis, spec->mode, hist, bin_out, pick(ctx, stream)));
+  return ART_OK;
+}
+
 int art_eval_rhs_device(const art_params* p, int64_t n, const double* u, const double* tau, const double* erg,
                         const int8_t* species, double* du, void* stream) {
   std::lock_guard<std::mutex> lk(g_mu);

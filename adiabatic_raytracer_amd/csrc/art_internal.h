@@ -230,6 +230,24 @@ hipError_t launch_flux(const KParams& P, int64_t n, const double* x_end, const d
                        const int8_t* species, const double* w, int32_t nbins, double* hist, hipStream_t s);
 hipError_t launch_flux_phi(int64_t n, const double* phi, const int8_t* species, const double* w, int32_t nbins,
                            double lo, double hi, double* hist, hipStream_t s);
+// Sky maps (sky_map_kernel, sky_map_segments_kernel): n[d] equal bins over [lo[d], hi[d]] on each of
+// the three axes; c_all: the third axis is one bin holding every finite value (n[2] = 1).
+struct SkyAxes {
+  int32_t n[3];
+  int32_t c_all;
+  double lo[3], hi[3];
+};
+// The largest table (2 n[0] n[1] n[2] doubles) a block keeps in LDS: 64 KiB, which leaves two
+// blocks on a CU's 160 KiB; larger tables are added to in HBM.
+constexpr int64_t SKY_LDS_DOUBLES = 8192;
+constexpr int64_t SKY_MAX_DOUBLES = (int64_t)1 << 26;
+// mode: 0 by the table's size, 1 the LDS table (the table must fit), 2 adds to HBM
+hipError_t launch_sky_map(int64_t n, const double* a, const double* b, const double* c, const int8_t* species,
+                          const double* w, const SkyAxes& A, int mode, double* hist, hipStream_t s);
+hipError_t launch_sky_map_segments(const KParams& P, int64_t n, const double* x_end, const double* k_end,
+                                   const double* u7_end, const int32_t* status, const int8_t* species, const double* w,
+                                   const double* dw_offset, const SkyAxes& A, int cos_axis, int mode, double* hist,
+                                   int32_t* bin_out, hipStream_t s);
 hipError_t launch_eval_rhs(const KParams& P, int64_t n, const double* u, const double* tau, const double* erg,
                            const int8_t* species, double* du, hipStream_t s);
 hipError_t launch_eval_hamiltonian(const KParams& P, int64_t n, const double* x, const double* k, const double* T,

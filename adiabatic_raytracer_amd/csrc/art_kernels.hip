@@ -527,9 +527,12 @@ __device__ inline int np_hist_bin(double x, int nbins, double lo = -PI, double h
 // segments): is_final -- no crossing and escaped beyond 1.1 rNS (MainRunner.jl:203-209) -- and
 // the azimuth of its momentum binned as np.histogram(range = (-π, π)); -1 = not counted.
 // flux_kernel and the streamed pipeline's helpers (finalize_one) both bin through here.
-__device__ inline int flux_bin_of(const KParams& P, const double* x, const double* k, int status, int nbins) {
+__device__ inline bool end_is_final(const KParams& P, const double* x, int status) {
   const double xr = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-  if (status == ART_STATUS_CROSSING || !(xr > 1.1 * P.rNS)) return -1;
+  return !(status == ART_STATUS_CROSSING || !(xr > 1.1 * P.rNS));
+}
+__device__ inline int flux_bin_of(const KParams& P, const double* x, const double* k, int status, int nbins) {
+  if (!end_is_final(P, x, status)) return -1;
   return np_hist_bin(atan2(k[1], k[0]), nbins);
 }
 
@@ -3498,6 +3501,92 @@ __global__ __launch_bounds__(256) void flux_phi_kernel(const int64_t n, const do
 }
 
 // ---------------------------------------------------------------------------
+// Sky maps: a weighted 3-D histogram per species, hist[((s na + ia) nb + ib) nc + ic] (axions
+// s = 0, photons s = 1), every axis np_hist_bin over its closed range -- np.histogramdd(range =,
+// bins =) per species. An item outside the range (or NaN) on any axis is dropped.
+__device__ inline int sky_bin_of(const SkyAxes& A, double a, double b, double c, int row) {
+  const int ia = np_hist_bin(a, A.n[0], A.lo[0], A.hi[0]);
+  const int ib = np_hist_bin(b, A.n[1], A.lo[1], A.hi[1]);
+  // (c_all: one bin that holds every finite c, a range no pair of doubles spans)
+  const int ic = A.c_all ? ((c - c == 0.0) ? 0 : -1) : np_hist_bin(c, A.n[2], A.lo[2], A.hi[2]);
+  if ((ia | ib | ic) < 0) return -1;
+  return ((row * A.n[0] + ia) * A.n[1] + ib) * A.n[2] + ic;
+}
+
+// The accumulation both sky-map kernels share. item(i, v) gives item i's flat bin (-1: not
+// counted) and its weight. LDS: a block-private table of `table` doubles, zeroed, added to with
+// LDS atomics and flushed once per block (its non-zero bins), as flux_phi_kernel does. Otherwise
+// float64 adds straight to the table in HBM (hist must be ordinary device memory: the hardware
+// add is not defined on fine-grained host memory); lanes of a wave in the same bin are not
+// combined first: on a flat batch's directions that changed nothing ("sky maps").
+template <bool LDS, class Item>
+__device__ inline void sky_accumulate(const int64_t n, const int table, double* __restrict__ hist, double* sh,
+                                      const Item& item) {
+  if (LDS) {
+    for (int b = threadIdx.x; b < table; b += blockDim.x) sh[b] = 0.0;
+    __syncthreads();
+  }
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < n; i0 += stride) {
+    const int64_t i = i0 + threadIdx.x;
+    double v = 0.0;
+    int idx = i < n ? item(i, v) : -1;
+    if (LDS) {
+      if (idx >= 0) atomicAdd(&sh[idx], v);
+      continue;
+    }
+    if (idx >= 0) unsafeAtomicAdd(&hist[idx], v);
+  }
+  if (LDS) {
+    __syncthreads();
+    for (int b = threadIdx.x; b < table; b += blockDim.x)
+      if (sh[b] != 0.0) unsafeAtomicAdd(&hist[b], sh[b]);
+  }
+}
+
+// The histogram of n items with coordinates (a, b, c), species flag and weight w (null: 1).
+template <bool LDS>
+__global__ __launch_bounds__(1024) void sky_map_kernel(const int64_t n, const double* __restrict__ a,
+                                                        const double* __restrict__ b, const double* __restrict__ c,
+                                                        const int8_t* __restrict__ species,
+                                                        const double* __restrict__ w, const SkyAxes A,
+                                                        double* __restrict__ hist) {
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  sky_accumulate<LDS>(n, 2 * A.n[0] * A.n[1] * A.n[2], hist, sh, [&](int64_t i, double& v) {
+    v = w ? w[i] : 1.0;
+    return sky_bin_of(A, a[i], b[i], c[i], (species && species[i] == ART_AXION) ? 0 : 1);
+  });
+}
+
+// The sky map of a propagated batch from its end states in HBM: the final segments (flux_bin_of's
+// rule) binned over (θf or cos θf, φf, Δω) of trees.py's rows: |k| = sqrt(kx² + ky² + kz²),
+// cos θf = kz / |k|, θf = acos(cos θf), φf = atan2(ky, kx), Δω = u7_end / mass_a + dw_offset,
+// every operation rounded on its own as numpy rounds them. bin_out (may be null): each ray's
+// flat bin, -1 for not counted.
+template <bool LDS>
+__global__ __launch_bounds__(1024) void sky_map_segments_kernel(
+    const KParams P, const int64_t n, const double* __restrict__ x_end, const double* __restrict__ k_end,
+    const double* __restrict__ u7_end, const int32_t* __restrict__ status, const int8_t* __restrict__ species,
+    const double* __restrict__ w, const double* __restrict__ dw_offset, const SkyAxes A, const int cos_axis,
+    double* __restrict__ hist, int32_t* __restrict__ bin_out) {
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  sky_accumulate<LDS>(n, 2 * A.n[0] * A.n[1] * A.n[2], hist, sh, [&](int64_t i, double& v) {
+    const double x[3] = {x_end[i], x_end[n + i], x_end[2 * n + i]};
+    int idx = -1;
+    if (end_is_final(P, x, status[i])) {
+#pragma clang fp contract(off)
+      const double kx = k_end[i], ky = k_end[n + i], kz = k_end[2 * n + i];
+      const double ct = kz / sqrt(kx * kx + ky * ky + kz * kz);
+      const double dw = u7_end[i] / P.mass_a + (dw_offset ? dw_offset[i] : 0.0);
+      idx = sky_bin_of(A, cos_axis ? ct : acos(ct), atan2(ky, kx), dw, (species && species[i] == ART_AXION) ? 0 : 1);
+    }
+    if (bin_out) bin_out[i] = idx;
+    v = w ? w[i] : 1.0;
+    return idx;
+  });
+}
+
+// ---------------------------------------------------------------------------
 // Pointwise physics for parity tests.
 __global__ void eval_rhs_kernel(const KParams P, const int64_t n, const double* __restrict__ u,
                                 const double* __restrict__ tau, const double* __restrict__ erg,
@@ -3951,6 +4040,50 @@ hipError_t launch_flux_phi(int64_t n, const double* phi, const int8_t* species, 
   if (grid < 1) grid = 1;
   hipLaunchKernelGGL(flux_phi_kernel, dim3((unsigned)grid), dim3(256), 2 * nbins * sizeof(double), s, n, phi, species, w,
                      nbins, lo, hi, hist);
+  return hipGetLastError();
+}
+
+// The sky-map launches' geometry. LDS path (mode 1, or 0 with a table within SKY_LDS_DOUBLES): the
+// blocks that are resident at once and no more, since each pays for zeroing and flushing its
+// table: 256 threads while 8 tables fit a CU's 160 KiB, else 1024 (two 64 KiB tables still leave
+// two blocks, 32 waves, on a CU). Global path: flux_kernel's grid. Every thread takes at least 4
+// items, so small batches also run the grid-stride loop.
+struct SkyLaunch {
+  bool lds;
+  int block;
+  unsigned grid;
+  size_t shmem;
+};
+static SkyLaunch sky_launch(int64_t n, const SkyAxes& A, int mode) {
+  const int64_t table = 2 * (int64_t)A.n[0] * A.n[1] * A.n[2];
+  SkyLaunch L;
+  L.lds = mode == 1 || (mode == 0 && table <= SKY_LDS_DOUBLES);
+  L.shmem = L.lds ? (size_t)table * sizeof(double) : 0;
+  L.block = L.shmem > 16384 ? 1024 : 256;
+  int64_t per_cu = 2048 / L.block;
+  if (L.lds && (int64_t)(163840 / L.shmem) < per_cu) per_cu = 163840 / L.shmem;
+  int64_t grid = (n + 4 * L.block - 1) / (4 * L.block);
+  if (grid > 256 * per_cu) grid = 256 * per_cu;
+  L.grid = (unsigned)(grid < 1 ? 1 : grid);
+  return L;
+}
+
+hipError_t launch_sky_map(int64_t n, const double* a, const double* b, const double* c, const int8_t* species,
+                          const double* w, const SkyAxes& A, int mode, double* hist, hipStream_t s) {
+  const SkyLaunch L = sky_launch(n, A, mode);
+  const auto fn = L.lds ? &sky_map_kernel<true> : &sky_map_kernel<false>;
+  hipLaunchKernelGGL(fn, dim3(L.grid), dim3(L.block), L.shmem, s, n, a, b, c, species, w, A, hist);
+  return hipGetLastError();
+}
+
+hipError_t launch_sky_map_segments(const KParams& P, int64_t n, const double* x_end, const double* k_end,
+                                   const double* u7_end, const int32_t* status, const int8_t* species, const double* w,
+                                   const double* dw_offset, const SkyAxes& A, int cos_axis, int mode, double* hist,
+                                   int32_t* bin_out, hipStream_t s) {
+  const SkyLaunch L = sky_launch(n, A, mode);
+  const auto fn = L.lds ? &sky_map_segments_kernel<true> : &sky_map_segments_kernel<false>;
+  hipLaunchKernelGGL(fn, dim3(L.grid), dim3(L.block), L.shmem, s, P, n, x_end, k_end, u7_end, status, species, w, dw_offset,
+                     A, cos_axis, hist, bin_out);
   return hipGetLastError();
 }
 

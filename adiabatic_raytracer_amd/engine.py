@@ -122,6 +122,30 @@ class Engine:
                                                  _stream()))
         return hist
 
+    # ---- sky map: flux over (θf | cos θf, φf, Δω) per species (art_sky_map_segments_device)
+    def sky_map(self, out: dict, species, weights=None, *, n_theta: int = 32, n_phi: int = 64, n_dw: int = 1,
+                theta_axis: str = "cos", dw_range=None, dw_offset=None, hist=None, return_bins: bool = False,
+                mode: int = 0):
+        """The batch's final segments binned by the direction and line shift of their final momentum,
+        on the current stream: a (2, n_theta, n_phi, n_dw) float64 tensor (axions, photons), added to
+        `hist` when one is given. theta_axis "cos" bins cos θf over [-1, 1] (equal solid angle),
+        "theta" θf over [0, π]; φf over [-π, π]; Δω = u7_end / mass_a + dw_offset over dw_range, which
+        n_dw > 1 needs (n_dw = 1 is one bin for every finite Δω). return_bins: also each ray's flat
+        bin index (int32, -1 for a ray that is not counted). mode: 0 picks the accumulation path by the
+        table's size, 1 forces the block-private LDS table, 2 adds to HBM (include/art.h)."""
+        n = out["status"].numel()
+        if n_dw > 1 and dw_range is None:
+            raise ValueError("sky_map: n_dw > 1 needs dw_range")
+        lo, hi = (0.0, 0.0) if dw_range is None else (float(dw_range[0]), float(dw_range[1]))
+        spec = _lib.SkySpec(int(n_theta), int(n_phi), int(n_dw), _lib.THETA_AXIS[theta_axis], int(mode), lo, hi)
+        if hist is None:
+            hist = torch.zeros(2, n_theta, n_phi, n_dw, dtype=F64, device=self.device)
+        bins = self.empty(n, dtype=torch.int32) if return_bins else None
+        check(self.lib.art_sky_map_segments_device(C.byref(self.cp), C.byref(spec), n, _p(out["x_end"]), _p(out["k_end"]),
+                                                   _p(out["u7_end"]), _p(out["status"]), _p(species), _p(weights),
+                                                   _p(dw_offset), _p(hist), _p(bins), _stream()))
+        return (hist, bins) if return_bins else hist
+
     # ---- get_Prob_nonAD (MainRunner.jl:67-124)
     def get_prob_nonad(self, pos, kpos, erg_eff, group_start=None):
         nc = erg_eff.numel()

@@ -161,7 +161,8 @@ def save_node(fh, node, tr, q):
 
 def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_DM=0.45, n_maxSample=6,
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
-                     file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False):
+                     file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
+                     sky_map=None):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -189,9 +190,26 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     escaping photons' cyclotron-resonance optical depth τ (cyclotron_optical_depth) goes into
     column 14 (saveMode > 0) and column 8, the weight (weight_tmp, :707-708), is multiplied by
     exp(-τ), so the flux of run_info is the absorbed one; columns 13 (the tree weight) and 15
-    (weightC) stay. With the default False every row, file and histogram is unchanged."""
+    (weightC) stay. With the default False every row, file and histogram is unchanged.
+
+    sky_map (beyond the reference; a dict of sky_map()'s keywords n_theta, n_phi, n_dw, theta_axis,
+    dw_range, or {} for its defaults): the rows' flux binned over (θf or cos θf, φf, Δω) per species
+    with the weights of run_info["flux"], summed over the ranks in the same all-reduce and divided
+    by the global f_inx: run_info["sky_map"] (2, n_theta, n_phi, n_dw) and run_info["sky_map_edges"];
+    with dir_tag also saved beside the npy as skymap_<its stem>.npz (sky_map, theta_edges, phi_edges,
+    dw_edges, theta_axis, f_inx). n_dw > 1 without a dw_range bins Δω over (min, max) of the rows
+    (numpy's rule, flux_range), which only one process can do: with world > 1 it is an error. With
+    the default None every row, file, run_info key and the reduced vector are unchanged."""
     if saveMode < 3:
         ntimes = 3  # "Times to store in ODE" (MainRunner.jl:379-381): also names the npy file
+    if sky_map is not None:
+        sky_kw = {"n_theta": 32, "n_phi": 64, "n_dw": 1, "theta_axis": "cos", "dw_range": None}
+        if set(sky_map) - set(sky_kw):
+            raise ValueError(f"sky_map: unknown keys {sorted(set(sky_map) - set(sky_kw))}")
+        sky_kw.update(sky_map)
+        _theta_range(sky_kw["theta_axis"])
+        if sky_kw["n_dw"] > 1 and sky_kw["dw_range"] is None and world > 1:
+            raise ValueError("sky_map: n_dw > 1 needs a dw_range when world > 1 (the ranks' rows span different Δω)")
     import time
     from .shard import allreduce_sum, shard_range
     t_start = time.perf_counter()
@@ -260,22 +278,38 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     want_flux = len(rows) and (world > 1 or run_info is not None)
     flux = radiated_flux(rows[:, 3], rows[:, 1], rows[:, 8] * rows[:, 7], nbins) if want_flux else np.zeros(2 * nbins)
     pps = rows[:, 8] * rows[:, 7] if len(rows) else np.zeros(0)
-    tot = np.concatenate([flux, [float(f_inx), float(pps[rows[:, 1] == 0].sum()) if len(rows) else 0.0,
-                                 float(pps[rows[:, 1] == 1].sum()) if len(rows) else 0.0, float(len(rows))]])
+    sky = sky_shape = None
+    if sky_map is not None:  # the rows' sky map, the flux's weights (every rank adds its part)
+        sky_shape = (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
+        if sky_kw["n_dw"] > 1 and sky_kw["dw_range"] is None:
+            sky_kw["dw_range"] = flux_range(rows[:, 12])
+        sky = np.zeros(sky_shape)
+        if len(rows):
+            sky = _sky_map_rows(rows[:, 2], rows[:, 3], rows[:, 12], rows[:, 1], pps, **sky_kw)
+    tot = pack_totals(flux, f_inx, pps[rows[:, 1] == 0].sum() if len(rows) else 0.0,
+                      pps[rows[:, 1] == 1].sum() if len(rows) else 0.0, len(rows), sky)
     if world > 1:
         tot = allreduce_sum(tot)
-    f_glob = tot[2 * nbins]
+    tt = unpack_totals(tot, nbins, sky_shape)
+    f_glob = tt["f_inx"]
     if len(rows):
         rows[:, 7] /= f_glob  # saveAll[:, 8] ./= f_inx (:747), the whole run's f_inx
     if run_info is not None:
-        run_info.update(f_inx=int(round(f_glob)), flux=(tot[:2 * nbins] / f_glob).reshape(2, nbins),
-                        sum_weight_sln_prob=(tot[2 * nbins + 1] / f_glob, tot[2 * nbins + 2] / f_glob),
-                        rows=int(round(tot[2 * nbins + 3])), events=(lo, hi), n_events=n_glob)
+        run_info.update(f_inx=int(round(f_glob)), flux=(tt["flux"] / f_glob).reshape(2, nbins),
+                        sum_weight_sln_prob=(tt["sum_axion"] / f_glob, tt["sum_photon"] / f_glob),
+                        rows=int(round(tt["rows"])), events=(lo, hi), n_events=n_glob)
+        if sky_map is not None:
+            run_info.update(sky_map=tt["sky"] / f_glob, sky_map_edges=sky_map_edges(**sky_kw))
     if dir_tag is not None:
         path = tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul, params.B0, Ntajs,
                               ntimes, num_cutoff, MC_nodes, max_nodes, tag)
         os.makedirs(os.path.dirname(path), exist_ok=True)
         np.save(path, rows)
+        if sky_map is not None:
+            te, pe, de = sky_map_edges(**sky_kw)
+            stem = os.path.splitext(os.path.basename(path))[0]
+            np.savez(os.path.join(os.path.dirname(path), f"skymap_{stem}.npz"), sky_map=tt["sky"] / f_glob,
+                     theta_edges=te, phi_edges=pe, dw_edges=de, theta_axis=sky_kw["theta_axis"], f_inx=int(round(f_glob)))
     return rows
 
 
@@ -340,6 +374,100 @@ def flux_range(phif):
 def flux_edges(lo, hi, nbins=50):
     """The bin edges np.histogram uses for `nbins` equal bins of [lo, hi] (np.linspace)."""
     return np.linspace(lo, hi, nbins + 1)
+
+
+def _theta_range(theta_axis):
+    if theta_axis not in _lib.THETA_AXIS:
+        raise ValueError(f"theta_axis must be 'cos' or 'theta', not {theta_axis!r}")
+    return (-1.0, 1.0) if theta_axis == "cos" else (0.0, np.pi)
+
+
+def sky_map_edges(n_theta=32, n_phi=64, n_dw=1, theta_axis="cos", dw_range=None):
+    """The bin edges of sky_map's three axes, as np.histogramdd returns them (np.linspace):
+    cos θf over [-1, 1] or θf over [0, π], φf over [-π, π], Δω over dw_range. With n_dw = 1 and no
+    dw_range the Δω axis is one bin for every finite value: edges (-inf, inf)."""
+    lo, hi = _theta_range(theta_axis)
+    if dw_range is None:
+        if n_dw != 1:
+            raise ValueError("sky_map: n_dw > 1 needs dw_range")
+        dw_edges = np.array([-np.inf, np.inf])
+    else:
+        dw_edges = np.linspace(float(dw_range[0]), float(dw_range[1]), n_dw + 1)
+    return np.linspace(lo, hi, n_theta + 1), np.linspace(-np.pi, np.pi, n_phi + 1), dw_edges
+
+
+def sky_map(theta_f, phi_f, dw, ident, weights=None, *, n_theta=32, n_phi=64, n_dw=1, theta_axis="cos", dw_range=None,
+            mode=0) -> np.ndarray:
+    """The sky map of npy rows on the GPU (art_histogram3_device): np.histogramdd of (θf or cos θf,
+    φf, Δω) -- columns 2, 3 and 12 -- with `weights` (the radiated power: column 8 * column 7; None
+    counts rows), for axion rows (ident 0, column 1) in [0] and photon rows in [1]: a
+    (2, n_theta, n_phi, n_dw) array over sky_map_edges(...). theta_axis "cos" takes np.cos(theta_f) on
+    the host, so the device bins numpy's values. A row outside a range, or NaN, on any axis is dropped;
+    with n_dw = 1 and no dw_range every row with a finite Δω counts. mode: the accumulation path
+    (0 by the table's size, 1 LDS, 2 HBM; include/art.h)."""
+    import torch
+    lib = _lib.load()
+    th = np.asarray(theta_f, np.float64)
+    a = np.cos(th) if theta_axis == "cos" else th
+    c = np.asarray(dw, np.float64)
+    lo, hi = _theta_range(theta_axis)
+    if dw_range is None:
+        if n_dw != 1:
+            raise ValueError("sky_map: n_dw > 1 needs dw_range")
+        c, dw_range = np.where(np.isfinite(c), 0.0, np.nan), (-1.0, 1.0)
+    n = a.size
+    dev = torch.device("cuda", torch.cuda.current_device())
+    f = lambda v, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(v), dtype=dt).to(dev)  # noqa: E731
+    da, db, dc, sp = f(a), f(np.asarray(phi_f, np.float64)), f(c), f(np.asarray(ident) != 0, torch.int8)
+    ww = None if weights is None else f(weights)
+    hist = torch.zeros(2, n_theta, n_phi, n_dw, dtype=torch.float64, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    check(lib.art_histogram3_device(n, ptr(da), ptr(db), ptr(dc), ptr(sp), ptr(ww), (C.c_int32 * 3)(n_theta, n_phi, n_dw),
+                                    (C.c_double * 3)(lo, -np.pi, float(dw_range[0])),
+                                    (C.c_double * 3)(hi, np.pi, float(dw_range[1])), int(mode), ptr(hist),
+                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return hist.cpu().numpy()
+
+
+_sky_map_rows = sky_map  # (main_runner_tree's keyword of the same name hides the function there)
+
+
+def pulse_profile(sky, theta_obs, theta_axis="cos", species=PHOTON):
+    """The pulse profile an observer at inclination theta_obs [rad] sees: the φf row of the θ bin
+    that holds theta_obs (numpy's bin rule: an edge belongs to the bin on its right, π to the last),
+    summed over Δω. The magnetosphere is stationary in the corotating frame and every sample starts at
+    the same rotational phase, so φf at fixed θf is the rotational phase. With theta_axis "cos" the
+    row is divided by the bin's solid angle (2 / n_theta)(2π / n_phi): power per steradian. Returns
+    (profile, the φ bin centres). sky: (2, n_theta, n_phi, n_dw), as sky_map and run_info give it."""
+    sky = np.asarray(sky)
+    _, n_theta, n_phi, _ = sky.shape
+    lo, hi = _theta_range(theta_axis)
+    x = math.cos(theta_obs) if theta_axis == "cos" else float(theta_obs)
+    if not lo <= x <= hi:
+        raise ValueError(f"theta_obs = {theta_obs} lies outside the map")
+    edges = np.linspace(lo, hi, n_theta + 1)
+    row = min(int(np.searchsorted(edges, x, side="right")) - 1, n_theta - 1)
+    prof = sky[species, row].sum(axis=-1)
+    if theta_axis == "cos":
+        prof = prof / ((2.0 / n_theta) * (2.0 * np.pi / n_phi))
+    phi_edges = np.linspace(-np.pi, np.pi, n_phi + 1)
+    return prof, 0.5 * (phi_edges[:-1] + phi_edges[1:])
+
+
+def pack_totals(flux, f_inx, sum_axion, sum_photon, n_rows, sky=None) -> np.ndarray:
+    """A rank's part of main_runner_tree's single all-reduce: [flux (2 nbins) | f_inx | Σ weight *
+    sln_prob (axions, photons) | rows], then the sky map's table when there is one."""
+    tot = np.concatenate([flux, [float(f_inx), float(sum_axion), float(sum_photon), float(n_rows)]])
+    return tot if sky is None else np.concatenate([tot, np.asarray(sky, np.float64).reshape(-1)])
+
+
+def unpack_totals(tot, nbins, sky_shape=None) -> dict:
+    """The parts of a pack_totals vector (sky_shape: the map's (2, n_theta, n_phi, n_dw), or None)."""
+    m = 2 * nbins
+    out = {"flux": tot[:m], "f_inx": tot[m], "sum_axion": tot[m + 1], "sum_photon": tot[m + 2], "rows": tot[m + 3]}
+    if sky_shape is not None:
+        out["sky"] = tot[m + 4:m + 4 + int(np.prod(sky_shape))].reshape(sky_shape)
+    return out
 
 
 def gather_rank_rows(dir_tag, params: Params, Ntajs, world, file_tag="", ntimes=3, num_cutoff=5, MC_nodes=5,

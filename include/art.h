@@ -19,6 +19,9 @@
  *   art_flux_histogram_device      plot/flux.py:38-48 (binned flux of segment end states)
  *   art_flux_histogram_phi_device  plot/flux.py:38-48 (binned flux of the npy rows' φf;
  *   art_flux_histogram_phi_range_device  _range: over flux.py's data-dependent bins)
+ *   art_histogram3_device          np.histogramdd of rows over (θf | cos θf, φf, Δω), per species
+ *   art_sky_map_segments_device    the same map of a propagated batch's end states (no reference
+ *                                  counterpart: its plot scripts leave Δω "NOT implemented")
  *   art_propagate_host_flux        RT.propagate + the batch's binned flux (bench.py's step)
  *   art_propagate_host_flux_async  the same, two batches in flight; art_host_wait
  *   art_comm_* / art_flux_allreduce  the reduction of the flux and counters over the GPUs of
@@ -444,6 +447,39 @@ int art_flux_histogram_phi_device(int64_t n, const double* phi, const int8_t* sp
  * bins (edges linspace(lo, hi, nbins + 1), numpy's bin assignment). */
 int art_flux_histogram_phi_range_device(int64_t n, const double* phi, const int8_t* species, const double* w,
                                         int32_t nbins, double lo, double hi, double* hist, void* stream);
+
+/* ---- sky maps: a weighted 3-D histogram per species (beyond the reference, whose plot scripts
+ * stop at the 1-D azimuth histogram above). hist[((s*na + ia)*nb + ib)*nc + ic] (device, float64,
+ * ACCUMULATED into; ordinary device memory), s = 0 axions, 1 photons. Each axis has nbins[d]
+ * equal bins over the closed range [lo[d], hi[d]] with numpy's bin assignment, so
+ * np.histogramdd(range =, bins =) of one species' items is the same table; an item outside the
+ * range, or NaN, on any axis is dropped. w NULL = 1; species NULL = photons. Counts are exact;
+ * weighted sums depend on the order the adds arrive in and differ in the last bits between runs.
+ * mode: 0 picks the accumulation path by the table's size, 1 forces the block-private LDS table
+ * (2*na*nb*nc <= 8192), 2 forces adds to device memory. ART_E_INVALID, before any device is
+ * touched: n < 0, a bin count < 1, a non-finite or empty range, an unknown mode, a table of more
+ * than 2^26 doubles, mode 1 with a table over the LDS budget. */
+int art_histogram3_device(int64_t n, const double* a, const double* b, const double* c,
+                          const int8_t* species, const double* w,
+                          const int32_t nbins[3], const double lo[3], const double hi[3],
+                          int32_t mode, double* hist, void* stream);
+
+/* The sky map of a propagated batch, straight from the device-resident outputs of
+ * art_propagate_device: the final segments (art_flux_histogram_device's rule) binned over
+ * (θf or cos θf, φf, Δω) of the final momentum: cos θf = kz / |k|, θf = acos(cos θf),
+ * φf = atan2(ky, kx) over [-π, π], Δω = u7_end / mass_a + dw_offset (NULL = 0; the rows' column 13,
+ * MainRunner.jl:709). bin_out (n, int32, may be NULL): each ray's flat index into hist, -1 for
+ * not counted. */
+typedef struct art_sky_spec {
+  int32_t n_theta, n_phi, n_dw;   /* each >= 1 */
+  int32_t theta_axis;             /* 0: θf over [0, π]; 1: cos θf over [-1, 1] (equal solid angle) */
+  int32_t mode;                   /* 0 auto, 1 LDS table, 2 global adds */
+  double  dw_lo, dw_hi;           /* range of Δω; ignored when n_dw == 1 (one bin holding every finite Δω) */
+} art_sky_spec;
+int art_sky_map_segments_device(const art_params* p, const art_sky_spec* spec, int64_t n,
+                                const double* x_end, const double* k_end, const double* u7_end,
+                                const int32_t* status, const int8_t* species, const double* w,
+                                const double* dw_offset, double* hist, int32_t* bin_out, void* stream);
 
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the

@@ -76,6 +76,29 @@ int main() {
         ART_E_INVALID);
   CHECK(art_flux_histogram_phi_device(n, nullptr, nullptr, nullptr, 50, nullptr, nullptr) == ART_E_INVALID);
   CHECK(art_flux_histogram_phi_device(-1, nullptr, nullptr, nullptr, 50, nullptr, nullptr) == ART_E_INVALID);
+  // the sky maps: every argument check comes before the device, n = 0 touches nothing
+  {
+    const int32_t nb[3] = {3, 5, 2}, nb0[3] = {3, 0, 2}, big[3] = {4096, 4096, 4}, wide[3] = {64, 128, 16};
+    const double l3[3] = {0.0, -1.0, 0.0}, h3[3] = {1.0, 1.0, 2.0}, hnan[3] = {1.0, NAN, 2.0}, hempty[3] = {1.0, -1.0, 2.0};
+    double* d = x.data();
+    CHECK(art_histogram3_device(-1, d, d, d, nullptr, nullptr, nb, l3, h3, 0, d, nullptr) == ART_E_INVALID);
+    CHECK(art_histogram3_device(n, d, d, d, nullptr, nullptr, nb0, l3, h3, 0, d, nullptr) == ART_E_INVALID);
+    CHECK(art_histogram3_device(n, d, d, d, nullptr, nullptr, nb, l3, hnan, 0, d, nullptr) == ART_E_INVALID);
+    CHECK(art_histogram3_device(n, d, d, d, nullptr, nullptr, nb, l3, hempty, 0, d, nullptr) == ART_E_INVALID);
+    CHECK(art_histogram3_device(n, d, d, d, nullptr, nullptr, nb, l3, h3, 3, d, nullptr) == ART_E_INVALID);
+    CHECK(art_histogram3_device(n, d, d, d, nullptr, nullptr, big, l3, h3, 0, d, nullptr) == ART_E_INVALID);
+    CHECK(art_histogram3_device(n, d, d, d, nullptr, nullptr, wide, l3, h3, 1, d, nullptr) == ART_E_INVALID);
+    CHECK(art_histogram3_device(0, nullptr, nullptr, nullptr, nullptr, nullptr, nb, l3, h3, 0, nullptr, nullptr) == ART_OK);
+    art_sky_spec sk{32, 64, 1, 1, 0, 0.0, 0.0};
+    CHECK(art_sky_map_segments_device(&p, &sk, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                      nullptr, nullptr) == ART_OK);
+    sk.theta_axis = 2;
+    CHECK(art_sky_map_segments_device(&p, &sk, n, d, d, d, st.data(), nullptr, nullptr, nullptr, d, nullptr, nullptr) ==
+          ART_E_INVALID);
+    sk.theta_axis = 0; sk.n_dw = 4;  // n_dw > 1 needs a range
+    CHECK(art_sky_map_segments_device(&p, &sk, n, d, d, d, st.data(), nullptr, nullptr, nullptr, d, nullptr, nullptr) ==
+          ART_E_INVALID);
+  }
   // the reduction: nothing to reduce without a communicator, bad ranks rejected
   double h[4] = {1, 2, 3, 4};
   CHECK(art_flux_allreduce(h, 4, nullptr) == ART_E_INVALID);

@@ -32,6 +32,11 @@ hipError_t launch_flux(const KParams&, int64_t, const double*, const double*, co
 hipError_t launch_flux_phi(int64_t, const double*, const int8_t*, const double*, int32_t, double, double, double*, hipStream_t) {
   return hipErrorNoDevice;
 }
+hipError_t launch_sky_map(int64_t, const double*, const double*, const double*, const int8_t*, const double*,
+                          const SkyAxes&, int, double*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_sky_map_segments(const KParams&, int64_t, const double*, const double*, const double*, const int32_t*,
+                                   const int8_t*, const double*, const double*, const SkyAxes&, int, int, double*,
+                                   int32_t*, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_eval_rhs(const KParams&, int64_t, const double*, const double*, const double*, const int8_t*, double*,
                            hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_eval_hamiltonian(const KParams&, int64_t, const double*, const double*, const double*, const double*,
