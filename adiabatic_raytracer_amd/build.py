@@ -9,14 +9,15 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libart.so")
 SOURCES = ["art_kernels.hip", "art_capi.cpp", "art_forest.cpp", "art_kernels_nolicm.hip"]
-HEADERS = ["art_core.h", "art_internal.h", "art_event.h"]
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))  # every header: a new one cannot be forgotten
 ARCH = os.environ.get("ART_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=on: FMA fusion within one source expression only ("FMA contraction").
 # -amdgpu-use-amdgpu-trackers: AMDGPU's own register-pressure trackers in the machine scheduler:
 #   fewer spills of the 256-VGPR integrator and 1% faster (A/B on the 1e7-ray flat batch, round 3).
 # art_kernels_nolicm.hip adds -disable-machine-licm (see its header): the helper, the non-flat
 #   integrators and the tail kernel spill nothing without MachineLICM's hoisted constants (and the GR
-#   ones run 2-3% faster); the flat integrator (art_kernels.hip) runs 3% faster with it.
+#   ones run 2-3% faster); the flat integrator (art_kernels.hip) runs 3% faster with it. The kernels
+#   are headers (art_propagate.h, art_tail.h, ...); each unit instantiates its share of them.
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-mllvm", "-amdgpu-use-amdgpu-trackers=1"]
 # art_kernels.hip (the flat integrator) keeps MachineLICM but lets it sink hoisted instructions back
 #   into the loop where they would spill (-sink-insts-to-avoid-spills): 12-18 spilled VGPRs -> 2-6;

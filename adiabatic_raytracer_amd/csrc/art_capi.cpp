@@ -154,9 +154,7 @@ int current_ctx(DeviceCtx** out) {
   // (and a profiler's finalisation), DESIGN.md §4 "exit".
   static bool at_exit = false;
   if (!at_exit) {
-#ifndef ART_NO_EXIT_RELEASE  // (dev A/B: the round-3 behaviour, static destruction only)
     std::atexit(shutdown_at_exit);
-#endif
     at_exit = true;
   }
   int dev = 0;

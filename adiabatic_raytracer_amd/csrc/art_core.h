@@ -31,8 +31,8 @@
 #define ART_FP_FAST
 #endif
 
-// ART_EXP_ASM (off by default): three-operand FMA Horner steps in exp_fma and a
-// one-instruction radius clamp in inline asm. The backend otherwise keeps the polynomial's
+// Tried in inline asm: three-operand v_fma_f64 Horner steps in exp_fma and a one-instruction
+// v_max_f64 radius clamp with rNS as a scalar operand. The backend otherwise keeps the polynomial's
 // coefficients in VGPRs and copies one into the accumulator before every two-address
 // v_fmac_f64. 1e7 flat rays: 84.34 -> 83.37 ms (profiles/r04b_ab.txt), but (1) the tail kernel
 // and the persistent integrator then no longer agree bit for bit (tests/test_edges.py,
@@ -131,13 +131,7 @@ __host__ __device__ inline double fmax_q(double a, double b) {
 // of a compare and two selects; a NaN radius gives rNS here, and the NaN state itself is
 // what the integrator reports), the select for the op-counting and dual types.
 __host__ __device__ inline double rclamp(double r, double rns) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(ART_EXP_ASM)
-  double m;
-  asm("v_max_f64 %0, %1, %2" : "=v"(m) : "v"(r), "s"(rns));
-  return m;
-#else
   return fmax(r, rns);
-#endif
 }
 template <class T>
 __host__ __device__ inline T rclamp(const T& r, double rns) {
@@ -172,33 +166,22 @@ __host__ __device__ inline double frcp(double x) {
 // <= 1 ulp (tests/test_corecheck.py). No overflow/underflow/NaN special-casing beyond what the
 // arithmetic propagates (e^710 = inf, e^-800 = 0, NaN gives NaN; the integrator's arguments are
 // moderate ln t and ln EEst values).
-// Horner step p r + c as one three-operand v_fma_f64 (the backend otherwise picks the two-
-// address v_fmac_f64 with the coefficient copied into the accumulator: a v_mov_b64 per step)
-__host__ __device__ inline double horner_fma(double p, double r, double c) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(ART_EXP_ASM)
-  double o;
-  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(o) : "v"(p), "v"(r), "v"(c));
-  return o;
-#else
-  return fma(p, r, c);
-#endif
-}
 __host__ __device__ inline double exp_fma(double x) {
   ART_FP_FAST
   const double k = rint(x * 1.4426950408889634);
   double r = fma(-k, 0.6931471805599453, x);
   r = fma(-k, 2.3190468138462996e-17, r);
   double p = 1.0 / 6227020800.0;  // 1/13!
-  p = horner_fma(p, r, 1.0 / 479001600.0);
-  p = horner_fma(p, r, 1.0 / 39916800.0);
-  p = horner_fma(p, r, 1.0 / 3628800.0);
-  p = horner_fma(p, r, 1.0 / 362880.0);
-  p = horner_fma(p, r, 1.0 / 40320.0);
-  p = horner_fma(p, r, 1.0 / 5040.0);
-  p = horner_fma(p, r, 1.0 / 720.0);
-  p = horner_fma(p, r, 1.0 / 120.0);
-  p = horner_fma(p, r, 1.0 / 24.0);
-  p = horner_fma(p, r, 1.0 / 6.0);
+  p = fma(p, r, 1.0 / 479001600.0);
+  p = fma(p, r, 1.0 / 39916800.0);
+  p = fma(p, r, 1.0 / 3628800.0);
+  p = fma(p, r, 1.0 / 362880.0);
+  p = fma(p, r, 1.0 / 40320.0);
+  p = fma(p, r, 1.0 / 5040.0);
+  p = fma(p, r, 1.0 / 720.0);
+  p = fma(p, r, 1.0 / 120.0);
+  p = fma(p, r, 1.0 / 24.0);
+  p = fma(p, r, 1.0 / 6.0);
   p = fma(p, r, 0.5);
   p = fma(p, r, 1.0);
   p = fma(p, r, 1.0);
@@ -273,9 +256,6 @@ __host__ __device__ inline double msin(double x) { return sin(x); }
 __host__ __device__ inline double mcos(double x) { return cos(x); }
 __host__ __device__ inline double macos(double x) { return acos(x); }
 __host__ __device__ inline double matan2(double y, double x) { return atan2(y, x); }
-__host__ __device__ inline double mpow(double x, double p) { return pow(x, p); }
-__host__ __device__ inline bool misnan(double x) { return isnan(x); }
-__host__ __device__ inline double mmax(double a, double b) { return a > b ? a : b; }
 
 // Kernel-side parameters: art_params plus derived constants, passed by value (kernarg ->
 // SGPRs: the NS parameters are wave-uniform scalars, never per-lane data).

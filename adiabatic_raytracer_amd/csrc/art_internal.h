@@ -1,4 +1,5 @@
-// art_internal.h -- launch wrappers shared by art_kernels.hip and art_capi.cpp.
+// art_internal.h -- the launch wrappers and record layouts shared by the two kernel translation
+// units (art_kernels.hip, art_kernels_nolicm.hip), their headers and art_capi.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -196,7 +197,10 @@ hipError_t launch_integrator_streamed(const KParams& P, int64_t n, const SegIn& 
 // announce counts each block into host_flags[64] as it starts.
 hipError_t launch_helpers(const KParams& P, int64_t n, const SegIn& in, const SegOut& out, int blocks, int64_t init_limit,
                           int announce, unsigned long long* stats, hipStream_t s);
-// The helper kernel (art_kernels_nolicm.hip, its own translation unit): the instantiation for these
+// The geometry a kernel is instantiated for: the GEOM_* of art_step.h (0 any, 1 flat, 2 GR). The one
+// classification both translation units select their instantiations by.
+int geom_of(const KParams& P);
+// The helper kernel (art_helper.h, built in art_kernels_nolicm.hip): the instantiation for these
 // parameters' geometry, and its waves per SIMD (2: a helper block shares its CU with one
 // integrator block; 1: it takes the whole CU).
 using HFn = void (*)(const KParams, const int64_t, const SegIn, const SegOut, const int, const int64_t, const int64_t,
@@ -204,7 +208,7 @@ using HFn = void (*)(const KParams, const int64_t, const SegIn, const SegOut, co
 HFn pick_helper(const KParams& P);
 // The integrator (propagate_kernel) and tail kernel builds of art_kernels_nolicm.hip: every geometry
 // but flat's (nullptr for a combination no path launches). integ: ART_VERN6 / ART_RK4; geom: the
-// GEOM_* of art_kernels.hip (0 any, 1 flat, 2 GR); don: the donation mode; wps: waves per SIMD.
+// GEOM_* of art_step.h (geom_of); don: the donation mode; wps: waves per SIMD.
 using KFn = void (*)(const KParams, const int64_t, const SegIn, const SegOut, const int32_t, unsigned long long*,
                      unsigned long long*);
 using TFn = void (*)(const KParams, const int64_t, const SegIn, const SegOut, const int32_t, const int32_t,

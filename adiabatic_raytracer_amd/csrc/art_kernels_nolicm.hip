@@ -12,5 +12,77 @@
 // rematerialises the constants inside the step loop and runs 3% slower
 // (profiles/r06o_ab_device_licm_off_everywhere.jsonl). The pass moves instructions and changes no
 // arithmetic: the outputs are bit-identical (profiles/r06n_bitident_licm.log).
-#define ART_NOLICM_TU 1
-#include "art_kernels.hip"
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "art_core.h"
+#include "art_event.h"
+#include "art_internal.h"
+#include "art_step.h"
+#include "art_ray_io.h"
+#include "art_propagate.h"
+#include "art_tail.h"
+#include "art_helper.h"
+#include "art_sample.h"
+#include "art_eval_math.h"
+
+namespace art {
+
+// the helper instantiation of the integrator's geometry (launch_propagate, launch_integrator_streamed)
+HFn pick_helper(const KParams& P) {
+  const int geom = geom_of(P);
+  return geom == GEOM_FLAT ? helper_kernel<GEOM_FLAT> : (geom == GEOM_GR ? helper_kernel<GEOM_GR> : helper_kernel<GEOM_ANY>);
+}
+int helper_waves_per_simd(const KParams& P) {
+  // 2 when the build for these parameters fits 2 waves per SIMD without scratch (read once per build)
+  static std::atomic<int> cached[3];
+  const HFn fn = pick_helper(P);
+  const int g = fn == helper_kernel<GEOM_FLAT> ? 1 : (fn == helper_kernel<GEOM_GR> ? 2 : 0);
+  int w = cached[g].load(std::memory_order_relaxed);
+  if (!w) {
+    hipFuncAttributes a{};
+    const bool ok = hipFuncGetAttributes(&a, (const void*)fn) == hipSuccess;
+    (void)hipGetLastError();
+    w = (ok && a.localSizeBytes == 0 && a.numRegs > 0 && a.numRegs <= 256) ? 2 : 1;
+    cached[g].store(w, std::memory_order_relaxed);
+  }
+  return w;
+}
+
+// The integrator and tail instantiations compiled here, without MachineLICM (art_kernels_nolicm.hip):
+// every geometry but flat's Vern6/RK4 integrator. GR: the bulk launch 235.2-236.7 -> 227.3-228.7
+// ms per 10^6 rays, the lone tail ray 7.69 -> 7.54 us per attempt (no spills: 256 VGPRs + 60 spilled
+// -> 226), bit-identical (profiles/r06q_gr_licm.jsonl); the flat integrator stays in art_kernels.hip,
+// 3% faster with the pass (profiles/r06o_ab_device_licm_off_everywhere.jsonl).
+KFn nl_propagate(int integ, int geom, bool save, int don, int wps) {
+#define ART_NL(I, G, S, D, W) \
+  if (integ == I && geom == G && save == S && don == D && wps == W) return propagate_kernel<I, G, S, D, W>;
+  ART_NL(ART_VERN6, GEOM_GR, true, 0, 2) ART_NL(ART_VERN6, GEOM_GR, true, 1, 2)
+  ART_NL(ART_VERN6, GEOM_ANY, true, 0, 2) ART_NL(ART_VERN6, GEOM_ANY, true, 1, 2)
+  ART_NL(ART_RK4, GEOM_ANY, true, 0, 2) ART_NL(ART_RK4, GEOM_ANY, true, 1, 2)
+  ART_NL(ART_RK4, GEOM_ANY, false, 0, 2) ART_NL(ART_RK4, GEOM_ANY, false, 1, 2)
+  ART_NL(ART_VERN6, GEOM_GR, false, 0, 2) ART_NL(ART_VERN6, GEOM_GR, false, 1, 2) ART_NL(ART_VERN6, GEOM_GR, false, 3, 2)
+  ART_NL(ART_VERN6, GEOM_ANY, false, 0, 2) ART_NL(ART_VERN6, GEOM_ANY, false, 1, 2) ART_NL(ART_VERN6, GEOM_ANY, false, 3, 2)
+  ART_NL(ART_VERN6, GEOM_GR, false, 0, 1) ART_NL(ART_VERN6, GEOM_GR, false, 1, 1)
+#undef ART_NL
+  return nullptr;
+}
+// (the cyclotron-observing Vern6 integrators, SegOut::cyc_tau: GR and the general geometry)
+KFn nl_propagate_cyc(int geom, int don) {
+  if (geom == GEOM_GR)
+    return don ? propagate_kernel<ART_VERN6, GEOM_GR, false, 1, ART_WAVES_PER_SIMD, true>
+               : propagate_kernel<ART_VERN6, GEOM_GR, false, 0, ART_WAVES_PER_SIMD, true>;
+  return don ? propagate_kernel<ART_VERN6, GEOM_ANY, false, 1, ART_WAVES_PER_SIMD, true>
+             : propagate_kernel<ART_VERN6, GEOM_ANY, false, 0, ART_WAVES_PER_SIMD, true>;
+}
+TFn nl_tail(int geom) { return geom == GEOM_FLAT ? tail_kernel<GEOM_FLAT> : (geom == GEOM_GR ? tail_kernel<GEOM_GR> : tail_kernel<GEOM_ANY>); }
+
+// the sampler's builds, compiled here without MachineLICM (art_kernels_nolicm.hip)
+SFn nl_sample(int wps, bool blocks) {
+  return wps == 3 ? (blocks ? sample_kernel<3, true> : sample_kernel<3, false>)
+                  : (blocks ? sample_kernel<2, true> : sample_kernel<2, false>);
+}
+MFn nl_eval_math(int fn) { return pick_eval_math<1>(fn); }
+
+}  // namespace art

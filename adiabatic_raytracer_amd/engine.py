@@ -192,7 +192,7 @@ class Engine:
         """One of art_core.h's hand-written scalar functions at every element of a (and b)
         (art_eval_math_device): fn an ART_MATH_* id or its name ("SINCOS", "EXP", "LOG", "RCP",
         "POW120", "MAX_ABS", "MIN_Q", "MAX_Q", "RCLAMP"); tu the translation unit the kernel was
-        compiled in (0 art_kernels.hip, 1 art_kernels_nolicm.hip). Returns (sin, cos) for SINCOS,
+        compiled in (0 art_kernels.hip, 1 art_kernels_nolicm.hip; art_eval_math.h in each). Returns (sin, cos) for SINCOS,
         else one tensor."""
         fn = _lib.MATH_FN[fn] if isinstance(fn, str) else int(fn)
         n = a.numel()

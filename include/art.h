@@ -518,8 +518,8 @@ int art_eval_cyclotron_device(const art_params* p, int64_t n, const double* pos,
  * ulp-level tests against the true value: out0[i] (and out1[i]) = fn(a[i], b[i]). b is read by
  * the two-operand ids only, out1 written by ART_MATH_SINCOS only; an output that is NULL is not
  * written. tu picks the translation unit the kernel was compiled in: 0 art_kernels.hip,
- * 1 art_kernels_nolicm.hip (the functions must round alike in both). An unknown fn or tu is
- * ART_E_INVALID. */
+ * 1 art_kernels_nolicm.hip (eval_math_kernel of art_eval_math.h in each; the functions must round
+ * alike in both). An unknown fn or tu is ART_E_INVALID. */
 enum {
   ART_MATH_SINCOS = 0,  /* msincos(a): out0 = sin, out1 = cos */
   ART_MATH_EXP = 1,     /* fexp(a) */

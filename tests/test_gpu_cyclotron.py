@@ -1,5 +1,5 @@
 """Cyclotron-resonance optical depth on the GPU (art_propagate_cyclotron_*, art_eval_cyclotron_device;
-propagate_kernel<..., CYC = true> in csrc/art_kernels.hip).
+propagate_kernel<..., CYC = true> in csrc/art_propagate.h).
 
 Truth errors. The engine's crossings of ω_c = ω against tests/golden/cyclotron/*.npz (DOP853 at rtol
 1e-13, the root by brentq on its dense output; make_cyclotron_fixture.py), measured on an MI355X over

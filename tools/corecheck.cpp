@@ -77,7 +77,7 @@ void cc_log_fma(const double* x, int64_t n, double* y) {
   for (int64_t i = 0; i < n; ++i) y[i] = log_fma(x[i]);
 }
 // the step-size controller's EEst2^(1/120) with the device's exp_fma / log_fma (the host's fexp /
-// flog are libm), the expression as the two controller sites of art_kernels.hip write it
+// flog are libm), the expression as the two controller sites of art_propagate.h and art_tail.h write it
 void cc_pow120(const double* x, int64_t n, double* y) {
   for (int64_t i = 0; i < n; ++i) y[i] = exp_fma(log_fma(x[i]) * (1.0 / 120.0));
 }

@@ -75,7 +75,7 @@ static void emit(bool flat, bool last) {
   const long long f_cond = count([&] { (void)condition(K, u, tau); });
   // a grid point of the scan: condition at t from the geometric recurrence (t *= q: 1 FLOP)
   const long long f_cond_scan = count([&] { (void)condition_t(K, u, OC(2e-5)); }) + 1;
-  // cubic Hermite point (art_kernels.hip hermite7): 4 setup + 7 x 10
+  // cubic Hermite point (art_step.h hermite7): 4 setup + 7 x 10
   OC u1[7], f0[7], f1[7], out[7], h(0.01), th(0.3);
   for (int i = 0; i < 7; ++i) { u1[i] = u[i]; f0[i] = du[i]; f1[i] = du[i]; }
   const long long f_herm = count([&] {
