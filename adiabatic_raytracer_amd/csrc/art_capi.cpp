@@ -1156,6 +1156,18 @@ constexpr int STREAM_FALLBACK = 1 << 20;
 //     scatters it into the caller's arrays.
 // Before the integrator, one helper_kernel pass on the integrator's stream initialises the first
 // rays with every block slot; after it, one more pass finalizes what is left.
+// The two ends of a call, where the GPU stands idle (10^7 flat rays, ART_HOST_TRACE timelines
+// profiles/host_trace_parent.log before and profiles/host_trace_new.log after). Start: the upload
+// units ramp -- 2^16-ray units until the launch's lanes all have a ray on its way, then doubling
+// to 2^18 -- and the gatherer submits the first unit's copy itself: first unit ready at 0.58 ms
+// (0.89 before), 2^17 rays in HBM at 0.83 ms (2^16 until 1.76 ms before). End: the batch's last
+// rays lie in fine output pieces (art_pieces.h: 35 pieces of 2^18 rays, then 26 of 2^15 over the
+// last 0.8e6), so a straggler holds back 5 MB, not 39 MB: the last scatter ends 1.0 ms after the
+// integrator (1.7 ms before). Pieces are still finalized in order, so the first piece with a
+// straggler holds back the finalize of the pieces behind it (7 of 2^15 in that timeline).
+// Interleaved A/B, seven processes each: 90.23-91.28 ms per call before, 89.31-89.85 now; 1.25e6
+// rays one call at a time 16.16-16.66 -> 15.11-15.70 ms (profiles/ab_host_two_ends*.jsonl).
+// Calls in flight keep the old start and one level of pieces (see fine_shift below).
 // Round 3's CU-masked pipeline ran the init and finalize kernels on 8 reserved CUs, which cost
 // ~10% of the integrator (profiles/r04g_stream_anatomy.jsonl); it is gone. Per-ray results
 // equal the single launch's bit for bit.
@@ -1223,20 +1235,38 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
   while (((int64_t)1 << (shift + 1)) * 32 <= n) ++shift;  // 32..64 pieces (2^18 rays for 10^7: the last
   // piece's finalize, copy and scatter are the call's tail, 95.3-96.5 ms against 98.4-101 with 2^19,
   // profiles/r04ag_piece_shift.jsonl)
-  if (const int e = env_int("ART_HOST_PIECE_SHIFT", 0)) shift = std::max(10, e);  // (tests: many small pieces)
-  while (((n + ((int64_t)1 << shift) - 1) >> shift) > HSIG_NFLAG) ++shift;  // 64 piece counters and flags
-  const int np = (int)((n + ((int64_t)1 << shift) - 1) >> shift);
+  const int shift_env = env_int("ART_HOST_PIECE_SHIFT", 0);
+  if (shift_env) shift = std::max(art::PIECE_MIN_SHIFT, shift_env);  // (tests: many small pieces, one level)
+  // The batch's last rays in fine pieces (art_pieces.h): a piece completes with its slowest ray, and
+  // the rays still running when the queue runs dry were claimed in its last few milliseconds, so
+  // each of the last coarse pieces kept 39 MB on the GPU until the integrator's very end -- the
+  // call's tail of finalize, D2H and scatter. ART_HOST_FINE_RAYS: the fine region (at most so many
+  // rays; default min(2^20, n / 8)), ART_HOST_FINE_SHIFT: its pieces (default 2^15 rays; 0: one
+  // level). One level by default where the coarse pieces are 2^15 rays or fewer already, and
+  // whenever ART_HOST_PIECE_SHIFT alone is set. The pieces number at most HSIG_NFLAG (make_pieces).
+  // Calls in flight (overlap) keep one level and the plain start below by default: their two ends
+  // overlap the neighbouring calls' work, so there is nothing idle to win, and with the ramped
+  // start two 1.25e6-ray calls in flight took the slow way of interleaving in 22 of 24 runs
+  // against 24 of 36 for the build before, ~15.1 against ~14.3 ms per call at the medians; with
+  // all three defaults off, 23 of 36 (profiles/aa_host_inflight2_*.jsonl)
+  const int fine_shift = env_int("ART_HOST_FINE_SHIFT", (!shift_env && shift > 15 && !overlap) ? 15 : 0);
+  const int64_t fine_rays = env_int("ART_HOST_FINE_RAYS", (int)std::min((int64_t)1 << 20, n / 8));
+  static_assert(art::PIECES_MAX == HSIG_NFLAG, "one flag and one counter per piece");
+  const art::Pieces pcs = art::make_pieces(n, shift, fine_shift, fine_rays);
+  const int np = pcs.count;
   int rc;
   if ((rc = lane_setup(c, H))) return rc;
   const size_t nd = (size_t)n;
   auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t in_bytes = nd * 9 * sizeof(double) + nd;  // x0 (3n) k0 (3n) erg dw lnt0 | species
-  // per-piece SoA output blobs, pinned and in HBM: the layout piece_blob (art_kernels.hip) computes
-  auto piece_lo = [&](int k) { return std::min((int64_t)k << shift, n); };
-  auto cnt_off = [&](int64_t m) { return up((size_t)m * 8 * sizeof(double) + (size_t)m * 3 * sizeof(int32_t)); };
-  auto xd_off = [&](int64_t m) { return cnt_off(m) + up((size_t)m * sizeof(int32_t)); };
-  auto out_bytes = [&](int64_t m) { return cap ? xd_off(m) + (size_t)cap * m * 9 * sizeof(double) : cnt_off(m); };
-  const size_t stride = up(out_bytes((int64_t)1 << shift));
+  // per-piece SoA output blobs, pinned and in HBM: the partition and the layout of art_pieces.h,
+  // which piece_blob (art_ray_io.h) and the integrator use too
+  auto piece_lo = [&](int k) { return art::piece_lo(pcs, k); };
+  auto cnt_off = [&](int64_t m) { return art::blob_cnt_off(m); };
+  auto xd_off = [&](int64_t m) { return art::blob_xd_off(m); };
+  auto out_bytes = [&](int64_t m) { return art::blob_bytes(m, cap); };
+  auto blob_off = [&](int k) { return art::piece_blob_off(pcs, k, cap); };
+  const size_t blobs = blob_off(np);
   // scratch: head [queue | stats (10) | init_next (16) fin_next (17) chunk misses (18) exit count (19) waves done (20)
   // waves started (21) |
   // finished rays per piece from word 32 | finalized tiles per piece from word 96] | chunk flags | u0 U0_REC n | rec 16n | xrec
@@ -1250,10 +1280,10 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
   const bool direct = env_int("ART_HOST_DIRECT", 0) != 0;
   void *pi, *po, *din, *dout, *dsc;
   if ((rc = pinned_get_v(H->pinned, 0, in_bytes, &pi)) ||
-      (rc = pinned_get_v(H->pinned, 1, stride * np, &po,
+      (rc = pinned_get_v(H->pinned, 1, blobs, &po,
                          direct ? (hipHostMallocMapped | hipHostMallocCoherent) : hipHostMallocDefault)) ||
       (rc = pool_get_v(H->pool, 0, in_bytes, &din)) ||
-      (!direct && (rc = pool_get_v(H->pool, 1, stride * np, &dout))) ||
+      (!direct && (rc = pool_get_v(H->pool, 1, blobs, &dout))) ||
       (rc = pool_get_v(H->pool, 2, head + ccb + u0b + recb + xrb, &dsc)))
     return rc;
   if (direct) HIP_OK(hipHostGetDevicePointer(&dout, po, 0));
@@ -1265,16 +1295,42 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
   double* rec = (double*)((char*)dsc + head + ccb + u0b);
   double* xrec = cap ? (double*)((char*)dsc + head + ccb + u0b + recb) : nullptr;
   const art::SegIn in{di, di + 3 * nd, di + 6 * nd, di + 7 * nd, di + 8 * nd, (const int8_t*)(di + 9 * nd), u0};
-  // upload units (independent of the output pieces): a small first one (2^16 rays, the
-  // integrator starts soon), then units of max(2^18 rays, a piece) -- each unit costs ~0.2 ms of
-  // host-side submission, which small pieces made the bound of a 1.25e6-ray call's uploads
-  // (ART_HOST_FIRST_UNIT / ART_HOST_UNIT: tests, other sizes in rays)
+  int ncu = 0;
+  HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
+  const int slots = std::max(2, env_int("ART_HOST_BLOCKS", 2 * ncu));  // block slots: 2 per CU
+  // helper blocks beside the integrator (ART_HOST_HELPERS, default 16): launched first, and the
+  // integrator only once every one of them is resident, so it cannot take their slots. Each helper
+  // block (2 waves per SIMD, the top issue priority) shares a CU with one integrator block, so it
+  // costs one integrator block slot, not a CU: 1e7 rays, 3 rounds on one box, the integrator 92.1-
+  // 93.4 -> 88.2-89.0 ms and the call 95.3-96.0 -> 91.1-92.1 ms with 16 helpers; 8 helpers let the
+  // finalize lag (109 ms calls), 12 and 24 are between (profiles/r06j_helpers.jsonl)
+  const int hw = art::helper_waves_per_simd(K);
+  const int helpers = std::min(slots - 1, std::max(1, env_int("ART_HOST_HELPERS", hw == 2 ? 16 : 8)));
+  // (dev, ART_HOST_STREAM_SERIAL=1: no persistent helpers -- every tile initialised before the
+  // integrator and finalized after it, kernel by kernel: for a counter-collection run, which
+  // serialises kernels; the integrator's code and traffic are the same)
+  const bool serial = env_int("ART_HOST_STREAM_SERIAL", 0) != 0;
+  // (a 1-wave/SIMD helper block holds a whole CU: two integrator block slots)
+  const int iblocks = serial ? slots : slots - (hw == 2 ? helpers : 2 * helpers);
+  // upload units (independent of the output pieces): small first ones (2^16 rays, the integrator
+  // starts soon) until the launch's lanes (iblocks x 256) all have a ray on its way -- a jump to the
+  // steady size after one small unit left half the lanes waiting for a 2^18-ray unit's cold gather
+  // and copy -- then units doubling up to the steady max(2^18 rays, a piece): each unit costs
+  // ~0.2 ms of host-side submission, which small pieces made the bound of a 1.25e6-ray call's
+  // uploads. (ART_HOST_FIRST_UNIT / ART_HOST_UNIT: tests and A/B, other first and steady sizes in
+  // rays; ART_HOST_UNIT_RAMP=0, the default for calls in flight: one first unit, then the steady
+  // size at once)
   std::vector<int64_t> ulo{0};
-  const int64_t ustep = std::max(1, env_int("ART_HOST_UNIT", (int)std::max((int64_t)1 << 18, (int64_t)1 << shift)));
-  for (int64_t lo = std::min(n, (int64_t)std::max(1, env_int("ART_HOST_FIRST_UNIT", 1 << 16))); ;
-       lo = std::min(n, lo + ustep)) {
-    ulo.push_back(lo);
-    if (lo >= n) break;
+  {
+    const int64_t ustep = std::max(1, env_int("ART_HOST_UNIT", (int)std::max((int64_t)1 << 18, (int64_t)1 << pcs.shift)));
+    const int64_t ufirst = std::max(1, env_int("ART_HOST_FIRST_UNIT", 1 << 16));
+    const bool ramp = env_int("ART_HOST_UNIT_RAMP", overlap ? 0 : 1) != 0;  // (calls in flight: see fine_shift)
+    const int64_t lanes = ramp ? (int64_t)iblocks * 256 : 0;
+    for (int64_t lo = 0, sz = ufirst; lo < n;) {
+      lo = std::min(n, lo + sz);
+      ulo.push_back(lo);
+      if (lo >= lanes) sz = (ramp && sz < ustep) ? std::min(ustep, 2 * sz) : ustep;
+    }
   }
   const int nu = (int)ulo.size() - 1;
   while ((int64_t)H->pev.size() < nu + np + 2) {
@@ -1302,8 +1358,27 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
   const int delay_ms = env_int("ART_HOST_UPLOAD_DELAY_MS", 0);
   std::atomic<int> gathered{0};
   std::atomic<bool> gstop{false};
+  // one unit's H2D copies and its event: the nine double rows in one strided copy (one DMA command
+  // instead of nine), then the species
+  auto submit_unit = [&](int u) -> bool {
+    const int64_t lo = ulo[u], m = ulo[u + 1] - lo;
+    bool bad = hipMemcpy2DAsync(di + lo, nd * sizeof(double), pin + lo, nd * sizeof(double), (size_t)m * sizeof(double), 9,
+                                hipMemcpyHostToDevice, H->m_up) != hipSuccess;
+    bad |= hipMemcpyAsync((int8_t*)(di + 9 * nd) + lo, (int8_t*)(pin + 9 * nd) + lo, (size_t)m, hipMemcpyHostToDevice,
+                          H->m_up) != hipSuccess;
+    bad |= hipEventRecord(ev_up[u], H->m_up) != hipSuccess;
+    return !bad;
+  };
+  // The first unit's copy is what the init pass and so the integrator wait for: the gatherer submits
+  // it itself the moment it is gathered, beside the caller's counter memsets, helper launch and
+  // residency wait instead of after them (ART_HOST_EARLY_UNIT0=0, the default for calls in flight:
+  // the caller submits it)
+  const bool early0 = env_int("ART_HOST_EARLY_UNIT0", overlap ? 0 : 1) != 0;  // (calls in flight: see fine_shift)
+  std::atomic<int> early0_err{0};
+  const int device = c->device;
   std::thread gatherer([&] {
     using Seg = CopyPool::Seg;
+    if (early0 && hipSetDevice(device) != hipSuccess) early0_err = 1;
     for (int u = 0; u < nu && !gstop.load(); ++u) {
       if (delay_ms > 0 && u == 1)
         for (int w = 0; w < delay_ms && !gstop.load(); ++w) std::this_thread::sleep_for(std::chrono::milliseconds(1));
@@ -1314,8 +1389,13 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
       g.push_back({(int8_t*)(pin + 9 * nd) + lo, species + lo, (size_t)m});
       const double tg0 = clk();
       copy_pool().run(g);
+      const double tg1 = clk();
+      if (u == 0 && early0) {  // (before `gathered`: the caller touches the upload stream only after it)
+        if (early0_err.load() == 0 && !submit_unit(0)) early0_err = 1;  // (not on another device: the caller sees the error)
+        if (trace) std::fprintf(stderr, "[art-host] t=%.2f unit 0 submitted (by the gatherer)\n", clk() - t_start);
+      }
       gathered.store(u + 1, std::memory_order_release);
-      if (trace) std::fprintf(stderr, "[art-host] t=%.2f unit %d gathered in %.2f ms\n", tg0 - t_start, u, clk() - tg0);
+      if (trace) std::fprintf(stderr, "[art-host] t=%.2f unit %d gathered in %.2f ms\n", tg0 - t_start, u, tg1 - tg0);
     }
   });
   // (every return below, the early ones of HIP_OK included, stops and joins the gatherer first)
@@ -1347,7 +1427,7 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
   // (tests: ART_HOST_WAVE_WAIT_MS shortens a wave's bound on its chunk, s_memrealtime at 100 MHz)
   so.wait_ticks = env_int("ART_HOST_WAVE_WAIT_MS", 0) > 0 ? (unsigned long long)env_int("ART_HOST_WAVE_WAIT_MS", 0) * 100000ull
                                                          : art::STREAM_WAIT_TICKS;
-  so.piece_shift = shift;
+  so.pieces = pcs;
   so.host_ready = H->hsig_dev;
   so.host_flags = H->hsig_dev + 8;
   so.init_next = words + 16;
@@ -1356,35 +1436,17 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
   so.chunk_ready = ccnt;
   so.blob = (char*)dout;
   so.blob_host = direct ? 1 : 0;
-  so.blob_stride = (int64_t)stride;
   so.flux_hist = hflux ? hist_dev : nullptr;
   so.flux_nbins = hflux ? fx.nbins : 0;
   so.done_host = H->hsig_dev + HSIG_DONE;
   so.exit_count = words + 19;
   so.waves_done = words + 20;
   so.waves_started = words + 21;
-  int ncu = 0;
-  HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-  const int slots = std::max(2, env_int("ART_HOST_BLOCKS", 2 * ncu));  // block slots: 2 per CU
-  // helper blocks beside the integrator (ART_HOST_HELPERS, default 16): launched first, and the
-  // integrator only once every one of them is resident, so it cannot take their slots. Each helper
-  // block (2 waves per SIMD, the top issue priority) shares a CU with one integrator block, so it
-  // costs one integrator block slot, not a CU: 1e7 rays, 3 rounds on one box, the integrator 92.1-
-  // 93.4 -> 88.2-89.0 ms and the call 95.3-96.0 -> 91.1-92.1 ms with 16 helpers; 8 helpers let the
-  // finalize lag (109 ms calls), 12 and 24 are between (profiles/r06j_helpers.jsonl)
-  const int hw = art::helper_waves_per_simd(K);
-  const int helpers = std::min(slots - 1, std::max(1, env_int("ART_HOST_HELPERS", hw == 2 ? 16 : 8)));
   so.helpers = helpers;
-  // (dev, ART_HOST_STREAM_SERIAL=1: no persistent helpers -- every tile initialised before the
-  // integrator and finalized after it, kernel by kernel: for a counter-collection run, which
-  // serialises kernels; the integrator's code and traffic are the same)
-  const bool serial = env_int("ART_HOST_STREAM_SERIAL", 0) != 0;
   // After the integrator, one pass of every block slot finalizes what is left -- unless this call
   // overlaps the next one (art_propagate_host_flux_async): then the next call's integrator would
   // hold those slots, and the helpers finalize alone
   const bool final_pass = serial || !overlap;
-  // (a 1-wave/SIMD helper block holds a whole CU: two integrator block slots)
-  const int iblocks = serial ? slots : slots - (hw == 2 ? helpers : 2 * helpers);
   so.exit_expected = (serial ? 0 : helpers) + (final_pass ? slots : 0);
   hipEvent_t ev_zero = H->pev[nu + np];  // (the helpers start on zeroed counters)
   HIP_OK(hipEventRecord(ev_zero, H->m_comp));
@@ -1495,7 +1557,7 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
   int dk = 0, sk = 0;  // pieces whose download is queued / scattered
   auto scatter = [&](int k) {
     const int64_t lo = piece_lo(k), m = piece_lo(k + 1) - lo;
-    const char* bo = (const char*)po + stride * k;
+    const char* bo = (const char*)po + blob_off(k);
     const double* d = (const double*)bo;
     const int32_t* i32 = (const int32_t*)(d + 8 * m);
     std::vector<Seg> g;
@@ -1533,7 +1595,7 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
     }
     while (!direct && dk < np && __atomic_load_n(hflag + dk, __ATOMIC_ACQUIRE) != 0ull) {
       const int64_t m = piece_lo(dk + 1) - piece_lo(dk);
-      if (hipMemcpyAsync((char*)po + stride * dk, (char*)dout + stride * dk, out_bytes(m), hipMemcpyDeviceToHost,
+      if (hipMemcpyAsync((char*)po + blob_off(dk), (char*)dout + blob_off(dk), out_bytes(m), hipMemcpyDeviceToHost,
                          H->m_dn) != hipSuccess ||
           hipEventRecord(ev_dn[dk], H->m_dn) != hipSuccess)
         return -1;
@@ -1563,16 +1625,14 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
       std::this_thread::sleep_for(std::chrono::microseconds(5));
     }
     if (perr) break;
-    const int64_t lo = ulo[u], m = ulo[u + 1] - lo;
-    // the nine double rows of the unit in one strided copy (one DMA command instead of nine)
-    perr |= hipMemcpy2DAsync(di + lo, nd * sizeof(double), pin + lo, nd * sizeof(double), (size_t)m * sizeof(double), 9,
-                             hipMemcpyHostToDevice, H->m_up) != hipSuccess;
-    perr |= hipMemcpyAsync((int8_t*)(di + 9 * nd) + lo, (int8_t*)(pin + 9 * nd) + lo, (size_t)m, hipMemcpyHostToDevice,
-                           H->m_up) != hipSuccess;
-    perr |= hipEventRecord(ev_up[u], H->m_up) != hipSuccess;
+    if (u == 0 && early0) {  // (the gatherer submitted it)
+      perr |= early0_err.load();
+    } else {
+      perr |= !submit_unit(u);
+      if (trace) std::fprintf(stderr, "[art-host] t=%.2f unit %d submitted%s\n", clk() - t_start, u,
+                              launched ? "" : " (integrator not launched yet)");
+    }
     recorded.store(u + 1, std::memory_order_release);
-    if (trace) std::fprintf(stderr, "[art-host] t=%.2f unit %d submitted%s\n", clk() - t_start, u,
-                            launched ? "" : " (integrator not launched yet)");
     if (!perr && progress() < 0) perr = 1;
   }
   if (!perr && !launched) {  // the helpers wait for CU slots the previous call still holds
@@ -1644,8 +1704,8 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
     }
   }
   stop = true;
-  if (peek) (void)hipHostFree(peek);
   if (gave_up) {
+    if (peek) (void)hipHostFree(peek);
     // stop the launch, then leave the batch to another path: every wait of the helpers and the
     // waves ends on the abort word, and a helper that sees it drains the work queue (queue_word),
     // so the integrator stops at each wave's next chunk claim. (The ready counter is NOT raised:
@@ -1671,7 +1731,9 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
     return STREAM_FALLBACK;
   }
   readier.join();
-  if (trace) std::fprintf(stderr, "[art-host] maskless total %.2f ms (%d pieces of 2^%d)\n", clk() - t_start, np, shift);
+  if (trace) std::fprintf(stderr, "[art-host] maskless total %.2f ms (%d pieces of 2^%d, %d of 2^%d)\n", clk() - t_start, pcs.ncoarse,
+                          pcs.shift, np - pcs.ncoarse, pcs.fine_shift);
+  if (peek) (void)hipHostFree(peek);  // (after the total: freeing pinned memory takes ~0.6 ms)
   const bool complete = __atomic_load_n(hdone, __ATOMIC_ACQUIRE) == 1ull;
   if (fx.nbins && hflux && complete) {
     for (int b = 0; b < 2 * fx.nbins; ++b) {
@@ -1682,7 +1744,7 @@ int propagate_host_maskless(DeviceCtx* c, HostLane* H, bool overlap, int64_t tic
     if (hflux) HIP_OK(hipMemsetAsync(hist_dev, 0, 2 * (size_t)fx.nbins * sizeof(double), H->m_comp));
     for (int k = 0; k < np; ++k) {
       const int64_t lo = piece_lo(k), m = piece_lo(k + 1) - lo;
-      double* dd = (double*)((char*)dout + stride * k);
+      double* dd = (double*)((char*)dout + blob_off(k));
       const int32_t* st = (const int32_t*)(dd + 8 * m);
       HIP_OK(art::launch_flux(K, m, dd, dd + 3 * m, st, in.species + lo, nullptr, fx.nbins, hist_dev, H->m_comp));
     }

@@ -49,11 +49,6 @@ __global__ __launch_bounds__(256, 2) void helper_kernel(
   if (flb)
     for (int b = tid; b < 2 * out.flux_nbins; b += 256) hfl[b] = 0.0;
   __syncthreads();
-  const int64_t full = (int64_t)1 << out.piece_shift;
-  auto piece_rays = [&](int p) {
-    const int64_t lo = (int64_t)p << out.piece_shift;
-    return (n - lo) < full ? n - lo : full;
-  };
   const int64_t TS = mode == HK_TILES ? S3_TILE : 256;  // rays per tile
   int64_t tile = blockIdx.x;
   unsigned long long hr = 0;  // (HK_TILES, thread 0) host_ready as last read: it only grows
@@ -106,16 +101,16 @@ __global__ __launch_bounds__(256, 2) void helper_kernel(
           if (pend < 0) {
             const unsigned long long fnext = ld_agent(out.fin_next);
             if ((int64_t)fnext < n) {
-              const int p = (int)(fnext >> out.piece_shift);
-              if ((int64_t)ld_agent(out.piece_cnt + p) == piece_rays(p)) {
+              const int p = piece_of(out.pieces, (int64_t)fnext);
+              if ((int64_t)ld_agent(out.piece_cnt + p) == piece_rays(out.pieces, p)) {
                 const unsigned long long c = atomicAdd(out.fin_next, (unsigned long long)S3_TILE);
                 if ((int64_t)c < n) pend = (long long)c;
               }
             }
           }
           if (pend >= 0) {
-            const int p = (int)(pend >> out.piece_shift);
-            if ((int64_t)ld_agent(out.piece_cnt + p) == piece_rays(p)) {
+            const int p = piece_of(out.pieces, (int64_t)pend);
+            if ((int64_t)ld_agent(out.piece_cnt + p) == piece_rays(out.pieces, p)) {
               what = 2;
               t = pend;
               pend = -1;
@@ -177,9 +172,9 @@ __global__ __launch_bounds__(256, 2) void helper_kernel(
       SegOut ol = out;
       int64_t ob = i0, m = i1 - i0;
       if (mode == HK_TILES) {
-        const int p = (int)(t >> out.piece_shift);
+        const int p = piece_of(out.pieces, (int64_t)t);
         ol = piece_blob(out, n, p, m);
-        ob = (int64_t)p << out.piece_shift;
+        ob = piece_lo(out.pieces, p);
       }
 #pragma unroll 1
       for (int64_t i = t + tid; i < t1; i += 256) finalize_one(P, n, i, i - ob, m, in, ol, flb ? hfl : nullptr, out.flux_nbins);
@@ -195,8 +190,8 @@ __global__ __launch_bounds__(256, 2) void helper_kernel(
           for (int64_t c = t / CHUNK; c * CHUNK < t1; ++c)
             __hip_atomic_store(out.chunk_ready + c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
-          const int p = (int)(t >> out.piece_shift);
-          const unsigned long long tiles = (unsigned long long)((piece_rays(p) + S3_TILE - 1) / S3_TILE);
+          const int p = piece_of(out.pieces, (int64_t)t);
+          const unsigned long long tiles = (unsigned long long)((piece_rays(out.pieces, p) + S3_TILE - 1) / S3_TILE);
           const unsigned long long old =
               __hip_atomic_fetch_add(out.piece_fin + p, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (old + 1ull == tiles) {  // the piece's last tile: its blob is complete in memory

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "art_core.h"
+#include "art_pieces.h"
 
 namespace art {
 // Segment inputs / outputs (device pointers, SoA), see art_segment_out / art_crossing_buf.
@@ -57,7 +58,8 @@ struct SegOut {
   // entry points' contract, include/art.h), so no fill of the outputs is needed beforehand
   int32_t nan_fill;
   // The streamed host pipeline (propagate_kernel<..., DON = 3>, art_propagate_host): piece
-  // p = ray >> piece_shift; every finished ray counts into piece_cnt[p]; a wave that waits too
+  // p = piece_of(pieces, ray) (art_pieces.h: coarse pieces, then fine ones over the batch's last
+  // rays); every finished ray counts into piece_cnt[p]; a wave that waits too
   // long (STREAM_WAIT_TICKS of s_memrealtime) raises *abort_word and stops taking rays.
   unsigned long long* piece_cnt;
   unsigned int* abort_word;
@@ -65,7 +67,7 @@ struct SegOut {
   // integrator wave's next chunk claim finds the queue drained and the launch runs out at once
   unsigned long long* queue_word;
   unsigned long long wait_ticks;  // a wave's bound on a chunk flag (STREAM_WAIT_TICKS; tests set less)
-  int32_t piece_shift;
+  Pieces pieces;
   // The maskless streamed pipeline (DON = 3, art_capi.cpp propagate_host_maskless): one launch
   // over the whole batch holds every CU; its first `helpers` blocks are helpers, not
   // integrators. *host_ready (host memory, raised by the host as each piece's copies land)
@@ -73,7 +75,7 @@ struct SegOut {
   // (*init_next, init_one) and set chunk_ready[c] for each 64-ray chunk they finish; an
   // integrator wave that claims a chunk waits for its flag. Finished rays count into
   // piece_cnt[p] as in DON = 2; once a piece is complete, helpers claim its tiles to finalize
-  // (*fin_next, finalize_one) into the piece's SoA blob (blob + p blob_stride, piece_blob), and
+  // (*fin_next, finalize_one) into the piece's SoA blob (blob + piece_blob_off, piece_blob), and
   // the block that finalizes a piece's last tile sets host_flags[p] (host memory the host
   // polls, then copies the blob out). The helpers are a separate persistent kernel on a stream of
   // their own; one helper pass over every block slot initialises the first rays before the
@@ -84,7 +86,6 @@ struct SegOut {
   unsigned long long* piece_fin;
   unsigned* chunk_ready;
   char* blob;
-  int64_t blob_stride;
   int32_t blob_host;  // 1: the blobs are pinned host memory the helpers write over PCIe (no download copies)
   int32_t helpers;
   // The end of a streamed call without the integrator's stream (art_capi.cpp, HostLane): the

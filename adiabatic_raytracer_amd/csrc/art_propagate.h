@@ -829,7 +829,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
     }
     int fin_piece = -1;  // (DON = 3) the piece of a ray finishing now
     if (finish >= 0) {  // the raw end record; finalize_kernel back-transforms it (RayTracer.jl:393-416)
-      if constexpr (DON == 3) fin_piece = ray >> out.piece_shift;
+      if constexpr (DON == 3) fin_piece = piece_of(out.pieces, ray);
       double2* rq = reinterpret_cast<double2*>(out.rec + (int64_t)ray * END_REC);
       rq[0] = make_double2(u[0], u[1]);
       rq[1] = make_double2(u[2], u[3]);

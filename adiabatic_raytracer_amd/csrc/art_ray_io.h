@@ -225,11 +225,8 @@ __device__ inline void finalize_one(const KParams& P, int64_t n, int64_t i, int6
 // (DON = 3) the SoA output blob of piece p (art_capi.cpp, propagate_host_maskless: the same
 // layout and 256-byte alignments), its rows m long
 __device__ inline SegOut piece_blob(const SegOut& out, int64_t n, int p, int64_t& m) {
-  const int64_t lo = (int64_t)p << out.piece_shift;
-  const int64_t full = (int64_t)1 << out.piece_shift;
-  m = (n - lo) < full ? n - lo : full;
-  auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-  char* db = out.blob + (int64_t)p * out.blob_stride;
+  m = piece_rays(out.pieces, p);
+  char* db = out.blob + piece_blob_off(out.pieces, p, out.cap);
   double* dd = (double*)db;
   int32_t* di32 = (int32_t*)(dd + 8 * m);
   SegOut ol{};
@@ -237,10 +234,9 @@ __device__ inline SegOut piece_blob(const SegOut& out, int64_t n, int p, int64_t
   ol.status = di32; ol.n_acc = di32 + m; ol.n_rej = di32 + 2 * m;
   ol.rec = out.rec;
   if (out.cap) {
-    const int64_t cnt = up(m * 8 * 8 + m * 3 * 4);
-    double* x = (double*)(db + cnt + up(m * 4));
+    double* x = (double*)(db + blob_xd_off(m));
     ol.cap = out.cap;
-    ol.xcount = (int32_t*)(db + cnt);
+    ol.xcount = (int32_t*)(db + blob_cnt_off(m));
     ol.xpos = x; ol.xk = x + 3 * out.cap * m; ol.xt = x + 6 * out.cap * m; ol.xdw = x + 7 * out.cap * m;
     ol.xp = x + 8 * out.cap * m;
     ol.xrec = out.xrec;
