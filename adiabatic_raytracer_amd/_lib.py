@@ -87,6 +87,8 @@ SIGNATURES = {
     "art_grow_trees": (C.c_int, [_P, _i64, _v, _v, _v, _v, C.POINTER(TreeOpts), _i64, _v, C.POINTER(_i64), _v, _v]),
     "art_grow_trees_traj": (C.c_int, [_P, _i64, _v, _v, _v, _v, C.POINTER(TreeOpts), _i64, _v, C.POINTER(_i64), _v,
                                       _v, C.POINTER(TreeTraj)]),
+    "art_grow_trees_device": (C.c_int, [_P, _i64, _v, _v, _v, _v, C.POINTER(TreeOpts), _i64, _v, _v, _v, _v,
+                                        C.POINTER(_i64), _v]),
     "art_event_weight_host": (C.c_int, [_P, _d, _d, _d, _i64, _v, _v, _v, _v]),
     "art_event_weight_device": (C.c_int, [_P, _d, _d, _d, _i64, _v, _v, _v, _v, _v]),
     "art_recent_kernel_ms": (C.c_int, [_i32, _v]),

@@ -924,6 +924,163 @@ int art_propagate_traj_device(const art_params* p, int64_t n, const double* x0, 
 }  // extern "C"
 
 namespace {
+// What one art_grow_trees_device call holds until it returns: its stream-ordered device blocks
+// and the pinned word the per-round count lands in.
+struct TreeScratch {
+  hipStream_t s = nullptr;
+  void* block = nullptr;
+  void* log = nullptr;
+  int32_t* host = nullptr;  // [0] the next round's batch size, [1] the overflow word
+  ~TreeScratch() {
+    if (log) (void)hipFreeAsync(log, s);
+    if (block) (void)hipFreeAsync(block, s);
+    if (host) (void)hipHostFree(host);
+  }
+};
+}  // namespace
+
+extern "C" {
+
+// get_tree for n roots with every tree's state in HBM (art_tree_step.h, the tree kernels of
+// art_kernels.hip): per round one pack, one batched propagate (propagate_device_impl: the
+// small-batch path, donation and graduation as for any device launch), one step and one scan on
+// `stream`; the host reads the next round's batch size and nothing else. g_mu is held while work is
+// enqueued and released while the host waits for a round, so other streams' calls go on.
+int art_grow_trees_device(const art_params* p, int64_t n, const double* x0, const double* k0, const double* erg,
+                          const int8_t* species, const art_tree_opts* opts, int64_t node_capacity, art_tree_node* nodes,
+                          int64_t* node_start, int32_t* counts, int32_t* infos, int64_t* n_nodes, void* stream) {
+  std::unique_lock<std::mutex> lk(g_mu);
+  if (!p) return fail(ART_E_INVALID, "params is NULL");
+  if (!opts) return fail(ART_E_INVALID, "opts is NULL");
+  if (!n_nodes) return fail(ART_E_INVALID, "n_nodes is NULL");
+  if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
+  if (n > 0 && (!x0 || !k0 || !erg || !species)) return fail(ART_E_INVALID, "input buffers must be non-NULL");
+  if (opts->max_nodes < 0) return fail(ART_E_INVALID, "max_nodes must be >= 0");
+  if (opts->crossing_cap < 0) return fail(ART_E_INVALID, "crossing_cap must be >= 0");
+  const bool split_all = opts->splittings_cutoff > 0;
+  if (split_all && opts->num_cutoff > 0)
+    return fail(ART_E_INVALID, "splittings_cutoff > 0 with num_cutoff > 0 has no device form (art_grow_trees grows such trees)");
+  int rc = validate(p);
+  if (rc) return rc;
+  *n_nodes = 0;
+  if (n == 0 && !node_start) return ART_OK;
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  hipStream_t s = pick(c, stream);
+  if (n == 0) {
+    HIP_OK(hipMemsetAsync(node_start, 0, sizeof(int64_t), s));
+    HIP_OK(hipStreamSynchronize(s));
+    return ART_OK;
+  }
+  const art::KParams K = kparams(*p);
+  art::TreeRules R{};
+  R.num_cutoff = opts->num_cutoff;
+  R.mc_nodes = opts->mc_nodes;
+  R.max_nodes = opts->max_nodes;
+  R.split_all = split_all ? 1 : 0;
+  R.cap = split_all ? std::max(1, opts->crossing_cap) : 1;
+  const int64_t depth = art::tree_stack_capacity(opts->mc_nodes, opts->max_nodes, split_all);
+  R.stack_cap = (int32_t)depth;
+  R.tree_offset = opts->tree_offset;
+  R.seed = opts->seed;
+  R.prob_cutoff = opts->prob_cutoff;
+  R.rNS = p->rNS;
+  const double dt0 = std::exp(-30.0);  // NumerPass[1] = ln_t_start = -30 (MainRunner.jl:410)
+  const double ln_dt0 = std::log(dt0);  // the double the host forest passes for its roots
+
+  // one block: [state | stacks | two lists, flag, pos | counts (n + 1) | node_start (n + 1) | overflow
+  // word | scan scratch | the round's batch], each part 256-byte aligned
+  const size_t nd = (size_t)n, cap = (size_t)R.cap;
+  size_t off = 0;
+  auto part = [&off](size_t bytes) {
+    const size_t at = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return at;
+  };
+  const size_t o_state = part(nd * sizeof(art::TreeState)), o_stack = part(nd * (size_t)depth * sizeof(art::TreeEv));
+  const size_t o_list0 = part(nd * 4), o_list1 = part(nd * 4), o_flag = part(nd * 4), o_pos = part(nd * 4);
+  const size_t o_counts = part((nd + 1) * 4), o_start = part((nd + 1) * 8), o_err = part(4);
+  const size_t tmp_bytes = art::tree_scan_bytes(n), o_tmp = part(tmp_bytes);
+  const size_t o_in = part(9 * nd * 8), o_sp = part(nd), o_out = part(8 * nd * 8), o_int = part(4 * nd * 4);
+  const size_t o_xc = part(9 * cap * nd * 8);
+  TreeScratch ts;
+  ts.s = s;
+  if ((rc = scratch_alloc(s, off, &ts.block))) return rc;
+  if (hipHostMalloc((void**)&ts.host, 64, hipHostMallocDefault) != hipSuccess) return fail(ART_E_NOMEM, "hipHostMalloc failed");
+  char* b = (char*)ts.block;
+  art::TreeState* state = (art::TreeState*)(b + o_state);
+  art::TreeEv* stack = (art::TreeEv*)(b + o_stack);
+  int32_t *cur = (int32_t*)(b + o_list0), *nxt = (int32_t*)(b + o_list1);
+  int32_t *flag = (int32_t*)(b + o_flag), *pos = (int32_t*)(b + o_pos), *counts1 = (int32_t*)(b + o_counts);
+  int32_t* err = (int32_t*)(b + o_err);
+  double *din = (double*)(b + o_in), *dout = (double*)(b + o_out), *dxc = (double*)(b + o_xc);
+  int32_t* dint = (int32_t*)(b + o_int);
+  HIP_OK(hipMemsetAsync(err, 0, 4, s));
+  HIP_OK(art::launch_tree_roots(K, R, n, x0, k0, erg, species, state, stack, cur, flag, pos, s));
+
+  int64_t log_cap = split_all ? n : 3 * n, total = 0;
+  if ((rc = scratch_alloc(s, (size_t)log_cap * sizeof(art_tree_node), &ts.log))) return rc;
+  const int64_t max_rounds = (int64_t)opts->max_nodes + 2;
+  int64_t m_prev = n, m = n;
+  for (int64_t round = 0; m > 0; ++round) {
+    if (round >= max_rounds) return fail(ART_E_HIP, "the forest did not end within max_nodes + 2 rounds");
+    if (total + m > log_cap) {  // grow the node log (kept across rounds; the flatten reads it whole)
+      const int64_t want = std::max(2 * log_cap, total + m);
+      void* bigger = nullptr;
+      if ((rc = scratch_alloc(s, (size_t)want * sizeof(art_tree_node), &bigger))) return rc;
+      HIP_OK(hipMemcpyAsync(bigger, ts.log, (size_t)total * sizeof(art_tree_node), hipMemcpyDeviceToDevice, s));
+      HIP_OK(hipFreeAsync(ts.log, s));
+      ts.log = bigger;
+      log_cap = want;
+    }
+    // this round's batch of m segments: SoA with stride m inside the buffers sized for n
+    const size_t md = (size_t)m;
+    art::TreeBatch B{};
+    B.x0 = din; B.k0 = din + 3 * md; B.erg = din + 6 * md; B.dw = din + 7 * md; B.lnt0 = din + 8 * md;
+    B.species = (int8_t*)(b + o_sp);
+    B.x_end = dout; B.k_end = dout + 3 * md; B.u7_end = dout + 6 * md; B.tau_end = dout + 7 * md;
+    B.status = dint; B.n_acc = dint + md; B.n_rej = dint + 2 * md; B.xcount = dint + 3 * md;
+    B.xpos = dxc; B.xk = dxc + 3 * cap * md; B.xt = dxc + 6 * cap * md; B.xdw = dxc + 7 * cap * md; B.xp = dxc + 8 * cap * md;
+    HIP_OK(art::launch_tree_pack(R, m_prev, m, cur, flag, pos, nxt, state, stack, B, dt0, ln_dt0, s));
+    art_segment_out so{B.x_end, B.k_end, B.u7_end, B.tau_end, B.status, B.n_acc, B.n_rej};
+    art_crossing_buf xb{R.cap, B.xcount, B.xpos, B.xk, B.xt, B.xdw, B.xp};
+    if ((rc = propagate_device_impl(p, m, B.x0, B.k0, B.erg, B.dw, B.lnt0, B.species, opts->splittings_cutoff, &so, &xb,
+                                    stream)))
+      return rc;
+    HIP_OK(art::launch_tree_step(K, R, n, m, nxt, state, stack, B, (art_tree_node*)ts.log + total, flag, pos, err,
+                                 b + o_tmp, tmp_bytes, s));
+    total += m;
+    HIP_OK(hipMemcpyAsync(ts.host, pos + (m - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    lk.unlock();
+    const hipError_t we = hipStreamSynchronize(s);
+    lk.lock();
+    if (we != hipSuccess) return fail(ART_E_HIP, "hipStreamSynchronize: %s", hipGetErrorString(we));
+    m_prev = m;
+    m = ts.host[0];
+    if (m < 0 || m > m_prev) return fail(ART_E_HIP, "the forest's round count is out of range");
+    std::swap(cur, nxt);
+  }
+  *n_nodes = total;
+  const bool fits = nodes && total <= node_capacity;
+  if (fits) {
+    int64_t* ns = node_start ? node_start : (int64_t*)(b + o_start);
+    HIP_OK(art::launch_tree_finish(R, n, state, counts1, counts, infos, ns, b + o_tmp, tmp_bytes, s));
+    HIP_OK(art::launch_tree_flatten(total, (const art_tree_node*)ts.log, ns, node_capacity, nodes, s));
+  }
+  HIP_OK(hipMemcpyAsync(ts.host + 1, err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  lk.unlock();
+  const hipError_t we = hipStreamSynchronize(s);
+  lk.lock();
+  if (we != hipSuccess) return fail(ART_E_HIP, "hipStreamSynchronize: %s", hipGetErrorString(we));
+  if (ts.host[1]) return fail(ART_E_INVALID, "a tree's event stack left its bound (art_tree_step.h): no result");
+  if (!fits && total > node_capacity)
+    return fail(ART_E_NOMEM, "node_capacity is too small: %s nodes", std::to_string(total).c_str());
+  return ART_OK;
+}
+
+}  // extern "C"
+
+namespace {
 // The chunked pipeline's output staging: coarse-grained (non-coherent) mapped host memory
 // lets the L2 combine finalize_kernel's 8-byte stores into full-line PCIe writes; the stream
 // event the host waits on makes them visible. ART_HOST_COHERENT=1: fine-grained memory (A/B).

@@ -5,6 +5,7 @@
 
 #include "art_core.h"
 #include "art_pieces.h"
+#include "art_tree_step.h"
 
 namespace art {
 // Segment inputs / outputs (device pointers, SoA), see art_segment_out / art_crossing_buf.
@@ -270,4 +271,36 @@ using MFn = void (*)(const int64_t, const double*, const double*, double*, doubl
 MFn nl_eval_math(int fn);
 hipError_t launch_eval_math(int fn, int tu, int64_t n, const double* a, const double* b, double* out0, double* out1,
                             hipStream_t s);
+// The device-resident tree driver (art_grow_trees_device; kernels in art_kernels.hip, the per-tree
+// rules in art_tree_step.h). One round's propagate inputs and outputs, device pointers, SoA with
+// the round's batch size as the stride:
+struct TreeBatch {
+  double *x0, *k0, *erg, *dw, *lnt0;
+  int8_t* species;
+  double *x_end, *k_end, *u7_end, *tau_end;
+  int32_t *status, *n_acc, *n_rej;
+  int32_t* xcount;
+  double *xpos, *xk, *xt, *xdw, *xp;
+};
+// scratch of the driver's two scans (over at most n trees)
+size_t tree_scan_bytes(int64_t n);
+// state, root events (stack, R.stack_cap per tree) and round 1's selection: list[i] = i, flag 1, pos i + 1
+hipError_t launch_tree_roots(const KParams& P, const TreeRules& R, int64_t n, const double* x0, const double* k0,
+                             const double* erg, const int8_t* species, TreeState* state, TreeEv* stack, int32_t* list,
+                             int32_t* flag, int32_t* pos, hipStream_t s);
+// pop and pack: the flagged entries of list_prev[0, m_prev) into this round's list and batch B of m
+hipError_t launch_tree_pack(const TreeRules& R, int64_t m_prev, int64_t m, const int32_t* list_prev, const int32_t* flag,
+                            const int32_t* pos, int32_t* list, TreeState* state, const TreeEv* stack, const TreeBatch& B,
+                            double dt0, double ln_dt0, hipStream_t s);
+// the step of the m trees of list: nodes into log[0, m), flag[j] whether tree list[j] goes on, pos the
+// inclusive scan of flag (pos[m - 1]: the next round's batch size), *err raised on a stack overflow
+hipError_t launch_tree_step(const KParams& P, const TreeRules& R, int64_t n, int64_t m, const int32_t* list, TreeState* state,
+                            TreeEv* stack, const TreeBatch& B, art_tree_node* log, int32_t* flag, int32_t* pos,
+                            int32_t* err, void* tmp, size_t tmp_bytes, hipStream_t s);
+// counts / infos (either may be null), and node_start[0, n] as the exclusive scan of the counts (counts1: n + 1 ints)
+hipError_t launch_tree_finish(const TreeRules& R, int64_t n, const TreeState* state, int32_t* counts1, int32_t* counts,
+                              int32_t* infos, int64_t* node_start, void* tmp, size_t tmp_bytes, hipStream_t s);
+// the log's `total` records into nodes (capacity records) at node_start[tree] + sequence
+hipError_t launch_tree_flatten(int64_t total, const art_tree_node* log, const int64_t* node_start, int64_t capacity,
+                               art_tree_node* nodes, hipStream_t s);
 }  // namespace art

@@ -16,6 +16,7 @@
 #include "art_propagate.h"
 #include "art_helper.h"
 #include "art_eval_math.h"
+#include "art_tree_step.h"
 
 namespace art {
 
@@ -750,6 +751,195 @@ hipError_t launch_eval_math(int fn, int tu, int64_t n, const double* a, const do
   const MFn k = tu ? nl_eval_math(fn) : pick_eval_math<0>(fn);
   if (!k) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, a, b, out0, out1);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The device-resident tree driver (art_grow_trees_device, art_capi.cpp): every tree's state and
+// event stack stay in HBM (art_tree_step.h); a round is pack -> one batched propagate -> step ->
+// an inclusive scan of the trees that go on, whose last value -- the next round's batch size -- is
+// the only thing the host reads. Ordering comes from the stream alone.
+
+// Roots (:132-137): state, the root event with prob = 1 - exp(-P_nonAD), and round 1's selection
+// (every tree, in order).
+__global__ __launch_bounds__(256) void tree_root_kernel(const KParams P, const TreeRules R, const int64_t n,
+                                                        const double* __restrict__ x0, const double* __restrict__ k0,
+                                                        const double* __restrict__ erg,
+                                                        const int8_t* __restrict__ species, TreeState* __restrict__ state,
+                                                        TreeEv* __restrict__ stack, int32_t* __restrict__ list,
+                                                        int32_t* __restrict__ flag, int32_t* __restrict__ pos) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x[3] = {x0[i], x0[n + i], x0[2 * n + i]}, k[3] = {k0[i], k0[n + i], k0[2 * n + i]};
+  TreeState T{};
+  T.erg = erg[i];
+  T.info = 1;
+  T.active = 1;
+  T.depth = 1;
+  state[i] = T;
+  stack[i * R.stack_cap] = tree_root(x, k, species[i], tree_root_prob(P, x, k, T.erg));
+  list[i] = (int32_t)i;
+  flag[i] = 1;
+  pos[i] = (int32_t)i + 1;
+}
+
+// Pop and pack: entry jp of the last round's list that goes on (flag) pops its tree's next event
+// into slot pos[jp] - 1 of this round's batch of m segments (SoA, stride m) and of its list.
+__global__ __launch_bounds__(256) void tree_pack_kernel(const TreeRules R, const int64_t m_prev, const int64_t m,
+                                                        const int32_t* __restrict__ list_prev,
+                                                        const int32_t* __restrict__ flag, const int32_t* __restrict__ pos,
+                                                        int32_t* __restrict__ list, TreeState* __restrict__ state,
+                                                        const TreeEv* __restrict__ stack, const TreeBatch B,
+                                                        const double dt0, const double ln_dt0) {
+  const int64_t jp = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (jp >= m_prev || !flag[jp]) return;
+  const int64_t j = (int64_t)pos[jp] - 1;
+  if (j < 0 || j >= m) return;
+  const int32_t tree = list_prev[jp];
+  TreeState T = state[tree];
+  if (!tree_pop(T)) return;
+  state[tree] = T;
+  const TreeEv e = stack[(int64_t)tree * R.stack_cap + T.depth];
+  for (int c = 0; c < 3; ++c) {
+    B.x0[c * m + j] = e.x[c];
+    B.k0[c * m + j] = e.k[c];
+  }
+  B.erg[j] = T.erg;
+  B.dw[j] = e.dw;
+  B.lnt0[j] = tree_ln_t0(e.t, dt0, ln_dt0);
+  B.species[j] = (int8_t)e.species;
+  list[j] = tree;
+}
+
+// The step: lane j takes the results of segment j for its tree, appends the finished node to the
+// log (its tree and its sequence number in it inside the record) and says whether the tree goes on.
+__global__ __launch_bounds__(256) void tree_step_kernel(const KParams P, const TreeRules R, const int64_t n, const int64_t m,
+                                                        const int32_t* __restrict__ list, TreeState* __restrict__ state,
+                                                        TreeEv* __restrict__ stack, const TreeBatch B,
+                                                        art_tree_node* __restrict__ log, int32_t* __restrict__ flag,
+                                                        int32_t* __restrict__ err) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const int32_t tree = list[j];
+  flag[j] = 0;
+  // (neither happens: pack fills every slot of the list, and a popped event lies below the
+  // capacity. Should one, no access leaves the arrays: the call fails, the log gets a record of tree 0)
+  const bool in_list = tree >= 0 && tree < n;
+  if (!in_list || state[tree].depth < 0 || state[tree].depth >= R.stack_cap) {
+    *err = 1;
+    art_tree_node none{};
+    log[j] = none;
+    return;
+  }
+  TreeState T = state[tree];
+  SegEnd S;
+  for (int c = 0; c < 3; ++c) {
+    S.x_end[c] = B.x_end[c * m + j];
+    S.k_end[c] = B.k_end[c * m + j];
+  }
+  S.u7_end = B.u7_end[j];
+  S.tau_end = B.tau_end[j];
+  S.status = B.status[j];
+  S.count = B.xcount[j];
+  const XcView X{R.cap, m, j, B.xpos, B.xk, B.xt, B.xdw, B.xp};
+  GroupProbPhysics gp{P, {}};
+  art_tree_node node;
+  const bool go = tree_step(R, (int64_t)tree, T, stack + (int64_t)tree * R.stack_cap, S, X, gp, node);
+  state[tree] = T;
+  log[j] = node;
+  flag[j] = go ? 1 : 0;
+  if (T.overflow) *err = 1;
+}
+
+// The end: get_tree's count and info of every tree, and the counts (n + 1 of them, the last 0) that
+// the exclusive scan turns into node_start.
+__global__ __launch_bounds__(256) void tree_finish_kernel(const TreeRules R, const int64_t n,
+                                                          const TreeState* __restrict__ state,
+                                                          int32_t* __restrict__ counts1, int32_t* __restrict__ counts,
+                                                          int32_t* __restrict__ infos) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {
+    counts1[n] = 0;
+    return;
+  }
+  const TreeState T = state[i];
+  counts1[i] = T.count;
+  if (counts) counts[i] = T.count;
+  if (infos) infos[i] = tree_info(T, R.mc_nodes);
+}
+
+// Flatten: log record q goes to nodes[node_start[its tree] + its sequence number] -- trees in
+// order, each tree's nodes in the order it processed them -- one 8-byte word per thread, pad zeroed.
+constexpr int TREE_NODE_WORDS = (int)(sizeof(art_tree_node) / 8);
+static_assert(sizeof(art_tree_node) % 8 == 0 && offsetof(art_tree_node, pad) == 20, "art_tree_node layout");
+__global__ __launch_bounds__(256) void tree_flatten_kernel(const int64_t total, const art_tree_node* __restrict__ log,
+                                                           const int64_t* __restrict__ node_start,
+                                                           const int64_t capacity, art_tree_node* __restrict__ nodes) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= total * TREE_NODE_WORDS) return;
+  const int64_t q = w / TREE_NODE_WORDS;
+  const int wi = (int)(w - q * TREE_NODE_WORDS);
+  const int64_t dst = node_start[log[q].tree] + log[q].pad;
+  if (dst < 0 || dst >= capacity) return;
+  unsigned long long v = reinterpret_cast<const unsigned long long*>(log + q)[wi];
+  if (wi == 2) v &= 0xffffffffull;  // {status, pad}
+  reinterpret_cast<unsigned long long*>(nodes + dst)[wi] = v;
+}
+
+struct ToI64 {
+  __host__ __device__ int64_t operator()(const int32_t& v) const { return (int64_t)v; }
+};
+using CountIt = hipcub::TransformInputIterator<int64_t, ToI64, const int32_t*>;
+
+size_t tree_scan_bytes(int64_t n) {
+  size_t a = 0, b = 0;
+  (void)hipcub::DeviceScan::InclusiveSum(nullptr, a, (const int32_t*)nullptr, (int32_t*)nullptr, (int)n);
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, CountIt(nullptr, ToI64()), (int64_t*)nullptr, (int)(n + 1));
+  return a > b ? a : b;
+}
+
+hipError_t launch_tree_roots(const KParams& P, const TreeRules& R, int64_t n, const double* x0, const double* k0,
+                             const double* erg, const int8_t* species, TreeState* state, TreeEv* stack, int32_t* list,
+                             int32_t* flag, int32_t* pos, hipStream_t s) {
+  hipLaunchKernelGGL(tree_root_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, R, n, x0, k0, erg, species,
+                     state, stack, list, flag, pos);
+  return hipGetLastError();
+}
+
+hipError_t launch_tree_pack(const TreeRules& R, int64_t m_prev, int64_t m, const int32_t* list_prev, const int32_t* flag,
+                            const int32_t* pos, int32_t* list, TreeState* state, const TreeEv* stack, const TreeBatch& B,
+                            double dt0, double ln_dt0, hipStream_t s) {
+  hipLaunchKernelGGL(tree_pack_kernel, dim3((unsigned)((m_prev + 255) / 256)), dim3(256), 0, s, R, m_prev, m, list_prev,
+                     flag, pos, list, state, stack, B, dt0, ln_dt0);
+  return hipGetLastError();
+}
+
+hipError_t launch_tree_step(const KParams& P, const TreeRules& R, int64_t n, int64_t m, const int32_t* list, TreeState* state,
+                            TreeEv* stack, const TreeBatch& B, art_tree_node* log, int32_t* flag, int32_t* pos,
+                            int32_t* err, void* tmp, size_t tmp_bytes, hipStream_t s) {
+  hipLaunchKernelGGL(tree_step_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, P, R, n, m, list, state, stack,
+                     B, log, flag, err);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return hipcub::DeviceScan::InclusiveSum(tmp, tmp_bytes, (const int32_t*)flag, pos, (int)m, s);
+}
+
+hipError_t launch_tree_finish(const TreeRules& R, int64_t n, const TreeState* state, int32_t* counts1, int32_t* counts,
+                              int32_t* infos, int64_t* node_start, void* tmp, size_t tmp_bytes, hipStream_t s) {
+  hipLaunchKernelGGL(tree_finish_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, s, R, n, state, counts1, counts,
+                     infos);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, CountIt(counts1, ToI64()), node_start, (int)(n + 1), s);
+}
+
+hipError_t launch_tree_flatten(int64_t total, const art_tree_node* log, const int64_t* node_start, int64_t capacity,
+                               art_tree_node* nodes, hipStream_t s) {
+  const int64_t words = total * TREE_NODE_WORDS;
+  if (words <= 0) return hipSuccess;
+  hipLaunchKernelGGL(tree_flatten_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, total, log, node_start,
+                     capacity, nodes);
   return hipGetLastError();
 }
 

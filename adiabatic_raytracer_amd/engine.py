@@ -22,6 +22,13 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def nodes_to_numpy(nodes):
+    """The records of Engine.grow_trees' `nodes` (a uint8 tensor of whole art_tree_node records),
+    copied to the host and viewed as a trees.NODE_DTYPE record array."""
+    from .trees import NODE_DTYPE
+    return nodes.detach().cpu().contiguous().numpy().reshape(-1).view(NODE_DTYPE)
+
+
 class Engine:
     def __init__(self, params: Params, device: int | None = None):
         self.lib = _lib.load()
@@ -164,6 +171,50 @@ class Engine:
                                                _p(sample["x"]), _p(sample["k_init"]), _p(sample["vifty"]), _p(out),
                                                _stream()))
         return out.view(5, n)
+
+    # ---- get_tree (MainRunner.jl:126-352) for n roots, every tree's state in HBM (art_grow_trees_device)
+    def grow_trees(self, x0, k0, erg, species, *, num_cutoff=5, mc_nodes=5, max_nodes=50, splittings_cutoff=-1,
+                   crossing_cap=64, prob_cutoff=1e-10, seed=1769, tree_offset=0, node_capacity=None) -> dict:
+        """The forest of n roots held in HBM -- x0, k0 (3n SoA, float64), erg (n), species (n int8, or
+        one ART_AXION / ART_PHOTON for all) -- on the current stream; the options are trees.grow_trees'.
+        Returns a dict of device tensors: nodes, uint8 (n_nodes, record size), whole art_tree_node
+        records, trees in order and each tree's nodes in the order it processed them (nodes_to_numpy
+        views a copy as trees.NODE_DTYPE); node_start int64 (n + 1): tree i owns records
+        node_start[i] .. node_start[i + 1]; counts, infos int32 (n): get_tree's count and info; and
+        n_nodes (an int). Unlike the other methods it blocks until the forest is done (the driver reads
+        the count of active trees between rounds). node_capacity: records to allocate (default: the
+        bound n (max_nodes + 2), or n for the backtrace form); a smaller one is grown and the forest
+        run again when it does not suffice (ART_E_NOMEM)."""
+        from .trees import NODE_DTYPE
+        rec = NODE_DTYPE.itemsize
+        n = erg.numel()
+        x0, k0, erg = (t.to(F64).contiguous() for t in (x0, k0, erg))
+        if not torch.is_tensor(species):
+            species = torch.full((n,), int(species), dtype=torch.int8, device=self.device)
+        species = species.to(torch.int8).contiguous()
+        if x0.numel() != 3 * n or k0.numel() != 3 * n or species.numel() != n:
+            raise ValueError("grow_trees: x0 and k0 hold 3n values, erg and species n")
+        opts = _lib.TreeOpts(num_cutoff, mc_nodes, max_nodes, splittings_cutoff, crossing_cap, int(tree_offset),
+                             prob_cutoff, seed)
+        per_tree = 1 if (splittings_cutoff > 0 and num_cutoff <= 0) else max_nodes + 2
+        cap = max(1, n * per_tree if node_capacity is None else int(node_capacity))
+        node_start = self.empty(n + 1, dtype=torch.int64)
+        counts, infos = self.empty(n, dtype=torch.int32), self.empty(n, dtype=torch.int32)
+        while True:
+            nodes = self.empty(cap, rec, dtype=torch.uint8)
+            nn = C.c_int64(0)
+            rc = self.lib.art_grow_trees_device(C.byref(self.cp), n, _p(x0), _p(k0), _p(erg), _p(species), C.byref(opts),
+                                                cap, _p(nodes), _p(node_start), _p(counts), _p(infos), C.byref(nn),
+                                                _stream())
+            if rc == -3 and nn.value > cap:  # ART_E_NOMEM: the needed count is known now
+                cap = nn.value
+                continue
+            check(rc)
+            break
+        used = nodes[:nn.value]
+        if 2 * nn.value < cap:  # (do not keep the whole bound alive behind a small view)
+            used = used.clone()
+        return {"nodes": used, "node_start": node_start, "counts": counts, "infos": infos, "n_nodes": int(nn.value)}
 
     # ---- pointwise physics (parity tests)
     def eval_rhs(self, u, tau, erg, species):

@@ -1,7 +1,8 @@
 """Trees and events on the GPU engine: the host side of main_runner_tree (MainRunner.jl:354-763).
 
 grow_trees()        get_tree (MainRunner.jl:126-352) for many trees at once, through the
-                    native batched driver art_grow_trees (csrc/art_forest.cpp).
+                    native batched driver art_grow_trees (csrc/art_forest.cpp), or with
+                    device=True through art_grow_trees_device, every tree's state in HBM.
 main_runner_tree()  the event loop: sample conversion points, weight them (sln_prob),
                     backtrace each one (axion, -k, -B0, every crossing), grow its forward
                     photon tree, and write the reference's npy rows, with the same columns
@@ -37,14 +38,19 @@ NODE_DTYPE = np.dtype([
 
 
 def grow_trees(params: Params, x0, k0, erg, species, *, num_cutoff=5, mc_nodes=5, max_nodes=50,
-               splittings_cutoff=-1, crossing_cap=64, prob_cutoff=1e-10, seed=1769, ntimes=None, tree_offset=0):
+               splittings_cutoff=-1, crossing_cap=64, prob_cutoff=1e-10, seed=1769, ntimes=None, tree_offset=0,
+               device=False):
     """get_tree for n roots RT.node(x0, k0, 0, -1, species, 1, 1, -1, -1, -1) (MainRunner.jl:578-590,
     :653-667). x0, k0: (n, 3) or SoA 3n; erg: erg_inf_ini per root. Returns (nodes, counts,
     infos): nodes is a NODE_DTYPE record array grouped by tree in get_tree's push order.
     With ntimes (>= 2, saveMode 3) a fourth item holds every node's saveNode data
     (art_grow_trees_traj): traj (nodes, ntimes, 3) Cartesian saved points, times (nodes,
     ntimes) their ln t, count (nodes,), xc (nodes, cap, 4) the kept crossings (x, y, z, tc).
-    tree_offset: global id of root 0 (the Monte-Carlo draws are keyed by the global tree id)."""
+    tree_offset: global id of root 0 (the Monte-Carlo draws are keyed by the global tree id).
+    device: grow the forest with every tree's state in HBM (art_grow_trees_device through
+    Engine.grow_trees: one batched launch per round and no per-round copies) instead of the host
+    forest; the same arguments and the same three results. It has no trajectory form (ntimes) and
+    takes the forward and the backtrace form only (not splittings_cutoff > 0 with num_cutoff > 0)."""
     x0, k0 = np.asarray(x0, np.float64), np.asarray(k0, np.float64)
     erg = np.ascontiguousarray(erg, np.float64).reshape(-1)
     n = erg.size
@@ -52,6 +58,17 @@ def grow_trees(params: Params, x0, k0, erg, species, *, num_cutoff=5, mc_nodes=5
         x0, k0 = x0.T, k0.T
     x0, k0 = np.ascontiguousarray(x0).reshape(-1), np.ascontiguousarray(k0).reshape(-1)
     sp = np.ascontiguousarray(np.broadcast_to(np.asarray(species, np.int8), (n,)))
+    if device:
+        if ntimes:
+            raise ValueError("grow_trees: device=True has no trajectory form (ntimes)")
+        import torch
+        from .engine import Engine, nodes_to_numpy
+        eng = Engine(params)
+        up = lambda a: torch.from_numpy(a).to(eng.device)  # noqa: E731
+        r = eng.grow_trees(up(x0), up(k0), up(erg), up(sp), num_cutoff=num_cutoff, mc_nodes=mc_nodes, max_nodes=max_nodes,
+                           splittings_cutoff=splittings_cutoff, crossing_cap=crossing_cap, prob_cutoff=prob_cutoff,
+                           seed=seed, tree_offset=tree_offset)
+        return nodes_to_numpy(r["nodes"]), r["counts"].cpu().numpy(), r["infos"].cpu().numpy()
     opts = TreeOpts(num_cutoff, mc_nodes, max_nodes, splittings_cutoff, crossing_cap, int(tree_offset), prob_cutoff,
                     seed)
     per_tree = 1 if (splittings_cutoff > 0 and num_cutoff <= 0) else max_nodes + 2
@@ -162,7 +179,7 @@ def save_node(fh, node, tr, q):
 def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_DM=0.45, n_maxSample=6,
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
-                     sky_map=None):
+                     sky_map=None, device_trees=False):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -199,7 +216,14 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     with dir_tag also saved beside the npy as skymap_<its stem>.npz (sky_map, theta_edges, phi_edges,
     dw_edges, theta_axis, f_inx). n_dw > 1 without a dw_range bins Δω over (min, max) of the rows
     (numpy's rule, flux_range), which only one process can do: with world > 1 it is an error. With
-    the default None every row, file, run_info key and the reduced vector are unchanged."""
+    the default None every row, file, run_info key and the reduced vector are unchanged.
+
+    device_trees: grow the backtrace and the forward forest with every tree's state in HBM
+    (grow_trees(..., device=True), art_grow_trees_device) instead of the host forest. Tree dumps
+    (saveMode > 2 with a dir_tag) need trajectories, which that driver does not save: ValueError.
+    With the default False every row, file and run_info key is unchanged."""
+    if device_trees and saveMode > 2 and dir_tag is not None:
+        raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
         ntimes = 3  # "Times to store in ODE" (MainRunner.jl:379-381): also names the npy file
     if sky_map is not None:
@@ -231,13 +255,14 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     dumps = saveMode > 2 and dir_tag is not None
     got = grow_trees(replace(params, B0=-params.B0), x, -k, erg, AXION, num_cutoff=0, splittings_cutoff=100000,
                      crossing_cap=backtrace_cap, prob_cutoff=prob_cutoff, seed=seed, ntimes=ntimes if dumps else None,
-                     tree_offset=lo)
+                     tree_offset=lo, device=device_trees)
     nb, c_bck = got[0], got[1]
     samp_back_weight = nb["prob"] * nb["weight"]  # (:635)
     prob0 = nb["prob"]
     # forward photon tree from the sample (:653-667)
     fwd = grow_trees(params, x, k, erg, PHOTON, num_cutoff=num_cutoff, mc_nodes=MC_nodes, max_nodes=max_nodes,
-                     prob_cutoff=prob_cutoff, seed=seed, ntimes=ntimes if dumps else None, tree_offset=lo)
+                     prob_cutoff=prob_cutoff, seed=seed, ntimes=ntimes if dumps else None, tree_offset=lo,
+                     device=device_trees)
     tree, counts, infos = fwd[:3]
     if dumps:  # saveMode > 2: one file per event, the backtrace node then the forward tree
         d = os.path.join(dir_tag, "tree")

@@ -29,6 +29,7 @@
  *                                  Combine_Files.py, Gen_Samples.jl:195-239)
  *   art_grow_trees[_traj]          get_tree (MainRunner.jl:126-352) for n trees, batched
  *                                  (_traj: + saveNode data, MainRunner.jl:17-65)
+ *   art_grow_trees_device          the same forest with roots, tree state and nodes in device memory
  *   art_event_weight_*             sln_prob of a sampled point: dwp_ds cos_w + g_det
  *                                  (MainRunner.jl:498-557, RayTracer.jl:734-754,1327-1403)
  *   art_eval_*_device              pointwise physics (func!, func_axion!, hamiltonian,
@@ -392,6 +393,36 @@ int art_grow_trees(const art_params* p, int64_t n, const double* x0, const doubl
                    const double* erg, const int8_t* species, const art_tree_opts* opts,
                    int64_t node_capacity, art_tree_node* nodes, int64_t* n_nodes,
                    int32_t* counts, int32_t* infos);
+
+/* art_grow_trees with every tree's state in device memory (HBM): the roots come as device arrays
+ * (the sampler's outputs, say) and the nodes are left in device memory, in art_grow_trees' layout:
+ * trees in order, each tree's nodes in the order it processed them. A round is one pack kernel, one
+ * batched art_propagate_device launch, one step kernel (one lane per active tree) and one scan, all
+ * on `stream`; the host reads one number per round, the count of trees still active, and runs at
+ * most max_nodes + 2 rounds.
+ *   - x0, k0, erg, species, nodes, node_start, counts, infos: device pointers. p, opts, n_nodes: host.
+ *   - node_start (n + 1 entries, may be NULL): tree i owns nodes[node_start[i] .. node_start[i + 1]).
+ *     counts, infos (n, may be NULL) as art_grow_trees'. *n_nodes receives the number of nodes;
+ *     ART_E_NOMEM with the needed count in *n_nodes when node_capacity is too small (nothing else
+ *     is written then).
+ *   - Every kernel and every scratch allocation (the stream-ordered allocator) goes on `stream`.
+ *   - Unlike the other *_device entry points it BLOCKS: it returns when the forest is done and its
+ *     outputs are written. It reads a count between rounds, so it cannot be captured into a graph.
+ *     Calls on other streams from other threads proceed while it waits.
+ *   - Forward trees (splittings_cutoff <= 0) and the backtrace form main_runner_tree uses
+ *     (splittings_cutoff > 0 with num_cutoff <= 0: only the root is processed, every crossing up
+ *     to crossing_cap is merged and grouped, the root's weight becomes prod(1 - P_j)).
+ *     splittings_cutoff > 0 with num_cutoff > 0 is ART_E_INVALID here, and trajectory dumps
+ *     (art_grow_trees_traj) have no device form.
+ *   - ART_E_INVALID before any device is touched: NULL p, opts or n_nodes; n < 0; n > 0 with a NULL
+ *     input; max_nodes < 0; crossing_cap < 0; the unsupported mode.
+ *   - Against art_grow_trees: the integrator and the probabilities are the same kernels; exp and
+ *     log of the bookkeeping are the device's (each within 1 ulp of the host's), and a "rare fail"
+ *     node (|kc| > 1) is recorded as the reference leaves it, without crossings (n_cross = 0). */
+int art_grow_trees_device(const art_params* p, int64_t n, const double* x0, const double* k0,
+                          const double* erg, const int8_t* species, const art_tree_opts* opts,
+                          int64_t node_capacity, art_tree_node* nodes, int64_t* node_start,
+                          int32_t* counts, int32_t* infos, int64_t* n_nodes, void* stream);
 
 /* saveMode 3 tree dumps (saveNode, MainRunner.jl:17-65, called at :612 and :671): per node,
  * its saved trajectory points (art_propagate_traj_*) and all of its crossings after the

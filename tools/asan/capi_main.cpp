@@ -99,6 +99,29 @@ int main() {
     CHECK(art_sky_map_segments_device(&p, &sk, n, d, d, d, st.data(), nullptr, nullptr, nullptr, d, nullptr, nullptr) ==
           ART_E_INVALID);
   }
+  // the device forest: every argument check comes before the device; with roots it reaches the HIP runtime
+  {
+    art_tree_opts to{5, 5, 50, -1, 64, 0, 1e-10, 1769};
+    int64_t nn = -1;
+    double* d = x.data();
+    CHECK(art_grow_trees_device(nullptr, n, d, d, d, sp.data(), &to, 0, nullptr, nullptr, nullptr, nullptr, &nn, nullptr) == ART_E_INVALID);
+    CHECK(art_grow_trees_device(&p, n, d, d, d, sp.data(), nullptr, 0, nullptr, nullptr, nullptr, nullptr, &nn, nullptr) == ART_E_INVALID);
+    CHECK(art_grow_trees_device(&p, n, d, d, d, sp.data(), &to, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == ART_E_INVALID);
+    CHECK(art_grow_trees_device(&p, -1, d, d, d, sp.data(), &to, 0, nullptr, nullptr, nullptr, nullptr, &nn, nullptr) == ART_E_INVALID);
+    CHECK(art_grow_trees_device(&p, n, d, d, nullptr, sp.data(), &to, 0, nullptr, nullptr, nullptr, nullptr, &nn, nullptr) == ART_E_INVALID);
+    art_tree_opts bad_opts = to;
+    bad_opts.max_nodes = -1;
+    CHECK(art_grow_trees_device(&p, n, d, d, d, sp.data(), &bad_opts, 0, nullptr, nullptr, nullptr, nullptr, &nn, nullptr) == ART_E_INVALID);
+    bad_opts = to; bad_opts.crossing_cap = -2;
+    CHECK(art_grow_trees_device(&p, n, d, d, d, sp.data(), &bad_opts, 0, nullptr, nullptr, nullptr, nullptr, &nn, nullptr) == ART_E_INVALID);
+    bad_opts = to; bad_opts.splittings_cutoff = 100000;
+    CHECK(art_grow_trees_device(&p, n, d, d, d, sp.data(), &bad_opts, 0, nullptr, nullptr, nullptr, nullptr, &nn, nullptr) == ART_E_INVALID);
+    CHECK(nn == -1);
+    CHECK(art_grow_trees_device(&p, 0, nullptr, nullptr, nullptr, nullptr, &to, 0, nullptr, nullptr, nullptr, nullptr, &nn, nullptr) == ART_OK);
+    CHECK(nn == 0);
+    rc = art_grow_trees_device(&p, n, d, d, d, sp.data(), &to, 0, nullptr, nullptr, nullptr, nullptr, &nn, nullptr);
+    CHECK(rc == ART_E_HIP || rc == ART_E_NOMEM);
+  }
   // the reduction: nothing to reduce without a communicator, bad ranks rejected
   double h[4] = {1, 2, 3, 4};
   CHECK(art_flux_allreduce(h, 4, nullptr) == ART_E_INVALID);

@@ -48,6 +48,24 @@ hipError_t launch_eval_condition(const KParams&, int64_t, const double*, const d
 }
 hipError_t launch_eval_cyclotron(const KParams&, int64_t, const double*, const double*, const double*, double*, double*,
                                  hipStream_t) { return hipErrorNoDevice; }
+size_t tree_scan_bytes(int64_t) { return 0; }
+hipError_t launch_tree_roots(const KParams&, const TreeRules&, int64_t, const double*, const double*, const double*,
+                             const int8_t*, TreeState*, TreeEv*, int32_t*, int32_t*, int32_t*, hipStream_t) {
+  return hipErrorNoDevice;
+}
+hipError_t launch_tree_pack(const TreeRules&, int64_t, int64_t, const int32_t*, const int32_t*, const int32_t*, int32_t*,
+                            TreeState*, const TreeEv*, const TreeBatch&, double, double, hipStream_t) {
+  return hipErrorNoDevice;
+}
+hipError_t launch_tree_step(const KParams&, const TreeRules&, int64_t, int64_t, const int32_t*, TreeState*, TreeEv*,
+                            const TreeBatch&, art_tree_node*, int32_t*, int32_t*, int32_t*, void*, size_t, hipStream_t) {
+  return hipErrorNoDevice;
+}
+hipError_t launch_tree_finish(const TreeRules&, int64_t, const TreeState*, int32_t*, int32_t*, int32_t*, int64_t*, void*,
+                              size_t, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_tree_flatten(int64_t, const art_tree_node*, const int64_t*, int64_t, art_tree_node*, hipStream_t) {
+  return hipErrorNoDevice;
+}
 MFn nl_eval_math(int) { return nullptr; }
 hipError_t launch_eval_math(int, int, int64_t, const double*, const double*, double*, double*, hipStream_t) {
   return hipErrorNoDevice;

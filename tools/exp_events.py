@@ -6,8 +6,14 @@ Each event is one sampled conversion point (find_samples_new). It then gets its 
 tree (axion, -B0, every crossing) and its forward photon tree. The defaults are
 num_cutoff = MC_nodes = 5 and max_nodes = 50.
 
-usage: [ART_DONATE=lanes] exp_events.py [flat|gr] [gpu event counts, comma-separated] [cpu events]
-Prints one JSON line per run."""
+usage: [ART_DONATE=lanes] [ART_DEVICE_TREES=0|1|ab] exp_events.py [flat|gr] [gpu event counts, comma-separated]
+       [cpu events] [repeats]
+ART_DEVICE_TREES: 0 (the default) grows the trees with the host forest (art_grow_trees), 1 with the
+device-resident driver (main_runner_tree(device_trees=True), art_grow_trees_device), ab runs both,
+alternating, `repeats` times (default 1) for each event count. Prints one JSON line per run; its
+"trees" key says which forest ran. After each event count's runs one more line ("forest shape",
+untimed) gives the forward forest's rounds -- its batched propagate launches -- and the sum of their
+batch sizes, from the trees' counts."""
 import json
 import os
 import sys
@@ -21,20 +27,31 @@ CFG = {"flat": dict(theta_m=0.2, mass_a=1e-5, flat=True), "gr": dict(theta_m=0.0
 cfg = sys.argv[1] if len(sys.argv) > 1 else "flat"
 counts = [int(c) for c in (sys.argv[2] if len(sys.argv) > 2 else "1000,10000").split(",")]
 n_cpu = int(sys.argv[3]) if len(sys.argv) > 3 else 50
+repeats = int(sys.argv[4]) if len(sys.argv) > 4 else 1
 p = A.Params(**CFG[cfg])
 DONATE = int(os.environ.get("ART_DONATE", "-1"))  # tail donation of the forest's launches (-1: the library default)
 if DONATE >= 0:
     import ctypes as C
     A._lib.load().art_set_tail_donation(C.c_int32(DONATE))
+SIDES = {"0": [False], "1": [True], "ab": [False, True]}[os.environ.get("ART_DEVICE_TREES", "0")]
 
-trees.main_runner_tree(p, 65)  # warm-up: library load, kernels, pools
+for dev in SIDES:
+    trees.main_runner_tree(p, 65, device_trees=dev)  # warm-up: library load, kernels, pools
 for n in counts:
-    info = {}
-    t0 = time.perf_counter()
-    rows = trees.main_runner_tree(p, n + 1, run_info=info)
-    dt = time.perf_counter() - t0
-    print(json.dumps({"config": cfg, "side": "gpu", "donate": DONATE, "events": n, "wall_s": dt, "events_per_s": n / dt,
-                      "rows": int(rows.shape[0]), "f_inx": info["f_inx"]}), flush=True)
+    for _ in range(repeats):
+        for dev in SIDES:
+            info = {}
+            t0 = time.perf_counter()
+            rows = trees.main_runner_tree(p, n + 1, run_info=info, device_trees=dev)
+            dt = time.perf_counter() - t0
+            print(json.dumps({"config": cfg, "side": "gpu", "trees": "device" if dev else "host", "donate": DONATE,
+                              "events": n, "wall_s": dt, "events_per_s": n / dt, "rows": int(rows.shape[0]),
+                              "f_inx": info["f_inx"]}), flush=True)
+    # the forward forest's shape (untimed): a tree takes part in `count` rounds, one segment in each
+    s = A.sample_conversion_points(p, n, seed=1769)
+    _, cnt, _ = trees.grow_trees(p, s["x"], s["k_init"], s["erg"], 1, device=SIDES[-1])
+    print(json.dumps({"config": cfg, "side": "forest shape", "trees": "device" if SIDES[-1] else "host", "events": n,
+                      "rounds": int(cnt.max()) if n else 0, "batch_sum": int(cnt.sum())}), flush=True)
 
 if n_cpu > 0:
     import oracle as O
