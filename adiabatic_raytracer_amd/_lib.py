@@ -39,6 +39,23 @@ class SkySpec(C.Structure):  # include/art.h art_sky_spec
                 ("mode", C.c_int32), ("dw_lo", C.c_double), ("dw_hi", C.c_double)]
 
 
+class EventRowsIn(C.Structure):  # include/art.h art_event_rows_in
+    _fields_ = [("n_events", C.c_int64), ("event_offset", C.c_int64), ("x", C.c_void_p), ("k_init", C.c_void_p),
+                ("attempts", C.c_void_p), ("weight5", C.c_void_p), ("back", C.c_void_p), ("back_counts", C.c_void_p),
+                ("nodes", C.c_void_p), ("n_nodes", C.c_int64), ("counts", C.c_void_p), ("infos", C.c_void_p),
+                ("cyc_slot", C.c_void_p), ("cyc_n", C.c_int64), ("cyc_tau", C.c_void_p),
+                ("cyc_end", C.POINTER(SegmentOut))]
+
+
+class EventRowsOut(C.Structure):  # include/art.h art_event_rows_out
+    _fields_ = [("ncols", C.c_int32), ("nbins", C.c_int32), ("rows", C.c_void_p), ("row_capacity", C.c_int64),
+                ("flux", C.c_void_p), ("sky", C.POINTER(SkySpec)), ("sky_hist", C.c_void_p), ("bin_out", C.c_void_p),
+                ("totals", C.c_void_p)]
+
+
+EVENT_TOTALS = ("rows", "photon_rows", "sum_axion", "sum_photon", "attempts_minus_1", "cyclotron_mismatches")
+
+
 # name -> (restype, argtypes); the test suite checks this table against include/art.h
 class TreeOpts(C.Structure):  # include/art.h art_tree_opts
     _fields_ = [("num_cutoff", C.c_int32), ("mc_nodes", C.c_int32), ("max_nodes", C.c_int32),
@@ -101,6 +118,9 @@ SIGNATURES = {
     "art_histogram3_device": (C.c_int, [_i64, _v, _v, _v, _v, _v, C.POINTER(_i32), C.POINTER(_d), C.POINTER(_d), _i32, _v,
                                         _v]),
     "art_sky_map_segments_device": (C.c_int, [_P, C.POINTER(SkySpec), _i64, _v, _v, _v, _v, _v, _v, _v, _v, _v, _v]),
+    "art_event_rows_device": (C.c_int, [_P, C.POINTER(EventRowsIn), C.POINTER(EventRowsOut), _v]),
+    "art_event_gather_photons_device": (C.c_int, [_P, _i64, _v, _i64, _v, _i64, _v, _v, _v, _v, _v, _v, _v,
+                                                  C.POINTER(_i64), _v]),
     "art_comm_unique_id": (C.c_int, [_v]),
     "art_comm_init": (C.c_int, [_i32, _i32, _v]),
     "art_flux_allreduce": (C.c_int, [_v, _i64, _v]),

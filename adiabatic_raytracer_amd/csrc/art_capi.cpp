@@ -28,6 +28,7 @@
 #include "../../include/art.h"
 #include "art_core.h"
 #include "art_internal.h"
+#include "art_event_rows.h"
 
 
 namespace {
@@ -2538,6 +2539,126 @@ int art_sky_map_segments_device(const art_params* p, const art_sky_spec* spec, i
   HIP_OK(art::launch_sky_map_segments(art::make_kparams(*p), n, x_end, k_end, u7_end, status, species, w, dw_offset, A,
                                       spec->theta_axis, spec->mode, hist, bin_out, pick(ctx, stream)));
   return ART_OK;
+}
+
+// The rows, flux, sky map and totals of a chunk of events whose forests lie in HBM (include/art.h):
+// a scan of the final nodes and event_rows_kernel, both on `stream`.
+int art_event_rows_device(const art_params* p, const art_event_rows_in* in, const art_event_rows_out* out,
+                          void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
+  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
+  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
+  if (out->ncols != art::EVENT_COLS_SHORT && out->ncols != art::EVENT_COLS_FULL)
+    return fail(ART_E_INVALID, "ncols must be 13 or 29");
+  if ((out->rows || out->bin_out) && out->row_capacity < in->n_nodes)
+    return fail(ART_E_INVALID, "row_capacity must be >= n_nodes");
+  if (out->nbins < 0 || out->nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
+  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
+  int cos_axis = 1, mode = 2;
+  if (out->sky) {
+    const art_sky_spec* spec = out->sky;
+    if (spec->theta_axis != 0 && spec->theta_axis != 1)
+      return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
+    const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
+    const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
+    const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
+    if ((rc = sky_axes(nb, lo, hi, spec->n_dw == 1, spec->mode, &A))) return rc;
+    if (spec->mode == 1 && 2 * (int64_t)nb[0] * nb[1] * nb[2] + 2 * out->nbins > art::SKY_LDS_DOUBLES)
+      return fail(ART_E_INVALID, "sky map mode 1: the sky and flux tables exceed the LDS budget of 8192 doubles");
+    cos_axis = spec->theta_axis;
+    mode = spec->mode;
+  }
+  if (in->n_events == 0 || (in->n_nodes == 0 && !in->attempts)) return ART_OK;
+  if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
+  if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
+  if (out->sky && !out->sky_hist) return fail(ART_E_INVALID, "sky_hist is NULL");
+  if (in->n_nodes > 0 && (!in->x || !in->k_init || !in->weight5 || !in->back || !in->back_counts || !in->nodes ||
+                          !in->counts || !in->infos))
+    return fail(ART_E_INVALID, "NULL input buffer");
+  const art_segment_out* ce = in->cyc_end;
+  if (in->cyc_slot && (in->cyc_n < 0 || (in->cyc_n > 0 && (!in->cyc_tau || !ce || !ce->x_end || !ce->k_end ||
+                                                           !ce->u7_end || !ce->tau_end || !ce->status))))
+    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0, cyc_tau and the re-run's end states");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  hipStream_t s = pick(ctx, stream);
+  art::EventRowsArgs a{};
+  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
+  a.row_capacity = out->row_capacity;
+  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
+  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
+  if (in->cyc_slot) {
+    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
+    if (ce) {
+      a.cyc_x_end = ce->x_end; a.cyc_k_end = ce->k_end; a.cyc_u7_end = ce->u7_end; a.cyc_tau_end = ce->tau_end;
+      a.cyc_status = ce->status;
+    }
+  }
+  a.mass_a = p->mass_a;
+  a.ncols = out->ncols; a.nbins = out->nbins;
+  a.rows = out->rows; a.flux = out->flux; a.sky_hist = out->sky ? out->sky_hist : nullptr; a.totals = out->totals;
+  a.bin_out = out->sky ? out->bin_out : nullptr;
+  void* block = nullptr;
+  if (in->n_nodes > 0) {
+    const size_t pos_bytes = ((size_t)in->n_nodes * 4 + 255) & ~(size_t)255, tmp_bytes = art::event_scan_bytes(in->n_nodes);
+    if ((rc = scratch_alloc(s, pos_bytes + tmp_bytes, &block))) return rc;
+    a.pos = (const int32_t*)block;
+    hipError_t e = art::launch_event_scan(in->n_nodes, in->nodes, false, (int32_t*)block, (char*)block + pos_bytes,
+                                          tmp_bytes, s);
+    if (e == hipSuccess) e = art::launch_event_rows(a, A, cos_axis, mode, s);
+    (void)hipFreeAsync(block, s);
+    HIP_OK(e);
+  } else {
+    HIP_OK(art::launch_event_rows(a, A, cos_axis, mode, s));
+  }
+  return ART_OK;
+}
+
+// The cyclotron re-run's batch (include/art.h): scan, one count to the host, gather.
+int art_event_gather_photons_device(const art_params* p, int64_t n_events, const double* erg, int64_t n_nodes,
+                                    const art_tree_node* nodes, int64_t capacity, double* x0, double* k0,
+                                    double* erg_out, double* dw, double* ln_t0, int8_t* species, int32_t* slot,
+                                    int64_t* n_out, void* stream) {
+  std::unique_lock<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!n_out) return fail(ART_E_INVALID, "n_out is NULL");
+  if (n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
+  if (n_nodes < 0 || n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
+  if (capacity < 0) return fail(ART_E_INVALID, "capacity must be >= 0");
+  *n_out = 0;
+  if (n_nodes == 0) return ART_OK;
+  if (!erg || !nodes || !slot) return fail(ART_E_INVALID, "NULL input buffer");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  hipStream_t s = pick(ctx, stream);
+  TreeScratch ts;  // (its block and its pinned word, released when the call returns)
+  ts.s = s;
+  const size_t pos_bytes = ((size_t)(n_nodes + 1) * 4 + 255) & ~(size_t)255, tmp_bytes = art::event_scan_bytes(n_nodes + 1);
+  if ((rc = scratch_alloc(s, pos_bytes + tmp_bytes, &ts.block))) return rc;
+  if (hipHostMalloc((void**)&ts.host, 64, hipHostMallocDefault) != hipSuccess) return fail(ART_E_NOMEM, "hipHostMalloc failed");
+  int32_t* pos = (int32_t*)ts.block;
+  // the count is the sum of the last prefix and the last node's own flag: both come to the host
+  HIP_OK(art::launch_event_scan(n_nodes, nodes, true, pos, (char*)ts.block + pos_bytes, tmp_bytes, s));
+  HIP_OK(hipMemcpyAsync(ts.host, pos + (n_nodes - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(ts.host + 2, &nodes[n_nodes - 1], 2 * sizeof(int32_t) + sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  lk.unlock();
+  const hipError_t we = hipStreamSynchronize(s);
+  lk.lock();
+  if (we != hipSuccess) return fail(ART_E_HIP, "hipStreamSynchronize: %s", hipGetErrorString(we));
+  // ts.host[2..4]: the last node's tree, species, is_final
+  const int64_t m = (int64_t)ts.host[0] + ((ts.host[4] != 0 && ts.host[3] != ART_AXION) ? 1 : 0);
+  *n_out = m;
+  if (m > capacity) return fail(ART_E_NOMEM, "capacity is too small: %s final photons", std::to_string(m).c_str());
+  if (m > 0 && (!x0 || !k0 || !erg_out || !dw || !ln_t0 || !species)) return fail(ART_E_INVALID, "NULL batch buffer");
+  art::TreeBatch B{};
+  B.x0 = x0; B.k0 = k0; B.erg = erg_out; B.dw = dw; B.lnt0 = ln_t0; B.species = species;
+  const double dt0 = std::exp(-30.0), ln_dt0 = std::log(dt0);  // art_grow_trees_device's
+  HIP_OK(art::launch_event_gather(n_nodes, nodes, pos, n_events, erg, m, B, slot, dt0, ln_dt0, s));
+  return ART_OK;  // (ts releases pos in the stream's order, after the gather)
 }
 
 int art_eval_rhs_device(const art_params* p, int64_t n, const double* u, const double* tau, const double* erg,

@@ -303,4 +303,30 @@ hipError_t launch_tree_finish(const TreeRules& R, int64_t n, const TreeState* st
 // the log's `total` records into nodes (capacity records) at node_start[tree] + sequence
 hipError_t launch_tree_flatten(int64_t total, const art_tree_node* log, const int64_t* node_start, int64_t capacity,
                                art_tree_node* nodes, hipStream_t s);
+// Event rows (art_event_rows_device, art_event_gather_photons_device; event_rows_kernel and the row
+// math of art_event_rows.h). Device pointers; art_event_rows_in / _out of include/art.h flattened,
+// with pos the exclusive sum of is_final != 0 over the node records.
+struct EventRowsArgs {
+  int64_t n_events, event_offset, n_nodes, row_capacity, cyc_n;
+  const double *x, *k_init, *weight5;
+  const int32_t* attempts;
+  const art_tree_node *back, *nodes;
+  const int32_t *back_counts, *counts, *infos, *pos, *cyc_slot;
+  const double *cyc_tau, *cyc_x_end, *cyc_k_end, *cyc_u7_end, *cyc_tau_end;
+  const int32_t* cyc_status;
+  double mass_a;
+  int32_t ncols, nbins;
+  double *rows, *flux, *sky_hist, *totals;
+  int32_t* bin_out;
+};
+// scratch of the scans over n_nodes records; pos[i] = final (or final photon) nodes before record i
+size_t event_scan_bytes(int64_t n_nodes);
+hipError_t launch_event_scan(int64_t n_nodes, const art_tree_node* nodes, bool photons_only, int32_t* pos, void* tmp,
+                             size_t tmp_bytes, hipStream_t s);
+// final photon node i into slot pos[i] of the batch B of m segments (x0, k0, erg, dw, lnt0, species), slot[i] = pos[i] or -1
+hipError_t launch_event_gather(int64_t n_nodes, const art_tree_node* nodes, const int32_t* pos, int64_t n_events,
+                               const double* erg, int64_t m, const TreeBatch& B, int32_t* slot, double dt0, double ln_dt0,
+                               hipStream_t s);
+// rows, flux, sky map (A, cos_axis, mode as launch_sky_map_segments; sky_hist null: none) and totals in one pass
+hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_axis, int mode, hipStream_t s);
 }  // namespace art

@@ -17,6 +17,7 @@
 #include "art_helper.h"
 #include "art_eval_math.h"
 #include "art_tree_step.h"
+#include "art_event_rows.h"
 
 namespace art {
 
@@ -940,6 +941,165 @@ hipError_t launch_tree_flatten(int64_t total, const art_tree_node* log, const in
   if (words <= 0) return hipSuccess;
   hipLaunchKernelGGL(tree_flatten_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, total, log, node_start,
                      capacity, nodes);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Event rows (art_event_rows_device): one pass over the forward forest's node records turns its
+// final nodes into main_runner_tree's npy rows (art_event_rows.h), in node order, and bins them
+// into the azimuth flux table and the sky map while they are in registers. The order comes from an
+// exclusive sum of is_final != 0 over the records (read through an iterator: no flag array), so
+// row r is the r-th final node, as tree[tree["is_final"] != 0] orders them.
+struct FinalOf {
+  __host__ __device__ int32_t operator()(const art_tree_node& nd) const { return nd.is_final != 0 ? 1 : 0; }
+};
+struct FinalPhotonOf {
+  __host__ __device__ int32_t operator()(const art_tree_node& nd) const {
+    return (nd.is_final != 0 && nd.species != ART_AXION) ? 1 : 0;
+  }
+};
+using FinalIt = hipcub::TransformInputIterator<int32_t, FinalOf, const art_tree_node*>;
+using FinalPhotonIt = hipcub::TransformInputIterator<int32_t, FinalPhotonOf, const art_tree_node*>;
+
+size_t event_scan_bytes(int64_t n_nodes) {
+  size_t a = 0, b = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, FinalIt(nullptr, FinalOf()), (int32_t*)nullptr, (int)n_nodes);
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, FinalPhotonIt(nullptr, FinalPhotonOf()), (int32_t*)nullptr,
+                                         (int)n_nodes);
+  return a > b ? a : b;
+}
+
+hipError_t launch_event_scan(int64_t n_nodes, const art_tree_node* nodes, bool photons_only, int32_t* pos, void* tmp,
+                             size_t tmp_bytes, hipStream_t s) {
+  if (photons_only)
+    return hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, FinalPhotonIt(nodes, FinalPhotonOf()), pos, (int)n_nodes, s);
+  return hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, FinalIt(nodes, FinalOf()), pos, (int)n_nodes, s);
+}
+
+// The cyclotron re-run's inputs: final photon node i goes to slot pos[i] of a segment batch of m
+// (SoA, stride m) with the forest's own inputs -- x0, k0, its tree's erg, dw0, and ln t0 by
+// tree_pack_kernel's function and constants -- and slot[i] says where (-1: no re-run).
+__global__ __launch_bounds__(256) void event_gather_kernel(const int64_t n_nodes, const art_tree_node* __restrict__ nodes,
+                                                           const int32_t* __restrict__ pos, const int64_t n_events,
+                                                           const double* __restrict__ erg, const int64_t m,
+                                                           const TreeBatch B, int32_t* __restrict__ slot, const double dt0,
+                                                           const double ln_dt0) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_nodes) return;
+  const art_tree_node& nd = nodes[i];
+  const int64_t j = pos[i];
+  const bool take = FinalPhotonOf()(nd) && j >= 0 && j < m && nd.tree >= 0 && nd.tree < n_events;
+  slot[i] = take ? (int32_t)j : -1;
+  if (!take) return;
+  for (int c = 0; c < 3; ++c) {
+    B.x0[c * m + j] = nd.x0[c];
+    B.k0[c * m + j] = nd.k0[c];
+  }
+  B.erg[j] = erg[nd.tree];
+  B.dw[j] = nd.dw0;
+  B.lnt0[j] = tree_ln_t0(nd.t0, dt0, ln_dt0);
+  B.species[j] = (int8_t)ART_PHOTON;
+}
+
+hipError_t launch_event_gather(int64_t n_nodes, const art_tree_node* nodes, const int32_t* pos, int64_t n_events,
+                               const double* erg, int64_t m, const TreeBatch& B, int32_t* slot, double dt0, double ln_dt0,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(event_gather_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, s, n_nodes, nodes, pos,
+                     n_events, erg, m, B, slot, dt0, ln_dt0);
+  return hipGetLastError();
+}
+
+// event_row's source of its event's values: each is loaded from HBM where its column is written
+struct EventLoad {
+  const EventRowsArgs& a;
+  const int64_t e;
+  __device__ double x(int c) const { return a.x[c * a.n_events + e]; }
+  __device__ double k(int c) const { return a.k_init[c * a.n_events + e]; }
+  __device__ double cos_w() const { return a.weight5[e]; }
+  __device__ double sln_prob() const { return a.weight5[2 * a.n_events + e]; }
+  __device__ double vel_eng() const { return a.weight5[4 * a.n_events + e]; }
+  __device__ double back_prob() const { return a.back[e].prob; }
+  __device__ double back_weight() const { return a.back[e].weight; }
+  __device__ double back_count() const { return (double)a.back_counts[e]; }
+  __device__ double count() const { return (double)a.counts[e]; }
+  __device__ double info() const { return (double)a.infos[e]; }
+};
+
+// One lane per node record (grid-stride). LDS holds [the flux table, 2 nbins | the sky table when
+// LDS]; the sky map goes through sky_accumulate, the flux table is block-private beside it and
+// flushed like it, the totals are summed per lane, then per wave, and added once per wave.
+template <bool LDS>
+__global__ __launch_bounds__(1024) void event_rows_kernel(const EventRowsArgs a, const SkyAxes A, const int cos_axis,
+                                                           const int sky_table) {
+  extern __shared__ __attribute__((aligned(16))) double sh[];
+  double* sh_flux = sh;
+  double* sh_sky = sh + 2 * a.nbins;
+  for (int b = threadIdx.x; b < 2 * a.nbins; b += blockDim.x) sh_flux[b] = 0.0;
+  if (!LDS) __syncthreads();  // (the LDS path syncs inside sky_accumulate, after zeroing its table)
+  double tot[EV_TOT_COUNT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const int64_t n = a.n_nodes > a.n_events ? a.n_nodes : a.n_events;
+  sky_accumulate<LDS>(n, LDS ? sky_table : 0, a.sky_hist, sh_sky, [&](int64_t i, double& v) {
+    if (i < a.n_events && a.attempts) tot[EV_TOT_ATTEMPTS] += (double)((int64_t)a.attempts[i] - 1);
+    if (i >= a.n_nodes) return -1;
+    const art_tree_node& nd = a.nodes[i];
+    const int64_t e = nd.tree;
+    if (nd.is_final == 0 || e < 0 || e >= a.n_events) return -1;
+    const int64_t r = a.pos[i];
+    const EventLoad E{a, e};
+    double tau = 0.0;
+    if (a.cyc_slot) {
+      const int64_t j = a.cyc_slot[i], m = a.cyc_n;
+      if (j >= 0 && j < m) {
+        tau = a.cyc_tau[j];
+        bool same = a.cyc_status[j] == nd.status && event_same(a.cyc_u7_end[j], nd.u7_end) &&
+                    event_same(a.cyc_tau_end[j], nd.tau_end);
+        for (int c = 0; c < 3; ++c)
+          same = same && event_same(a.cyc_x_end[c * m + j], nd.x_end[c]) && event_same(a.cyc_k_end[c * m + j], nd.k_end[c]);
+        if (!same) tot[EV_TOT_MISMATCH] += 1.0;
+      } else if (nd.species != ART_AXION) {
+        tot[EV_TOT_MISMATCH] += 1.0;  // a final photon without its re-run
+      }
+    }
+    double* dst = (a.rows && r >= 0 && r < a.row_capacity) ? a.rows + r * a.ncols : nullptr;
+    const EventRowBins B = event_row(nd, E, a.event_offset, a.mass_a, tau, a.cyc_slot != nullptr, a.ncols, dst);
+    const int sp = B.species;
+    v = B.power;
+    tot[EV_TOT_ROWS] += 1.0;
+    tot[EV_TOT_PHOTONS] += (double)sp;
+    tot[EV_TOT_SUM_AXION + sp] += v;
+    if (a.nbins > 0) {
+      const int fb = np_hist_bin(B.phi, a.nbins);
+      if (fb >= 0) atomicAdd(&sh_flux[sp * a.nbins + fb], v);
+    }
+    int idx = -1;
+    if (a.sky_hist) idx = sky_bin_of(A, cos_axis ? B.cos_theta : B.theta, B.phi, B.dw, sp);
+    if (a.bin_out && r >= 0 && r < a.row_capacity) a.bin_out[r] = idx;
+    return idx;
+  });
+  __syncthreads();
+  for (int b = threadIdx.x; b < 2 * a.nbins; b += blockDim.x)
+    if (sh_flux[b] != 0.0) unsafeAtomicAdd(&a.flux[b], sh_flux[b]);
+  for (int q = 0; q < EV_TOT_COUNT; ++q) {
+    double t = tot[q];
+    for (int off = warpSize / 2; off > 0; off >>= 1) t += __shfl_down(t, off);
+    if ((threadIdx.x & (warpSize - 1)) == 0 && t != 0.0) unsafeAtomicAdd(&a.totals[q], t);
+  }
+}
+
+hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_axis, int mode, hipStream_t s) {
+  const int64_t n = a.n_nodes > a.n_events ? a.n_nodes : a.n_events;
+  if (n <= 0) return hipSuccess;
+  // the sky launches' geometry; without a sky map, its HBM path's (no table in LDS)
+  SkyLaunch L = sky_launch(n, A, a.sky_hist ? mode : 2);
+  const int64_t table = 2 * (int64_t)A.n[0] * A.n[1] * A.n[2];
+  // the two tables share the 64 KiB a block takes (mode 1 beyond it is refused by the caller)
+  if (L.lds && table + 2 * a.nbins > SKY_LDS_DOUBLES) {
+    const SkyLaunch G = sky_launch(n, A, 2);
+    L = G;
+  }
+  const size_t shmem = L.shmem + 2 * (size_t)a.nbins * sizeof(double);
+  const auto fn = L.lds ? &event_rows_kernel<true> : &event_rows_kernel<false>;
+  hipLaunchKernelGGL(fn, dim3(L.grid), dim3(L.block), shmem, s, a, A, cos_axis, (int)table);
   return hipGetLastError();
 }
 

@@ -216,6 +216,183 @@ class Engine:
             used = used.clone()
         return {"nodes": used, "node_start": node_start, "counts": counts, "infos": infos, "n_nodes": int(nn.value)}
 
+    # ---- main_runner_tree's rows, flux and sky map from forests in HBM (art_event_rows_device)
+    def _sky_spec(self, sky):
+        """(SkySpec, shape, the keywords completed) of a sky-map dict: sky_map()'s keywords n_theta, n_phi,
+        n_dw, theta_axis, dw_range, and mode."""
+        kw = {"n_theta": 32, "n_phi": 64, "n_dw": 1, "theta_axis": "cos", "dw_range": None, "mode": 0}
+        if set(sky) - set(kw):
+            raise ValueError(f"sky_map: unknown keys {sorted(set(sky) - set(kw))}")
+        kw.update(sky)
+        if kw["theta_axis"] not in _lib.THETA_AXIS:
+            raise ValueError(f"theta_axis must be 'cos' or 'theta', not {kw['theta_axis']!r}")
+        if kw["n_dw"] > 1 and kw["dw_range"] is None:
+            raise ValueError("sky_map: n_dw > 1 needs a dw_range (a data-dependent range cannot be binned chunk by chunk)")
+        lo, hi = (0.0, 0.0) if kw["dw_range"] is None else (float(kw["dw_range"][0]), float(kw["dw_range"][1]))
+        spec = _lib.SkySpec(int(kw["n_theta"]), int(kw["n_phi"]), int(kw["n_dw"]), _lib.THETA_AXIS[kw["theta_axis"]],
+                            int(kw["mode"]), lo, hi)
+        return spec, (2, int(kw["n_theta"]), int(kw["n_phi"]), int(kw["n_dw"])), kw
+
+    def event_rows(self, sample, weight5, back, forward, *, event_offset=0, saveMode=0, nbins=50, flux=None, sky=None,
+                   sky_hist=None, totals=None, rows=True, cyclotron=False, return_bins=False) -> dict:
+        """The npy rows of main_runner_tree for one chunk of events whose forests the caller grew, on the
+        current stream: sample (Engine.sample's dict), weight5 (Engine.event_weight's (5, n)), back and
+        forward (Engine.grow_trees' dicts of the backtrace and of the forward forest). One pass over the
+        forward nodes writes the rows of the final ones in node order (13 columns, 29 with saveMode > 0;
+        column 7 is the raw sln_prob, NOT yet divided by f_inx) and adds column 8 * column 7 to
+        flux (2 nbins; nbins = 0: none), to the sky map sky_hist (sky: a dict of n_theta, n_phi, n_dw,
+        theta_axis, dw_range, mode; None: no map) and to totals (6 float64: rows, photon rows,
+        Σ weight sln_prob of axions and of photons, Σ (attempts - 1), cyclotron mismatches). flux,
+        sky_hist and totals are ACCUMULATED into when given, else start at zero. rows=False only bins.
+        cyclotron: the final photon segments run again through art_propagate_cyclotron_device (one count
+        comes to the host for it), τ goes into column 14 and exp(-τ) into column 8; a re-run that does
+        not reproduce its node's end state is counted in totals[5]. return_bins: also each row's flat
+        sky bin (int32, -1 for not counted). Returns a dict: rows ((n_rows, ncols) or None), n_rows
+        (an int when rows or bins were asked for, which costs one synchronisation, else None), flux,
+        sky_hist, totals, chunk_totals (this call's part of totals), bins."""
+        n = sample["erg"].numel()
+        nn = int(forward["n_nodes"])
+        ncols = 29 if saveMode > 0 else 13
+        nbins = int(nbins)
+        if flux is None:
+            flux = torch.zeros(2 * nbins, dtype=F64, device=self.device)
+        spec = shape = None
+        if sky is not None:
+            spec, shape, _ = self._sky_spec(sky)
+            if sky_hist is None:
+                sky_hist = torch.zeros(*shape, dtype=F64, device=self.device)
+        if return_bins and spec is None:
+            raise ValueError("event_rows: return_bins needs a sky map")
+        part = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
+        out_rows = self.empty(max(nn, 1), ncols) if rows else None
+        bins = self.empty(max(nn, 1), dtype=torch.int32) if return_bins else None
+        ei = _lib.EventRowsIn(n, int(event_offset), sample["x"].data_ptr(), sample["k_init"].data_ptr(),
+                              sample["attempts"].data_ptr() if sample.get("attempts") is not None else None,
+                              weight5.data_ptr(), back["nodes"].data_ptr(), back["counts"].data_ptr(),
+                              forward["nodes"].data_ptr(), nn, forward["counts"].data_ptr(), forward["infos"].data_ptr(),
+                              None, 0, None, None)
+        keep = None
+        if cyclotron:
+            keep = self._cyclotron_rerun(sample, forward, nn, n)
+            ei.cyc_slot, ei.cyc_n, ei.cyc_tau = keep["slot"].data_ptr(), keep["m"], keep["tau"].data_ptr()
+            ei.cyc_end = C.pointer(keep["end"])
+        eo = _lib.EventRowsOut(ncols, nbins, _p(out_rows), nn if (rows or return_bins) else 0, _p(flux),
+                               C.pointer(spec) if spec is not None else None, _p(sky_hist), _p(bins), _p(part))
+        check(self.lib.art_event_rows_device(C.byref(self.cp), C.byref(ei), C.byref(eo), _stream()))
+        if totals is None:
+            totals = part
+        else:
+            totals += part
+        n_rows = None
+        if rows or return_bins:
+            n_rows = int(part[0].item())
+            out_rows = out_rows[:n_rows] if rows else None
+            bins = bins[:n_rows] if return_bins else None
+        return {"rows": out_rows, "n_rows": n_rows, "flux": flux, "sky_hist": sky_hist, "totals": totals,
+                "chunk_totals": part, "bins": bins}
+
+    def _cyclotron_rerun(self, sample, forward, nn, n):
+        """The final photon segments of a forward forest, packed (art_event_gather_photons_device) and run
+        again with the cyclotron observation: slot per node, the batch size m, its tau and end states."""
+        cap = max(nn, 1)
+        b = {"x0": self.empty(3 * cap), "k0": self.empty(3 * cap), "erg": self.empty(cap), "dw": self.empty(cap),
+             "ln_t0": self.empty(cap), "species": self.empty(cap, dtype=torch.int8)}
+        slot = self.empty(cap, dtype=torch.int32)
+        m = C.c_int64(0)
+        check(self.lib.art_event_gather_photons_device(C.byref(self.cp), n, _p(sample["erg"]), nn, _p(forward["nodes"]), cap,
+                                                       *[_p(b[k]) for k in ("x0", "k0", "erg", "dw", "ln_t0", "species")],
+                                                       _p(slot), C.byref(m), _stream()))
+        m = int(m.value)
+        if m == 0:
+            z = self.empty(1)
+            return {"slot": slot, "m": 0, "tau": z, "end": _lib.SegmentOut(), "out": None}
+        inp = {k: (v[:3 * m] if k in ("x0", "k0") else v[:m]) for k, v in b.items()}
+        out = self.propagate(inp, max_crossings=-1, capacity=1, cyclotron=True)
+        end = _lib.SegmentOut(*[out[k].data_ptr() for k in ("x_end", "k_end", "u7_end", "tau_end", "status", "n_accept",
+                                                           "n_reject")])
+        return {"slot": slot, "m": m, "tau": out["cyc_tau"], "end": end, "out": out, "inp": inp}
+
+    def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
+                   max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
+                   cyclotron=False, rows=True) -> dict:
+        """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
+        n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
+        event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
+        tree_offset = lo), the forward forest (tree_offset = lo) and event_rows (event_offset = lo); flux,
+        sky map and totals accumulate on the device and the rows are collected there. The sampler and the
+        Monte-Carlo draws are keyed by global ids, so the chunking does not change the rows (the weighted
+        tables differ by the order of their adds only). It blocks, because grow_trees does.
+
+        chunk: events per chunk (None: one chunk). A chunk of c events holds at most c (max_nodes + 2)
+        node records of 264 B for the forward forest (3.4 MB per 250 events at the defaults, 1.8 GB per
+        2^17; about 3.5 records per event are used on the flat configuration), the same again while the
+        driver's node log is flattened, c records for the backtrace forest with 9 backtrace_cap c doubles
+        of crossing slots, and, with rows, ncols doubles per record for the chunk's rows before they are
+        cut to the final nodes.
+
+        sky_map: a dict of n_theta, n_phi, n_dw, theta_axis, dw_range, mode ({}: the defaults), or None.
+        n_dw > 1 needs a dw_range: ValueError without one. rows=False: no rows, the large-run mode.
+
+        Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
+        or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
+        f_inx, sum_weight_sln_prob, n_rows, n_photon_rows, and the raw, undivided parts for a caller that
+        reduces over ranks first: totals (6: rows, photon rows, Σ weight sln_prob of axions and photons,
+        Σ (attempts - 1), cyclotron mismatches), flux_raw, sky_raw, rows_raw (column 7 undivided; the
+        tensor `rows` is a divided copy of)."""
+        from dataclasses import replace
+        from .trees import AXION, PHOTON, sky_map_edges
+        n_events = int(n_events)
+        if n_events < 0:
+            raise ValueError("run_events: n_events must be >= 0")
+        chunk = max(1, n_events) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError("run_events: chunk must be >= 1")
+        ncols = 29 if saveMode > 0 else 13
+        sky_hist = sky_kw = None
+        if sky_map is not None:
+            _, shape, sky_kw = self._sky_spec(sky_map)
+            sky_hist = torch.zeros(*shape, dtype=F64, device=self.device)
+        max_r = self.params.max_r()
+        if max_r < self.params.rNS:
+            raise ValueError("maxR < rNS: this neutron star has no conversion surface (MainRunner.jl:387-396)")
+        back_eng = Engine(replace(self.params, B0=-self.params.B0), device=self.device.index)
+        flux = torch.zeros(2 * int(nbins), dtype=F64, device=self.device)
+        totals = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
+        parts = []
+        for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
+            c = min(chunk, int(event_offset) + n_events - lo)
+            s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r)
+            w5 = self.event_weight(s, max_r=max_r, rho_DM=rho_DM, n_maxSample=n_maxSample)
+            back = back_eng.grow_trees(s["x"], -s["k_init"], s["erg"], AXION, num_cutoff=0, splittings_cutoff=100000,
+                                       crossing_cap=backtrace_cap, prob_cutoff=prob_cutoff, seed=seed, tree_offset=lo)
+            fwd = self.grow_trees(s["x"], s["k_init"], s["erg"], PHOTON, num_cutoff=num_cutoff, mc_nodes=MC_nodes,
+                                  max_nodes=max_nodes, prob_cutoff=prob_cutoff, seed=seed, tree_offset=lo)
+            r = self.event_rows(s, w5, back, fwd, event_offset=lo, saveMode=saveMode, nbins=nbins, flux=flux,
+                                sky=sky_map, sky_hist=sky_hist, totals=totals, rows=rows, cyclotron=cyclotron)
+            if rows:
+                parts.append(r["rows"] if len(r["rows"]) * 2 >= fwd["n_nodes"] else r["rows"].clone())
+        tot = totals.cpu().numpy()
+        if tot[5] != 0:
+            raise _lib.ArtError(f"run_events: {int(tot[5])} cyclotron re-runs of final photon segments do not "
+                                "reproduce their end states")
+        f_inx = int(round(tot[4] + tot[1]))
+        # (a device tensor, not a Python number: torch turns a division by a host scalar into a
+        # multiplication by its reciprocal, which rounds differently from the host's division)
+        div = torch.full((), float(f_inx) if f_inx > 0 else 1.0, dtype=F64, device=self.device)
+        rows_raw = rows_div = None
+        if rows:
+            rows_raw = torch.cat(parts, dim=0) if parts else torch.zeros(0, ncols, dtype=F64, device=self.device)
+            rows_div = rows_raw.clone()
+            rows_div[:, 7] /= div  # saveAll[:, 8] ./= f_inx (MainRunner.jl:747): one IEEE division
+        res = {"rows": rows_div, "flux": (flux / div).view(2, int(nbins)), "f_inx": f_inx,
+               "sum_weight_sln_prob": (float(tot[2]) / max(f_inx, 1), float(tot[3]) / max(f_inx, 1)),
+               "n_rows": int(round(tot[0])),
+               "n_photon_rows": int(round(tot[1])), "totals": totals, "flux_raw": flux, "rows_raw": rows_raw}
+        if sky_map is not None:
+            ekw = {k: sky_kw[k] for k in ("n_theta", "n_phi", "n_dw", "theta_axis", "dw_range")}
+            res.update(sky_map=sky_hist / div, sky_raw=sky_hist, sky_map_edges=sky_map_edges(**ekw))
+        return res
+
     # ---- pointwise physics (parity tests)
     def eval_rhs(self, u, tau, erg, species):
         n = tau.numel()

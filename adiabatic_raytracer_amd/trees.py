@@ -179,7 +179,7 @@ def save_node(fh, node, tr, q):
 def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_DM=0.45, n_maxSample=6,
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
-                     sky_map=None, device_trees=False):
+                     sky_map=None, device_trees=False, device_events=False):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -221,7 +221,23 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     device_trees: grow the backtrace and the forward forest with every tree's state in HBM
     (grow_trees(..., device=True), art_grow_trees_device) instead of the host forest. Tree dumps
     (saveMode > 2 with a dir_tag) need trajectories, which that driver does not save: ValueError.
-    With the default False every row, file and run_info key is unchanged."""
+    With the default False every row, file and run_info key is unchanged.
+
+    device_events: the rank's block of events runs through Engine.run_events: sampler, weights, both
+    forests, the rows, the flux and the sky map stay in HBM (art_event_rows_device), the rows come to the
+    host once, for the npy file and the return value, and the raw flux, sky map and totals feed the same
+    all-reduce. The event_/final_ text files of saveMode > 1 need per-node data on the host: with a
+    dir_tag that is a ValueError. A sky map with n_dw > 1 needs a dw_range. With the default False every
+    row, file and run_info key is unchanged."""
+    if device_events:
+        if saveMode > 1 and dir_tag is not None:
+            raise ValueError("device_events: the text files and tree dumps of saveMode > 1 with a dir_tag need the "
+                             "nodes on the host")
+        return _main_runner_tree_device(params, Ntajs, seed=seed, rho_DM=rho_DM, n_maxSample=n_maxSample,
+                                        num_cutoff=num_cutoff, MC_nodes=MC_nodes, max_nodes=max_nodes,
+                                        prob_cutoff=prob_cutoff, saveMode=saveMode, dir_tag=dir_tag, file_tag=file_tag,
+                                        backtrace_cap=backtrace_cap, rank=rank, world=world, nbins=nbins, run_info=run_info,
+                                        cyclotron=cyclotron, sky_map=sky_map)
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -331,6 +347,59 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
         os.makedirs(os.path.dirname(path), exist_ok=True)
         np.save(path, rows)
         if sky_map is not None:
+            te, pe, de = sky_map_edges(**sky_kw)
+            stem = os.path.splitext(os.path.basename(path))[0]
+            np.savez(os.path.join(os.path.dirname(path), f"skymap_{stem}.npz"), sky_map=tt["sky"] / f_glob,
+                     theta_edges=te, phi_edges=pe, dw_edges=de, theta_axis=sky_kw["theta_axis"], f_inx=int(round(f_glob)))
+    return rows
+
+
+def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
+                             saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map):
+    """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
+    totals vector, all-reduce, division, run_info and files as the host assembly."""
+    from .engine import Engine
+    from .shard import allreduce_sum, shard_range
+    sky_kw = None
+    if sky_map is not None:
+        sky_kw = {"n_theta": 32, "n_phi": 64, "n_dw": 1, "theta_axis": "cos", "dw_range": None}
+        if set(sky_map) - set(sky_kw):
+            raise ValueError(f"sky_map: unknown keys {sorted(set(sky_map) - set(sky_kw))}")
+        sky_kw.update(sky_map)
+        _theta_range(sky_kw["theta_axis"])
+        if sky_kw["n_dw"] > 1 and sky_kw["dw_range"] is None:
+            raise ValueError("sky_map: device_events bins on the device as it goes: n_dw > 1 needs a dw_range")
+    ntimes = 3 if saveMode < 3 else 1000  # names the npy file only (main_runner_tree's default beyond saveMode 2)
+    n_glob = max(0, int(Ntajs) - 1)
+    lo, hi = shard_range(n_glob, rank, world)
+    tag = f"{file_tag}{rank}" if world > 1 else file_tag
+    r = Engine(params).run_events(hi - lo, seed=seed, event_offset=lo, saveMode=saveMode, num_cutoff=num_cutoff,
+                                  MC_nodes=MC_nodes, max_nodes=max_nodes, prob_cutoff=prob_cutoff,
+                                  backtrace_cap=backtrace_cap, rho_DM=rho_DM, n_maxSample=n_maxSample, nbins=nbins,
+                                  sky_map=sky_kw, cyclotron=cyclotron, rows=True)
+    rows = r["rows_raw"].cpu().numpy()
+    t6 = r["totals"].cpu().numpy()
+    sky_shape = None if sky_kw is None else (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
+    tot = pack_totals(r["flux_raw"].cpu().numpy(), t6[4] + t6[1], t6[2], t6[3], t6[0],
+                      None if sky_kw is None else r["sky_raw"].cpu().numpy())
+    if world > 1:
+        tot = allreduce_sum(tot)
+    tt = unpack_totals(tot, nbins, sky_shape)
+    f_glob = tt["f_inx"]
+    if len(rows):
+        rows[:, 7] /= f_glob  # saveAll[:, 8] ./= f_inx (:747), the whole run's f_inx
+    if run_info is not None:
+        run_info.update(f_inx=int(round(f_glob)), flux=(tt["flux"] / f_glob).reshape(2, nbins),
+                        sum_weight_sln_prob=(tt["sum_axion"] / f_glob, tt["sum_photon"] / f_glob),
+                        rows=int(round(tt["rows"])), events=(lo, hi), n_events=n_glob)
+        if sky_kw is not None:
+            run_info.update(sky_map=tt["sky"] / f_glob, sky_map_edges=sky_map_edges(**sky_kw))
+    if dir_tag is not None:
+        path = tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul, params.B0, Ntajs,
+                              ntimes, num_cutoff, MC_nodes, max_nodes, tag)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        np.save(path, rows)
+        if sky_kw is not None:
             te, pe, de = sky_map_edges(**sky_kw)
             stem = os.path.splitext(os.path.basename(path))[0]
             np.savez(os.path.join(os.path.dirname(path), f"skymap_{stem}.npz"), sky_map=tt["sky"] / f_glob,

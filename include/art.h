@@ -512,6 +512,80 @@ int art_sky_map_segments_device(const art_params* p, const art_sky_spec* spec, i
                                 const int32_t* status, const int8_t* species, const double* w,
                                 const double* dw_offset, double* hist, int32_t* bin_out, void* stream);
 
+/* ---- event rows: main_runner_tree's npy rows, flux and sky map from forests held in HBM ----
+ * One pass over the forward forest's node records (art_grow_trees_device's layout) selects the
+ * final nodes (is_final != 0), writes each one's row (MainRunner.jl:690-747, 715-761) in node
+ * order -- row r is the r-th final node -- and, while the row is in registers, adds
+ * column 8 * column 7 (weight * sln_prob) to the azimuth flux table and to the sky map and sums
+ * the run's totals. Columns, 0-based: 0 event_offset + node.tree + 1; 1 species (0 axion,
+ * 1 photon); 2, 3 θf, φf of k_end; 4-6 θ, φ, |.| of x_end; 7 sln_prob, raw (the division by the
+ * run's f_inx comes later); 8 node.weight * (back.prob * back.weight) [* exp(-τ)]; 9-11 the sampled
+ * x; 12 u7_end / mass_a + vel_eng; and with ncols = 29: 13 column 8 without exp(-τ); 14 τ; 15 1;
+ * 16-18 k_init; 19 cos_w; 20, 21 the forward tree's count and info; 22-24 prob, prob_conv,
+ * prob_conv0; 25 back.prob * back.weight; 26 column 6; 27 the backtrace tree's count; 28 back.prob.
+ * Every operation is rounded on its own, as numpy rounds them: |v| = sqrt((x² + y²) + z²),
+ * θ = acos(z / |v|), φ = atan2(y, x).
+ * All array pointers are device pointers; the structs and p are host memory. */
+typedef struct art_event_rows_in {
+  int64_t n_events;            /* events (trees) of this chunk                                        */
+  int64_t event_offset;        /* global id of the chunk's event 0 (column 0)                         */
+  const double* x;             /* 3n  the sampler's x (SoA)                                           */
+  const double* k_init;        /* 3n  the sampler's k_init                                            */
+  const int32_t* attempts;     /* n   the sampler's attempts; may be NULL (totals[4] stays)           */
+  const double* weight5;       /* 5n  the output of art_event_weight_device                           */
+  const art_tree_node* back;   /* n   the backtrace forest's nodes, one per event                     */
+  const int32_t* back_counts;  /* n   its counts (column 27)                                          */
+  const art_tree_node* nodes;  /* n_nodes  the forward forest's nodes                                 */
+  int64_t n_nodes;             /* < 2^31                                                              */
+  const int32_t* counts;       /* n   the forward forest's counts (column 20)                         */
+  const int32_t* infos;        /* n   its infos (column 21)                                           */
+  /* cyclotron (all NULL / 0 without): the re-run of the final photon segments that
+   * art_event_gather_photons_device packed and art_propagate_cyclotron_device ran */
+  const int32_t* cyc_slot;     /* n_nodes  each node's segment in that batch, -1 for none             */
+  int64_t cyc_n;               /* segments in the batch                                               */
+  const double* cyc_tau;       /* cyc_n  art_cyclotron_out::tau: column 14, and exp(-τ) into column 8 */
+  const art_segment_out* cyc_end; /* the batch's end states (x_end, k_end, u7_end, tau_end, status),  */
+                               /* compared with the nodes' bitwise, NaN equal to NaN: totals[5]       */
+} art_event_rows_in;
+/* Every table is ACCUMULATED into (zero it first); ordinary device memory.
+ * totals (6 float64; counts are exact below 2^53): [0] rows, [1] photon rows, [2] Σ column 8 *
+ * column 7 of the axion rows, [3] of the photon rows, [4] Σ (attempts - 1) over the events,
+ * [5] cyclotron re-runs that did not reproduce their node's end state (must stay 0). */
+typedef struct art_event_rows_out {
+  int32_t ncols;               /* 13 or 29                                                            */
+  int32_t nbins;               /* bins of the azimuth flux over [-π, π], 0 .. 4096 (0: no flux)       */
+  double* rows;                /* row_capacity * ncols, row-major; NULL: bin only (large runs)        */
+  int64_t row_capacity;        /* rows that `rows` and `bin_out` hold: >= n_nodes when either is given */
+  double* flux;                /* 2 * nbins: axions, photons (np.histogram's bins, np_hist_bin)       */
+  const art_sky_spec* sky;     /* NULL: no sky map. θ axis from kz / |k| or column 2, φf = column 3,  */
+  double* sky_hist;            /*   Δω = column 12; the table of art_sky_map_segments_device          */
+  int32_t* bin_out;            /* may be NULL: each row's flat sky bin, -1 for not counted            */
+  double* totals;              /* 6                                                                   */
+} art_event_rows_out;
+/* Asynchronous on `stream` like the other *_device calls; its scratch (one int32 per node and the
+ * scan's) comes from the stream-ordered allocator. The flux table is block-private in LDS; the sky
+ * table too when 2 n_theta n_phi n_dw + 2 nbins <= 8192 doubles (mode 0) and otherwise added to in
+ * device memory, as art_sky_map_segments_device chooses. ART_E_INVALID before any device is touched:
+ * a NULL p, in or out; n_events < 0; n_nodes < 0 or >= 2^31; ncols not 13 or 29; rows or bin_out
+ * given with row_capacity < n_nodes; nbins < 0 or > 4096; a bad sky spec by
+ * art_sky_map_segments_device's rules (mode 1: the two tables together exceed the LDS budget);
+ * a NULL buffer that the call needs. */
+int art_event_rows_device(const art_params* p, const art_event_rows_in* in, const art_event_rows_out* out,
+                          void* stream);
+/* The cyclotron re-run's inputs, a second small entry point (art_event_rows_device itself stays
+ * asynchronous): packs the final photon nodes of `nodes` in node order into a segment batch --
+ * x0, k0 (3m SoA, stride m), erg = erg[node.tree], dw = dw0, ln_t0 = log(max(t0, e^-30)) by the
+ * function and constants art_grow_trees_device packed its rounds with, species = photon -- so
+ * art_propagate_cyclotron_device(max_crossings = -1) starts from the forest's own inputs bit for
+ * bit. slot (n_nodes): each node's segment, -1 for none. It BLOCKS, because it reads one count on
+ * the host, m = *n_out, the stride of the batch and the n the propagate call takes by value. The
+ * batch buffers hold `capacity` segments (3 capacity for x0 and k0); n_nodes always suffices, a
+ * smaller capacity than m is ART_E_NOMEM with m in *n_out and nothing packed. erg: n_events. */
+int art_event_gather_photons_device(const art_params* p, int64_t n_events, const double* erg, int64_t n_nodes,
+                                    const art_tree_node* nodes, int64_t capacity, double* x0, double* k0,
+                                    double* erg_out, double* dw, double* ln_t0, int8_t* species, int32_t* slot,
+                                    int64_t* n_out, void* stream);
+
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the
  * other ranks (a file, MPI, the launcher); every rank then calls art_comm_init on its device.

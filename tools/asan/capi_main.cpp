@@ -98,6 +98,29 @@ int main() {
     sk.theta_axis = 0; sk.n_dw = 4;  // n_dw > 1 needs a range
     CHECK(art_sky_map_segments_device(&p, &sk, n, d, d, d, st.data(), nullptr, nullptr, nullptr, d, nullptr, nullptr) ==
           ART_E_INVALID);
+    // event rows: the struct checks, the sky spec's and the shared LDS budget, all before the device
+    art_event_rows_in ei{};
+    art_event_rows_out eo{};
+    ei.n_events = ei.n_nodes = 4;
+    eo.ncols = 13; eo.nbins = 50; eo.row_capacity = 4; eo.rows = d;
+    CHECK(art_event_rows_device(&p, nullptr, &eo, nullptr) == ART_E_INVALID);
+    CHECK(art_event_rows_device(&p, &ei, nullptr, nullptr) == ART_E_INVALID);
+    eo.sky = &sk;  // still n_dw = 4 without a range
+    CHECK(art_event_rows_device(&p, &ei, &eo, nullptr) == ART_E_INVALID);
+    art_sky_spec full{16, 32, 8, 1, 1, 0.0, 1.0};  // 8192 doubles: fits alone, not beside the flux table
+    eo.sky = &full;
+    CHECK(art_event_rows_device(&p, &ei, &eo, nullptr) == ART_E_INVALID);
+    eo.sky = nullptr; eo.ncols = 14;
+    CHECK(art_event_rows_device(&p, &ei, &eo, nullptr) == ART_E_INVALID);
+    eo.ncols = 29; eo.row_capacity = 3;
+    CHECK(art_event_rows_device(&p, &ei, &eo, nullptr) == ART_E_INVALID);
+    ei.n_events = ei.n_nodes = 0;
+    CHECK(art_event_rows_device(&p, &ei, &eo, nullptr) == ART_OK);
+    int64_t m = -1;
+    CHECK(art_event_gather_photons_device(&p, 4, d, -1, nullptr, 4, d, d, d, d, d, nullptr, nullptr, &m, nullptr) ==
+          ART_E_INVALID);
+    CHECK(art_event_gather_photons_device(&p, 4, d, 0, nullptr, 4, d, d, d, d, d, nullptr, nullptr, &m, nullptr) == ART_OK &&
+          m == 0);
   }
   // the device forest: every argument check comes before the device; with roots it reaches the HIP runtime
   {

@@ -66,6 +66,15 @@ hipError_t launch_tree_finish(const TreeRules&, int64_t, const TreeState*, int32
 hipError_t launch_tree_flatten(int64_t, const art_tree_node*, const int64_t*, int64_t, art_tree_node*, hipStream_t) {
   return hipErrorNoDevice;
 }
+size_t event_scan_bytes(int64_t) { return 0; }
+hipError_t launch_event_scan(int64_t, const art_tree_node*, bool, int32_t*, void*, size_t, hipStream_t) {
+  return hipErrorNoDevice;
+}
+hipError_t launch_event_gather(int64_t, const art_tree_node*, const int32_t*, int64_t, const double*, int64_t,
+                               const TreeBatch&, int32_t*, double, double, hipStream_t) {
+  return hipErrorNoDevice;
+}
+hipError_t launch_event_rows(const EventRowsArgs&, const SkyAxes&, int, int, hipStream_t) { return hipErrorNoDevice; }
 MFn nl_eval_math(int) { return nullptr; }
 hipError_t launch_eval_math(int, int, int64_t, const double*, const double*, double*, double*, hipStream_t) {
   return hipErrorNoDevice;

@@ -6,12 +6,15 @@ Each event is one sampled conversion point (find_samples_new). It then gets its 
 tree (axion, -B0, every crossing) and its forward photon tree. The defaults are
 num_cutoff = MC_nodes = 5 and max_nodes = 50.
 
-usage: [ART_DONATE=lanes] [ART_DEVICE_TREES=0|1|ab] exp_events.py [flat|gr] [gpu event counts, comma-separated]
-       [cpu events] [repeats]
+usage: [ART_DONATE=lanes] [ART_DEVICE_TREES=0|1|ab|events|events-ab] [ART_EVENTS_BIG=n,chunk] exp_events.py [flat|gr]
+       [gpu event counts, comma-separated] [cpu events] [repeats]
 ART_DEVICE_TREES: 0 (the default) grows the trees with the host forest (art_grow_trees), 1 with the
 device-resident driver (main_runner_tree(device_trees=True), art_grow_trees_device), ab runs both,
-alternating, `repeats` times (default 1) for each event count. Prints one JSON line per run; its
-"trees" key says which forest ran. After each event count's runs one more line ("forest shape",
+alternating, `repeats` times (default 1) for each event count. events runs
+main_runner_tree(device_events=True) (Engine.run_events: rows, flux and sky map built in HBM),
+events-ab alternates device trees and device events. ART_EVENTS_BIG=n,chunk adds one
+Engine.run_events(n, chunk=chunk, rows=False) run with the default sky map after the counts (untimed
+warm-up of one chunk first). Prints one JSON line per run; its "trees" key says which variant ran. After each event count's runs one more line ("forest shape",
 untimed) gives the forward forest's rounds -- its batched propagate launches -- and the sum of their
 batch sizes, from the trees' counts."""
 import json
@@ -33,25 +36,49 @@ DONATE = int(os.environ.get("ART_DONATE", "-1"))  # tail donation of the forest'
 if DONATE >= 0:
     import ctypes as C
     A._lib.load().art_set_tail_donation(C.c_int32(DONATE))
-SIDES = {"0": [False], "1": [True], "ab": [False, True]}[os.environ.get("ART_DEVICE_TREES", "0")]
+SIDES = {"0": [False], "1": [True], "ab": [False, True], "events": ["events"],
+         "events-ab": [True, "events"]}[os.environ.get("ART_DEVICE_TREES", "0")]
+NAME = {False: "host", True: "device", "events": "device events"}
+
+
+def run(n, dev, **kw):
+    if dev == "events":
+        return trees.main_runner_tree(p, n + 1, device_events=True, **kw)
+    return trees.main_runner_tree(p, n + 1, device_trees=dev, **kw)
+
 
 for dev in SIDES:
-    trees.main_runner_tree(p, 65, device_trees=dev)  # warm-up: library load, kernels, pools
+    run(64, dev)  # warm-up: library load, kernels, pools
 for n in counts:
     for _ in range(repeats):
         for dev in SIDES:
             info = {}
             t0 = time.perf_counter()
-            rows = trees.main_runner_tree(p, n + 1, run_info=info, device_trees=dev)
+            rows = run(n, dev, run_info=info)
             dt = time.perf_counter() - t0
-            print(json.dumps({"config": cfg, "side": "gpu", "trees": "device" if dev else "host", "donate": DONATE,
+            print(json.dumps({"config": cfg, "side": "gpu", "trees": NAME[dev], "donate": DONATE,
                               "events": n, "wall_s": dt, "events_per_s": n / dt, "rows": int(rows.shape[0]),
                               "f_inx": info["f_inx"]}), flush=True)
     # the forward forest's shape (untimed): a tree takes part in `count` rounds, one segment in each
     s = A.sample_conversion_points(p, n, seed=1769)
-    _, cnt, _ = trees.grow_trees(p, s["x"], s["k_init"], s["erg"], 1, device=SIDES[-1])
+    _, cnt, _ = trees.grow_trees(p, s["x"], s["k_init"], s["erg"], 1, device=bool(SIDES[-1]))
     print(json.dumps({"config": cfg, "side": "forest shape", "trees": "device" if SIDES[-1] else "host", "events": n,
                       "rounds": int(cnt.max()) if n else 0, "batch_sum": int(cnt.sum())}), flush=True)
+
+if os.environ.get("ART_EVENTS_BIG"):
+    import torch
+    n_big, chunk = (int(v) for v in os.environ["ART_EVENTS_BIG"].split(","))
+    eng = A.Engine(p)
+    eng.run_events(min(chunk, n_big), rows=False, sky_map={})
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    t0 = time.perf_counter()
+    r = eng.run_events(n_big, chunk=chunk, rows=False, sky_map={})
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print(json.dumps({"config": cfg, "side": "gpu", "trees": "device events, chunked, rows=False, sky map 32x64x1",
+                      "events": n_big, "chunk": chunk, "wall_s": dt, "events_per_s": n_big / dt, "rows": r["n_rows"],
+                      "f_inx": r["f_inx"], "torch_peak_bytes": int(torch.cuda.max_memory_allocated())}), flush=True)
 
 if n_cpu > 0:
     import oracle as O
