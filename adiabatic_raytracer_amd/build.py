@@ -8,7 +8,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libart.so")
-SOURCES = ["art_kernels.hip", "art_capi.cpp", "art_forest.cpp", "art_kernels_nolicm.hip"]
+# the two kernel units, the host units of the C boundary (art_host.h says which holds what) and the tree driver
+SOURCES = ["art_kernels.hip", "art_context.cpp", "art_device.cpp", "art_host_stream.cpp", "art_host_paths.cpp",
+           "art_post.cpp", "art_rccl.cpp", "art_forest.cpp", "art_kernels_nolicm.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))  # every header: a new one cannot be forgotten
 ARCH = os.environ.get("ART_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=on: FMA fusion within one source expression only ("FMA contraction").

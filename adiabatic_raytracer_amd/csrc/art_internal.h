@@ -1,5 +1,5 @@
 // art_internal.h -- the launch wrappers and record layouts shared by the two kernel translation
-// units (art_kernels.hip, art_kernels_nolicm.hip), their headers and art_capi.cpp.
+// units (art_kernels.hip, art_kernels_nolicm.hip), their headers and the host units (art_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -69,7 +69,7 @@ struct SegOut {
   unsigned long long* queue_word;
   unsigned long long wait_ticks;  // a wave's bound on a chunk flag (STREAM_WAIT_TICKS; tests set less)
   Pieces pieces;
-  // The maskless streamed pipeline (DON = 3, art_capi.cpp propagate_host_maskless): one launch
+  // The maskless streamed pipeline (DON = 3, art_host_stream.cpp StreamCall): one launch
   // over the whole batch holds every CU; its first `helpers` blocks are helpers, not
   // integrators. *host_ready (host memory, raised by the host as each piece's copies land)
   // counts rays whose inputs are in HBM. Helpers claim 1024-ray tiles (HELPER_TILE) to initialise
@@ -89,7 +89,7 @@ struct SegOut {
   char* blob;
   int32_t blob_host;  // 1: the blobs are pinned host memory the helpers write over PCIe (no download copies)
   int32_t helpers;
-  // The end of a streamed call without the integrator's stream (art_capi.cpp, HostLane): the
+  // The end of a streamed call without the integrator's stream (art_host.h, HostLane): the
   // helpers bin the radiated flux of the rays they finalize (flux_hist, 2 flux_nbins doubles of
   // device memory, flux_nbins <= FLUX_HELPER_BINS; 0 = none), every integrator wave counts itself
   // into *waves_started as it starts and into *waves_done after its statistics, and the last of the
@@ -109,7 +109,7 @@ struct SegOut {
   unsigned long long* resident_host;
   unsigned long long resident_value;
   int32_t waves_total;
-  // Small batches (art_capi.cpp, propagate_device_impl): 1 = every fresh ray goes straight to
+  // Small batches (art_device.cpp, propagate_device_impl): 1 = every fresh ray goes straight to
   // tail_kernel, one wave per ray (pack_fresh_kernel writes their CONT_REC records to cont),
   // instead of one lane per ray of the persistent integrator
   int32_t small_tail;
@@ -121,7 +121,7 @@ struct SegOut {
   double* grad;
   unsigned long long *grad_count, *grad_queue;
   int32_t grad_cap, graduate;
-  // Early graduation (DON = 1 launches with tail_kernel, art_capi.cpp): a ray whose progress
+  // Early graduation (DON = 1 launches with tail_kernel, art_device.cpp): a ray whose progress
   // in ln t since its start is below hot_dtau + hot_slope log2(attempts / 256) -- tested at every
   // power-of-two attempt count >= hot_at, and when its drained wave donates it -- leaves for
   // hot[0, hot_cap) at once: the count in *hot_count (it may pass hot_cap: a ray that finds no

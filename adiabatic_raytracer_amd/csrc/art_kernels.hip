@@ -756,7 +756,7 @@ hipError_t launch_eval_math(int fn, int tu, int64_t n, const double* a, const do
 }
 
 // ---------------------------------------------------------------------------
-// The device-resident tree driver (art_grow_trees_device, art_capi.cpp): every tree's state and
+// The device-resident tree driver (art_grow_trees_device, art_device.cpp): every tree's state and
 // event stack stay in HBM (art_tree_step.h); a round is pack -> one batched propagate -> step ->
 // an inclusive scan of the trees that go on, whose last value -- the next round's batch size -- is
 // the only thing the host reads. Ordering comes from the stream alone.

@@ -1,5 +1,5 @@
 // art_pieces.h -- the streamed host pipeline's partition of a batch into output pieces, for the host
-// (art_capi.cpp), the helpers (art_helper.h, art_ray_io.h) and the integrator (art_propagate.h):
+// (art_host_stream.cpp), the helpers (art_helper.h, art_ray_io.h) and the integrator (art_propagate.h):
 // one definition, so the ray -> piece map, the pieces' bounds and their blobs' offsets cannot
 // disagree between them. Plain C++ (no HIP): tools/piececheck.cpp compiles it with the host compiler.
 //

@@ -1,0 +1,484 @@
+// art_post.cpp -- the entry points around the propagate calls (declared in include/art.h): the
+// non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows and
+// the eval entry points the tests compare against the oracle. Each checks its arguments, then
+// launches on the caller's stream (or stages through the context's pool, the *_host ones).
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <string>
+
+#include "art_event_rows.h"
+#include "art_host.h"
+
+namespace art {
+namespace host {
+
+static int sample_device_impl(const art_params* p, double max_r, uint64_t seed, int64_t ray_offset, int64_t n, double* x,
+                       double* k_init, double* erg_inf, double* vifty, int32_t* weights, int32_t* attempts,
+                       hipStream_t s) {
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
+  if (!(max_r > p->rNS)) return fail(ART_E_INVALID, "max_r must exceed rNS (MainRunner.jl:389-396 quits otherwise)");
+  if (!x || !k_init || !erg_inf || !vifty || !weights || !attempts) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  void* q = nullptr;  // this launch's work-queue word
+  if ((rc = scratch_alloc(s, 256, &q))) return rc;
+  HIP_OK(hipMemsetAsync(q, 0, sizeof(unsigned long long), s));
+  HIP_OK(hipMemsetAsync(q, 0, 256, s));
+  HIP_OK(art::launch_sample(kparams(*p), max_r, seed, ray_offset, n, x, k_init, erg_inf, vifty, weights,
+                            attempts, (unsigned long long*)q, s, c->sampler_waves));
+#ifdef ART_SAMPLER_SECTIONS  // (dev build: the sampler's section cycles to stderr)
+  {
+    unsigned long long w[16];
+    HIP_OK(hipMemcpyAsync(w, q, sizeof w, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    std::fprintf(stderr, "[sampler-sections] n=%lld setup %llu control %llu cert %llu grid %llu brackets %llu out %llu "
+                 "grid_steps %llu steps %llu\n", (long long)n, w[8], w[9], w[10], w[11], w[12], w[13], w[14], w[15]);
+  }
+#endif
+  HIP_OK(hipFreeAsync(q, s));
+  return ART_OK;
+}
+
+static int event_weight_device_impl(const art_params* p, double max_r, double rho_dm, double mcmc_weight, int64_t n,
+                             const double* x, const double* k_init, const double* vifty, double* out, hipStream_t s) {
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
+  if (!x || !k_init || !vifty || !out) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  HIP_OK(art::launch_event_weight(art::make_kparams(*p), n, x, k_init, vifty, max_r, rho_dm, mcmc_weight, out, s));
+  return ART_OK;
+}
+
+}  // namespace host
+}  // namespace art
+
+using namespace art::host;
+
+extern "C" {
+
+int art_get_prob_nonad_device(const art_params* p, int64_t nc, const double* pos, const double* kpos,
+                              const double* erg_eff, int64_t n_groups, const int64_t* group_start, double* out,
+                              void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (nc == 0) return ART_OK;
+  if (nc < 0 || nc > 2147483647LL) return fail(ART_E_INVALID, "nc must be in [0, 2^31)");
+  if (!pos || !kpos || !erg_eff || !out) return fail(ART_E_INVALID, "NULL buffer");
+  if (!group_start) n_groups = nc;
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  HIP_OK(art::launch_prob(art::make_kparams(*p), nc, pos, kpos, erg_eff, n_groups, group_start, out, (hipStream_t)stream));
+  return ART_OK;
+}
+
+int art_get_prob_nonad_host(const art_params* p, int64_t nc, const double* pos, const double* kpos,
+                            const double* erg_eff, int64_t n_groups, const int64_t* group_start, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (nc == 0) return ART_OK;
+  if (nc < 0 || nc > 2147483647LL) return fail(ART_E_INVALID, "nc must be in [0, 2^31)");
+  if (!pos || !kpos || !erg_eff || !out) return fail(ART_E_INVALID, "NULL buffer");
+  if (!group_start) n_groups = nc;
+  if (group_start) {  // groups must tile [0, nc)
+    if (n_groups < 1) return fail(ART_E_INVALID, "n_groups must be >= 1");
+    if (group_start[0] != 0 || group_start[n_groups] != nc) return fail(ART_E_INVALID, "group_start must span [0, nc]");
+    for (int64_t g = 0; g < n_groups; ++g)
+      if (group_start[g + 1] <= group_start[g]) return fail(ART_E_INVALID, "empty or unsorted group");
+  }
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  void* d;
+  const size_t nd = (size_t)nc;
+  const size_t bytes = nd * 8 * sizeof(double) + (size_t)(n_groups + 1) * sizeof(int64_t);
+  if ((rc = pool_get(c, 3, bytes, &d))) return rc;
+  double* dd = (double*)d;
+  int64_t* dg = group_start ? (int64_t*)(dd + 8 * nd) : nullptr;
+  hipStream_t s = c->stream;
+  HIP_OK(hipMemcpyAsync(dd, pos, nd * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(dd + 3 * nd, kpos, nd * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(dd + 6 * nd, erg_eff, nd * sizeof(double), hipMemcpyHostToDevice, s));
+  if (dg) HIP_OK(hipMemcpyAsync(dg, group_start, (size_t)(n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  HIP_OK(art::launch_prob(art::make_kparams(*p), nc, dd, dd + 3 * nd, dd + 6 * nd, n_groups, dg, dd + 7 * nd, s));
+  HIP_OK(hipMemcpyAsync(out, dd + 7 * nd, nd * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return ART_OK;
+}
+
+int art_sample_conversion_points_device(const art_params* p, double max_r, uint64_t seed, int64_t ray_offset,
+                                        int64_t n, double* x, double* k_init, double* erg_inf, double* vifty,
+                                        int32_t* weights, int32_t* attempts, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return sample_device_impl(p, max_r, seed, ray_offset, n, x, k_init, erg_inf, vifty, weights, attempts,
+                            (hipStream_t)stream);
+}
+
+// The whole stage-run-copy sequence holds the mutex, so no other thread can regrow the staging
+// buffer in between.
+int art_sample_conversion_points_host(const art_params* p, double max_r, uint64_t seed, int64_t ray_offset, int64_t n,
+                                      double* x, double* k_init, double* erg_inf, double* vifty, int32_t* weights,
+                                      int32_t* attempts) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
+  if (!(max_r > p->rNS)) return fail(ART_E_INVALID, "max_r must exceed rNS (MainRunner.jl:389-396 quits otherwise)");
+  if (!x || !k_init || !erg_inf || !vifty || !weights || !attempts) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  void* d;
+  const size_t nd = (size_t)n;
+  if ((rc = pool_get(c, 4, nd * 10 * sizeof(double) + nd * 2 * sizeof(int32_t), &d))) return rc;
+  double* dd = (double*)d;
+  int32_t* di = (int32_t*)(dd + 10 * nd);
+  hipStream_t s = c->stream;
+  if ((rc = sample_device_impl(p, max_r, seed, ray_offset, n, dd, dd + 3 * nd, dd + 6 * nd, dd + 7 * nd, di, di + nd,
+                               s)))
+    return rc;
+  HIP_OK(hipMemcpyAsync(x, dd, nd * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(k_init, dd + 3 * nd, nd * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(erg_inf, dd + 6 * nd, nd * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(vifty, dd + 7 * nd, nd * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(weights, di, nd * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(attempts, di + nd, nd * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return ART_OK;
+}
+
+int art_event_weight_device(const art_params* p, double max_r, double rho_dm, double mcmc_weight, int64_t n,
+                            const double* x, const double* k_init, const double* vifty, double* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return event_weight_device_impl(p, max_r, rho_dm, mcmc_weight, n, x, k_init, vifty, out, (hipStream_t)stream);
+}
+
+int art_event_weight_host(const art_params* p, double max_r, double rho_dm, double mcmc_weight, int64_t n,
+                          const double* x, const double* k_init, const double* vifty, double* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
+  if (!x || !k_init || !vifty || !out) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  void* d;
+  const size_t nd = (size_t)n;
+  if ((rc = pool_get(c, 5, nd * 14 * sizeof(double), &d))) return rc;
+  double* dd = (double*)d;
+  hipStream_t s = c->stream;
+  HIP_OK(hipMemcpyAsync(dd, x, nd * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(dd + 3 * nd, k_init, nd * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_OK(hipMemcpyAsync(dd + 6 * nd, vifty, nd * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+  if ((rc = event_weight_device_impl(p, max_r, rho_dm, mcmc_weight, n, dd, dd + 3 * nd, dd + 6 * nd, dd + 9 * nd, s)))
+    return rc;
+  HIP_OK(hipMemcpyAsync(out, dd + 9 * nd, nd * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return ART_OK;
+}
+
+int art_flux_histogram_device(const art_params* p, int64_t n, const double* x_end, const double* k_end,
+                              const int32_t* status, const int8_t* species, const double* w, int32_t nbins,
+                              double* hist, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (nbins < 1 || nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [1, 4096]");
+  if (n == 0) return ART_OK;
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  HIP_OK(art::launch_flux(art::make_kparams(*p), n, x_end, k_end, status, species, w, nbins, hist, (hipStream_t)stream));
+  return ART_OK;
+}
+
+int art_flux_histogram_phi_device(int64_t n, const double* phi, const int8_t* species, const double* w, int32_t nbins,
+                                  double* hist, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (nbins < 1 || nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [1, 4096]");
+  if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
+  if (n == 0) return ART_OK;
+  if (!phi || !hist) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* c;
+  int rc = current_ctx(&c);
+  if (rc) return rc;
+  HIP_OK(art::launch_flux_phi(n, phi, species, w, nbins, -art::PI, art::PI, hist, (hipStream_t)stream));
+  return ART_OK;
+}
+
+int art_flux_histogram_phi_range_device(int64_t n, const double* phi, const int8_t* species, const double* w,
+                                        int32_t nbins, double lo, double hi, double* hist, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (nbins < 1 || nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [1, 4096]");
+  if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
+  if (!(lo < hi) || !std::isfinite(lo) || !std::isfinite(hi)) return fail(ART_E_INVALID, "need finite lo < hi");
+  if (n == 0) return ART_OK;
+  if (!phi || !hist) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* c;
+  int rc = current_ctx(&c);
+  if (rc) return rc;
+  HIP_OK(art::launch_flux_phi(n, phi, species, w, nbins, lo, hi, hist, (hipStream_t)stream));
+  return ART_OK;
+}
+
+// The argument checks the two sky-map entry points share (no device is touched): the axes of a
+// table of at most SKY_MAX_DOUBLES doubles, and a mode the table allows.
+static int sky_axes(const int32_t nbins[3], const double lo[3], const double hi[3], bool c_all, int32_t mode,
+                    art::SkyAxes* A) {
+  if (mode < 0 || mode > 2) return fail(ART_E_INVALID, "sky map mode must be 0 (auto), 1 (LDS table) or 2 (global adds)");
+  int64_t table = 2;
+  for (int d = 0; d < 3; ++d) {
+    if (nbins[d] < 1) return fail(ART_E_INVALID, "sky map bin counts must be >= 1");
+    if (nbins[d] > art::SKY_MAX_DOUBLES / table) return fail(ART_E_INVALID, "sky map table exceeds 2^26 doubles");
+    table *= nbins[d];
+    A->n[d] = nbins[d];
+    if (d == 2 && c_all) {
+      A->lo[d] = A->hi[d] = 0.0;
+      continue;
+    }
+    if (!std::isfinite(lo[d]) || !std::isfinite(hi[d]) || !(lo[d] < hi[d]))
+      return fail(ART_E_INVALID, "sky map ranges need finite lo < hi");
+    A->lo[d] = lo[d];
+    A->hi[d] = hi[d];
+  }
+  A->c_all = c_all;
+  if (mode == 1 && table > art::SKY_LDS_DOUBLES)
+    return fail(ART_E_INVALID, "sky map mode 1: the table exceeds the LDS budget of 8192 doubles");
+  return ART_OK;
+}
+
+int art_histogram3_device(int64_t n, const double* a, const double* b, const double* c, const int8_t* species,
+                          const double* w, const int32_t nbins[3], const double lo[3], const double hi[3], int32_t mode,
+                          double* hist, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
+  if (!nbins || !lo || !hi) return fail(ART_E_INVALID, "NULL nbins, lo or hi");
+  art::SkyAxes A;
+  int rc = sky_axes(nbins, lo, hi, false, mode, &A);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  if (!a || !b || !c || !hist) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  HIP_OK(art::launch_sky_map(n, a, b, c, species, w, A, mode, hist, (hipStream_t)stream));
+  return ART_OK;
+}
+
+int art_sky_map_segments_device(const art_params* p, const art_sky_spec* spec, int64_t n, const double* x_end,
+                                const double* k_end, const double* u7_end, const int32_t* status, const int8_t* species,
+                                const double* w, const double* dw_offset, double* hist, int32_t* bin_out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
+  if (!spec) return fail(ART_E_INVALID, "NULL spec");
+  if (spec->theta_axis != 0 && spec->theta_axis != 1)
+    return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
+  const int32_t nbins[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
+  const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
+  const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
+  art::SkyAxes A;
+  if ((rc = sky_axes(nbins, lo, hi, spec->n_dw == 1, spec->mode, &A))) return rc;
+  if (n == 0) return ART_OK;
+  if (!x_end || !k_end || !u7_end || !status || !hist) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  HIP_OK(art::launch_sky_map_segments(art::make_kparams(*p), n, x_end, k_end, u7_end, status, species, w, dw_offset, A,
+                                      spec->theta_axis, spec->mode, hist, bin_out, (hipStream_t)stream));
+  return ART_OK;
+}
+
+// The rows, flux, sky map and totals of a chunk of events whose forests lie in HBM (include/art.h):
+// a scan of the final nodes and event_rows_kernel, both on `stream`.
+int art_event_rows_device(const art_params* p, const art_event_rows_in* in, const art_event_rows_out* out,
+                          void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
+  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
+  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
+  if (out->ncols != art::EVENT_COLS_SHORT && out->ncols != art::EVENT_COLS_FULL)
+    return fail(ART_E_INVALID, "ncols must be 13 or 29");
+  if ((out->rows || out->bin_out) && out->row_capacity < in->n_nodes)
+    return fail(ART_E_INVALID, "row_capacity must be >= n_nodes");
+  if (out->nbins < 0 || out->nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
+  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
+  int cos_axis = 1, mode = 2;
+  if (out->sky) {
+    const art_sky_spec* spec = out->sky;
+    if (spec->theta_axis != 0 && spec->theta_axis != 1)
+      return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
+    const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
+    const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
+    const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
+    if ((rc = sky_axes(nb, lo, hi, spec->n_dw == 1, spec->mode, &A))) return rc;
+    if (spec->mode == 1 && 2 * (int64_t)nb[0] * nb[1] * nb[2] + 2 * out->nbins > art::SKY_LDS_DOUBLES)
+      return fail(ART_E_INVALID, "sky map mode 1: the sky and flux tables exceed the LDS budget of 8192 doubles");
+    cos_axis = spec->theta_axis;
+    mode = spec->mode;
+  }
+  if (in->n_events == 0 || (in->n_nodes == 0 && !in->attempts)) return ART_OK;
+  if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
+  if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
+  if (out->sky && !out->sky_hist) return fail(ART_E_INVALID, "sky_hist is NULL");
+  if (in->n_nodes > 0 && (!in->x || !in->k_init || !in->weight5 || !in->back || !in->back_counts || !in->nodes ||
+                          !in->counts || !in->infos))
+    return fail(ART_E_INVALID, "NULL input buffer");
+  const art_segment_out* ce = in->cyc_end;
+  if (in->cyc_slot && (in->cyc_n < 0 || (in->cyc_n > 0 && (!in->cyc_tau || !ce || !ce->x_end || !ce->k_end ||
+                                                           !ce->u7_end || !ce->tau_end || !ce->status))))
+    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0, cyc_tau and the re-run's end states");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  art::EventRowsArgs a{};
+  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
+  a.row_capacity = out->row_capacity;
+  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
+  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
+  if (in->cyc_slot) {
+    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
+    if (ce) {
+      a.cyc_x_end = ce->x_end; a.cyc_k_end = ce->k_end; a.cyc_u7_end = ce->u7_end; a.cyc_tau_end = ce->tau_end;
+      a.cyc_status = ce->status;
+    }
+  }
+  a.mass_a = p->mass_a;
+  a.ncols = out->ncols; a.nbins = out->nbins;
+  a.rows = out->rows; a.flux = out->flux; a.sky_hist = out->sky ? out->sky_hist : nullptr; a.totals = out->totals;
+  a.bin_out = out->sky ? out->bin_out : nullptr;
+  void* block = nullptr;
+  if (in->n_nodes > 0) {
+    const size_t pos_bytes = ((size_t)in->n_nodes * 4 + 255) & ~(size_t)255, tmp_bytes = art::event_scan_bytes(in->n_nodes);
+    if ((rc = scratch_alloc(s, pos_bytes + tmp_bytes, &block))) return rc;
+    a.pos = (const int32_t*)block;
+    hipError_t e = art::launch_event_scan(in->n_nodes, in->nodes, false, (int32_t*)block, (char*)block + pos_bytes,
+                                          tmp_bytes, s);
+    if (e == hipSuccess) e = art::launch_event_rows(a, A, cos_axis, mode, s);
+    (void)hipFreeAsync(block, s);
+    HIP_OK(e);
+  } else {
+    HIP_OK(art::launch_event_rows(a, A, cos_axis, mode, s));
+  }
+  return ART_OK;
+}
+
+// The cyclotron re-run's batch (include/art.h): scan, one count to the host, gather.
+int art_event_gather_photons_device(const art_params* p, int64_t n_events, const double* erg, int64_t n_nodes,
+                                    const art_tree_node* nodes, int64_t capacity, double* x0, double* k0,
+                                    double* erg_out, double* dw, double* ln_t0, int8_t* species, int32_t* slot,
+                                    int64_t* n_out, void* stream) {
+  std::unique_lock<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!n_out) return fail(ART_E_INVALID, "n_out is NULL");
+  if (n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
+  if (n_nodes < 0 || n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
+  if (capacity < 0) return fail(ART_E_INVALID, "capacity must be >= 0");
+  *n_out = 0;
+  if (n_nodes == 0) return ART_OK;
+  if (!erg || !nodes || !slot) return fail(ART_E_INVALID, "NULL input buffer");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  TreeScratch ts;  // (its block and its pinned word, released when the call returns)
+  ts.s = s;
+  const size_t pos_bytes = ((size_t)(n_nodes + 1) * 4 + 255) & ~(size_t)255, tmp_bytes = art::event_scan_bytes(n_nodes + 1);
+  if ((rc = scratch_alloc(s, pos_bytes + tmp_bytes, &ts.block))) return rc;
+  if (hipHostMalloc((void**)&ts.host, 64, hipHostMallocDefault) != hipSuccess) return fail(ART_E_NOMEM, "hipHostMalloc failed");
+  int32_t* pos = (int32_t*)ts.block;
+  // the count is the sum of the last prefix and the last node's own flag: both come to the host
+  HIP_OK(art::launch_event_scan(n_nodes, nodes, true, pos, (char*)ts.block + pos_bytes, tmp_bytes, s));
+  HIP_OK(hipMemcpyAsync(ts.host, pos + (n_nodes - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(ts.host + 2, &nodes[n_nodes - 1], 2 * sizeof(int32_t) + sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  lk.unlock();
+  const hipError_t we = hipStreamSynchronize(s);
+  lk.lock();
+  if (we != hipSuccess) return fail(ART_E_HIP, "hipStreamSynchronize: %s", hipGetErrorString(we));
+  // ts.host[2..4]: the last node's tree, species, is_final
+  const int64_t m = (int64_t)ts.host[0] + ((ts.host[4] != 0 && ts.host[3] != ART_AXION) ? 1 : 0);
+  *n_out = m;
+  if (m > capacity) return fail(ART_E_NOMEM, "capacity is too small: %s final photons", std::to_string(m).c_str());
+  if (m > 0 && (!x0 || !k0 || !erg_out || !dw || !ln_t0 || !species)) return fail(ART_E_INVALID, "NULL batch buffer");
+  art::TreeBatch B{};
+  B.x0 = x0; B.k0 = k0; B.erg = erg_out; B.dw = dw; B.lnt0 = ln_t0; B.species = species;
+  const double dt0 = std::exp(-30.0), ln_dt0 = std::log(dt0);  // art_grow_trees_device's
+  HIP_OK(art::launch_event_gather(n_nodes, nodes, pos, n_events, erg, m, B, slot, dt0, ln_dt0, s));
+  return ART_OK;  // (ts releases pos in the stream's order, after the gather)
+}
+
+int art_eval_rhs_device(const art_params* p, int64_t n, const double* u, const double* tau, const double* erg,
+                        const int8_t* species, double* du, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  HIP_OK(art::launch_eval_rhs(art::make_kparams(*p), n, u, tau, erg, species, du, (hipStream_t)stream));
+  return ART_OK;
+}
+
+int art_eval_hamiltonian_device(const art_params* p, int64_t n, const double* x, const double* k, const double* T,
+                                const double* E, double* H, double* dHdx, double* dHdk, double* dHdT, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  HIP_OK(art::launch_eval_hamiltonian(art::make_kparams(*p), n, x, k, T, E, H, dHdx, dHdk, dHdT, (hipStream_t)stream));
+  return ART_OK;
+}
+
+int art_eval_condition_device(const art_params* p, int64_t n, const double* u, const double* tau, double* out,
+                              void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  HIP_OK(art::launch_eval_condition(art::make_kparams(*p), n, u, tau, out, (hipStream_t)stream));
+  return ART_OK;
+}
+
+int art_eval_cyclotron_device(const art_params* p, int64_t n, const double* pos, const double* k, const double* t,
+                              double* wc, double* tau, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (n == 0) return ART_OK;
+  if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
+  if (!pos || !k || !t || !wc || !tau) return fail(ART_E_INVALID, "NULL buffer");
+  DeviceCtx* c;
+  if ((rc = current_ctx(&c))) return rc;
+  HIP_OK(art::launch_eval_cyclotron(art::make_kparams(*p), n, pos, k, t, wc, tau, (hipStream_t)stream));
+  return ART_OK;
+}
+
+int art_eval_math_device(int32_t fn, int32_t tu, int64_t n, const double* a, const double* b, double* out0,
+                         double* out1, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (fn < 0 || fn >= ART_MATH_COUNT) return fail(ART_E_INVALID, "unknown fn (ART_MATH_*)");
+  if (tu != 0 && tu != 1) return fail(ART_E_INVALID, "tu must be 0 or 1");
+  if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
+  if (n == 0) return ART_OK;
+  const bool two = fn == ART_MATH_MAX_ABS || fn == ART_MATH_MIN_Q || fn == ART_MATH_MAX_Q || fn == ART_MATH_RCLAMP;
+  if (!a || (two && !b)) return fail(ART_E_INVALID, "NULL operand");
+  DeviceCtx* c;
+  int rc = current_ctx(&c);
+  if (rc) return rc;
+  HIP_OK(art::launch_eval_math(fn, tu, n, a, b, out0, out1, (hipStream_t)stream));
+  return ART_OK;
+}
+
+}  // extern "C"

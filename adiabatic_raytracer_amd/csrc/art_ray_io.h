@@ -222,7 +222,7 @@ __device__ inline void finalize_one(const KParams& P, int64_t n, int64_t i, int6
   }
 }
 
-// (DON = 3) the SoA output blob of piece p (art_capi.cpp, propagate_host_maskless: the same
+// (DON = 3) the SoA output blob of piece p (art_host_stream.cpp, StreamCall: the same
 // layout and 256-byte alignments), its rows m long
 __device__ inline SegOut piece_blob(const SegOut& out, int64_t n, int p, int64_t& m) {
   m = piece_rays(out.pieces, p);

@@ -1,8 +1,10 @@
 """The host C++ of libart under AddressSanitizer + UndefinedBehaviorSanitizer (SURVEY §5,
 tools/asan/): the batched tree driver (art_forest.cpp) on the oracle's CPU segments --
 forward trees, Monte-Carlo branches, the backtrace, saveMode 3 data, determinism and the
-error paths -- and the C boundary (art_capi.cpp): its host entry points and every argument
-check. Any sanitizer report fails the run (UBSan without recovery, LeakSanitizer on for
+error paths -- the C boundary (the host units of art_host.h: art_context.cpp, art_device.cpp,
+art_host_stream.cpp, art_host_paths.cpp, art_post.cpp, art_rccl.cpp): its host entry points and
+every argument check -- and the host paths' plan and copy lists (art_host_plan.h, through
+tools/hostplancheck.cpp's own cases). Any sanitizer report fails the run (UBSan without recovery, LeakSanitizer on for
 the driver with third-party runtimes suppressed)."""
 import os
 import shutil
@@ -21,7 +23,8 @@ def built():
     return ASAN
 
 
-@pytest.mark.parametrize("exe,leaks,ok", [("forest_asan", 1, "forest OK"), ("capi_asan", 0, "capi OK")])
+@pytest.mark.parametrize("exe,leaks,ok", [("forest_asan", 1, "forest OK"), ("capi_asan", 0, "capi OK"),
+                                          ("hostplan_asan", 1, "hostplan OK")])
 def test_host_code_is_sanitizer_clean(built, exe, leaks, ok):
     env = dict(os.environ, ASAN_OPTIONS=f"detect_leaks={leaks}:abort_on_error=0",
                LSAN_OPTIONS=f"suppressions={os.path.join(built, 'lsan.supp')}",

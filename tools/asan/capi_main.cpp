@@ -1,5 +1,5 @@
 // capi_main.cpp -- TEST INFRASTRUCTURE ONLY: the host code of the C boundary
-// (art_capi.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer, in a container
+// (the host units of art_host.h) under AddressSanitizer + UndefinedBehaviorSanitizer, in a container
 // without a GPU: the pure host entry points, every argument check, and the paths that
 // reach the HIP runtime (which then reports that no device is present). The kernels'
 // launch wrappers are replaced by stubs (launch_stubs.cpp). Prints "capi OK".

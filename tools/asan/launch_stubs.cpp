@@ -1,5 +1,5 @@
 // launch_stubs.cpp -- TEST INFRASTRUCTURE ONLY: the kernel launch wrappers of
-// art_internal.h for the host-only sanitizer build of art_capi.cpp (capi_main.cpp). No GPU
+// art_internal.h for the host-only sanitizer build of the C boundary's host units (capi_main.cpp). No GPU
 // exists there, so every launch reports hipErrorNoDevice.
 #include "../../adiabatic_raytracer_amd/csrc/art_internal.h"
 

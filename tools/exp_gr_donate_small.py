@@ -4,7 +4,7 @@ to which a donation-free launch runs the 1-wave/SIMD build (ncu x 256 rays): the
 kernel and graduation) against donation off (0: the 1-wave/SIMD build, no tail kernel). The
 batches are forward roots of configs[3] (the first n rays of the seed-1769 batch); every
 setting is timed on the same inputs, interleaved, and its outputs compared bit for bit.
-One JSON line per (n, setting). ADVICE r04 (low): art_capi.cpp launch_donate."""
+One JSON line per (n, setting). ADVICE r04 (low): art_device.cpp launch_donate."""
 import json
 import os
 import sys
