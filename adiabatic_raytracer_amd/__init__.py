@@ -5,11 +5,11 @@ conversion-surface sampling and the binned flux, all on hand-written HIP kernels
 libart.so (include/art.h). `Engine` (device-resident torch tensors) is imported lazily."""
 from ._lib import (ART_AXION, ART_PHOTON, ART_RK4, ART_VERN6, STATUS_NAMES, ArtError,  # noqa: F401
                    load as load_library)
-from .raytracer import (Find_Conversion_Surface, Params, Propagated, func_axion, func_photon,  # noqa: F401
+from .raytracer import (Find_Conversion_Surface, Halo, Params, Propagated, func_axion, func_photon,  # noqa: F401
                         get_Prob_nonAD, params_from_mvars, propagate, propagate_batch, sample_conversion_points,
                         vern6_tableau)
 
-__all__ = ["Params", "propagate", "propagate_batch", "get_Prob_nonAD", "Find_Conversion_Surface",
+__all__ = ["Params", "Halo", "propagate", "propagate_batch", "get_Prob_nonAD", "Find_Conversion_Surface",
            "sample_conversion_points", "Engine", "func_photon", "func_axion"]
 
 

@@ -53,6 +53,10 @@ class EventRowsOut(C.Structure):  # include/art.h art_event_rows_out
                 ("totals", C.c_void_p)]
 
 
+class ArtHalo(C.Structure):  # include/art.h art_halo
+    _fields_ = [("v0", C.c_double), ("v_ns", C.c_double * 3), ("v_prop", C.c_double)]
+
+
 EVENT_TOTALS = ("rows", "photon_rows", "sum_axion", "sum_photon", "attempts_minus_1", "cyclotron_mismatches")
 
 
@@ -71,6 +75,7 @@ class TreeTraj(C.Structure):  # include/art.h art_tree_traj
 _P = C.POINTER(ArtParams)
 _v = C.c_void_p
 _i64, _i32, _d, _u64 = C.c_int64, C.c_int32, C.c_double, C.c_uint64
+_H = C.POINTER(ArtHalo)
 SIGNATURES = {
     "art_abi_version": (C.c_int, []),
     "art_last_error": (C.c_char_p, []),
@@ -100,6 +105,8 @@ SIGNATURES = {
     "art_get_prob_nonad_device": (C.c_int, [_P, _i64, _v, _v, _v, _i64, _v, _v, _v]),
     "art_sample_conversion_points_host": (C.c_int, [_P, _d, _u64, _i64, _i64, _v, _v, _v, _v, _v, _v]),
     "art_sample_conversion_points_device": (C.c_int, [_P, _d, _u64, _i64, _i64, _v, _v, _v, _v, _v, _v, _v]),
+    "art_sample_conversion_points_halo_host": (C.c_int, [_P, _H, _d, _u64, _i64, _i64, _v, _v, _v, _v, _v, _v]),
+    "art_sample_conversion_points_halo_device": (C.c_int, [_P, _H, _d, _u64, _i64, _i64, _v, _v, _v, _v, _v, _v, _v]),
     "art_flux_histogram_device": (C.c_int, [_P, _i64, _v, _v, _v, _v, _v, _i32, _v, _v]),
     "art_grow_trees": (C.c_int, [_P, _i64, _v, _v, _v, _v, C.POINTER(TreeOpts), _i64, _v, C.POINTER(_i64), _v, _v]),
     "art_grow_trees_traj": (C.c_int, [_P, _i64, _v, _v, _v, _v, C.POINTER(TreeOpts), _i64, _v, C.POINTER(_i64), _v,
@@ -108,6 +115,8 @@ SIGNATURES = {
                                         C.POINTER(_i64), _v]),
     "art_event_weight_host": (C.c_int, [_P, _d, _d, _d, _i64, _v, _v, _v, _v]),
     "art_event_weight_device": (C.c_int, [_P, _d, _d, _d, _i64, _v, _v, _v, _v, _v]),
+    "art_event_weight_halo_host": (C.c_int, [_P, _H, _d, _d, _d, _i64, _v, _v, _v, _v]),
+    "art_event_weight_halo_device": (C.c_int, [_P, _H, _d, _d, _d, _i64, _v, _v, _v, _v, _v]),
     "art_recent_kernel_ms": (C.c_int, [_i32, _v]),
     "art_recent_kernel_span_ms": (C.c_int, [_i32, _v]),
     "art_set_tail_donation": (C.c_int, [_i32]),

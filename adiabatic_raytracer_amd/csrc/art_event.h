@@ -7,6 +7,7 @@
 #pragma once
 
 #include "art_core.h"
+#include "art_halo.h"
 
 namespace art {
 
@@ -170,6 +171,21 @@ __host__ __device__ inline EventW event_weight(const KParams& P, const double x[
   const double redshift = sqrt(1.0 - GM2 / rmag);
   const double phaseS = dense_extra * (2.0 * PI * maxR * maxR) * (rho_DM * 1e9) / P.mass_a * E.jacobian_GR;
   E.sln_prob = E.cos_w * redshift * phaseS * 1e10 * C_KM * 1e5 * mcmc_weight;
+  return E;
+}
+
+// The same with the halo model (art_halo.h): vifty is the sampler's u/c with |u| = s, sln_prob
+// carries the importance ratio F of the draw, and vel_eng is |vifty|²/2 -- without the
+// reference's second division by c (MainRunner.jl:522 on a vIfty divided at RayTracer.jl:1651),
+// so that column 12 of the rows, u7_end/m_a + vel_eng, is the line position.
+__host__ __device__ inline EventW event_weight_halo(const KParams& P, const double x[3], const double k_init[3],
+                                                    const double vifty[3], double maxR, double rho_DM,
+                                                    double mcmc_weight, const HaloK& H) {
+  EventW E = event_weight(P, x, k_init, vifty, maxR, rho_DM, mcmc_weight);
+  const double v2 = vifty[0] * vifty[0] + vifty[1] * vifty[1] + vifty[2] * vifty[2];
+  const double u[3] = {vifty[0] * C_KM, vifty[1] * C_KM, vifty[2] * C_KM};
+  E.sln_prob *= halo_factor(u, sqrt(v2) * C_KM, H.v0, H.v_ns, H.vp);
+  E.vel_eng = v2 / 2.0;
   return E;
 }
 

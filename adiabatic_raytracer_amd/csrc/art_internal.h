@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "art_core.h"
+#include "art_halo.h"
 #include "art_pieces.h"
 #include "art_tree_step.h"
 
@@ -223,13 +224,18 @@ TFn nl_tail(int geom);
 using SFn = void (*)(const KParams, const double, const uint64_t, const int64_t, const int64_t, double*, double*,
                      double*, double*, int32_t*, int32_t*, unsigned long long*);
 SFn nl_sample(int wps, bool blocks);
+// the same builds with the halo velocity model (sample_kernel's HALO, art_halo.h): one more
+// argument, the proposal's speed scale
+using SHFn = void (*)(const KParams, const double, const uint64_t, const int64_t, const int64_t, double*, double*,
+                      double*, double*, int32_t*, int32_t*, unsigned long long*, const double);
+SHFn nl_sample_halo(int wps, bool blocks);
 int helper_waves_per_simd(const KParams& P);
 // The batch size up to which launch_propagate runs every ray on a wave of its own (tail_kernel):
 // ART_SMALL_TAIL, default one ray per SIMD of the device; 0 switches it off.
 int64_t small_tail_limit();
 hipError_t launch_sample(const KParams& P, double maxR, uint64_t seed, int64_t ray_offset, int64_t n, double* x,
                          double* k, double* erg, double* vifty, int32_t* w, int32_t* att, unsigned long long* queue,
-                         hipStream_t s, int waves);
+                         hipStream_t s, int waves, const HaloK* halo = nullptr);  // halo: the HALO builds
 hipError_t launch_prob(const KParams& P, int64_t nc, const double* pos, const double* kpos, const double* erg,
                        int64_t n_groups, const int64_t* gstart, double* out, hipStream_t s);
 hipError_t launch_flux(const KParams& P, int64_t n, const double* x_end, const double* k_end, const int32_t* status,
@@ -260,7 +266,8 @@ hipError_t launch_eval_hamiltonian(const KParams& P, int64_t n, const double* x,
                                    const double* E, double* H, double* dHdx, double* dHdk, double* dHdT,
                                    hipStream_t s);
 hipError_t launch_event_weight(const KParams& P, int64_t n, const double* x, const double* k, const double* v,
-                               double maxR, double rho, double mcmc, double* out, hipStream_t s);
+                               double maxR, double rho, double mcmc, double* out, hipStream_t s,
+                               const HaloK* halo = nullptr);  // halo: event_weight_halo_kernel
 hipError_t launch_eval_condition(const KParams& P, int64_t n, const double* u, const double* tau, double* out,
                                  hipStream_t s);
 hipError_t launch_eval_cyclotron(const KParams& P, int64_t n, const double* x, const double* k, const double* t,

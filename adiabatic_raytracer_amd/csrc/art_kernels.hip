@@ -296,6 +296,26 @@ __global__ __launch_bounds__(256) void event_weight_kernel(const KParams P, cons
   out[4 * n + i] = E.vel_eng;
 }
 
+// The same with the halo model's factor and vel_eng (event_weight_halo, art_event.h).
+__global__ __launch_bounds__(256) void event_weight_halo_kernel(const KParams P, const int64_t n,
+                                                                const double* __restrict__ x,
+                                                                const double* __restrict__ k,
+                                                                const double* __restrict__ v, const double maxR,
+                                                                const double rho, const double mcmc, const HaloK H,
+                                                                double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double xi[3] = {x[i], x[n + i], x[2 * n + i]};
+  const double ki[3] = {k[i], k[n + i], k[2 * n + i]};
+  const double vi[3] = {v[i], v[n + i], v[2 * n + i]};
+  const EventW E = event_weight_halo(P, xi, ki, vi, maxR, rho, mcmc, H);
+  out[i] = E.cos_w;
+  out[n + i] = E.jacobian_GR;
+  out[2 * n + i] = E.sln_prob;
+  out[3 * n + i] = E.erg_inf_ini;
+  out[4 * n + i] = E.vel_eng;
+}
+
 // ---------------------------------------------------------------------------
 // host-side launch wrappers (art_internal.h)
 // Resident blocks of `func` per CU from its own resource use: the unified 512-entry VGPR file
@@ -624,7 +644,7 @@ hipError_t launch_helpers(const KParams& P, int64_t n, const SegIn& in, const Se
 
 hipError_t launch_sample(const KParams& P, double maxR, uint64_t seed, int64_t ray_offset, int64_t n, double* x,
                          double* k, double* erg, double* vifty, int32_t* w, int32_t* att, unsigned long long* queue,
-                         hipStream_t s, int waves) {
+                         hipStream_t s, int waves, const HaloK* halo) {
   // lines of up to 2.2 x 60 km (264 steps): the 3-wave build, step by step (blocks of steps: no
   // faster there, 118 vs 119 ms per 1e7 flat samples); longer lines, mostly certified far from the
   // conversion surface: 2 waves, blocks of 3 steps (the scan's largest-maxR point 55 -> 43 ms,
@@ -637,6 +657,13 @@ hipError_t launch_sample(const KParams& P, double maxR, uint64_t seed, int64_t r
   if (const char* e = std::getenv("ART_SAMPLER_BLOCKS"))
     if (e[0] == '0' || e[0] == '1') blocks = e[0] == '1';
 
+  if (halo) {  // the HALO builds: the same choice of build, the proposal scale as one more argument
+    const SHFn fh = nl_sample_halo(wps, blocks);
+    const int gh = persistent_blocks((const void*)fh, n, 256, 1);
+    hipLaunchKernelGGL(fh, dim3(gh), dim3(256), 0, s, P, maxR, seed, ray_offset, n, x, k, erg, vifty, w, att, queue,
+                       halo->vp);
+    return hipGetLastError();
+  }
   const SFn fn = nl_sample(wps, blocks);
   const int grid = persistent_blocks((const void*)fn, n, 256, 1);
   hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, s, P, maxR, seed, ray_offset, n, x, k, erg, vifty, w, att, queue);
@@ -729,7 +756,12 @@ hipError_t launch_eval_hamiltonian(const KParams& P, int64_t n, const double* x,
 }
 
 hipError_t launch_event_weight(const KParams& P, int64_t n, const double* x, const double* k, const double* v,
-                               double maxR, double rho, double mcmc, double* out, hipStream_t s) {
+                               double maxR, double rho, double mcmc, double* out, hipStream_t s, const HaloK* halo) {
+  if (halo) {
+    hipLaunchKernelGGL(event_weight_halo_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, n, x, k, v, maxR,
+                       rho, mcmc, *halo, out);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(event_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, P, n, x, k, v, maxR, rho,
                      mcmc, out);
   return hipGetLastError();

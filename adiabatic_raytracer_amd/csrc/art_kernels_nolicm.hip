@@ -83,6 +83,10 @@ SFn nl_sample(int wps, bool blocks) {
   return wps == 3 ? (blocks ? sample_kernel<3, true> : sample_kernel<3, false>)
                   : (blocks ? sample_kernel<2, true> : sample_kernel<2, false>);
 }
+SHFn nl_sample_halo(int wps, bool blocks) {
+  return wps == 3 ? (blocks ? sample_kernel<3, true, true, double> : sample_kernel<3, false, true, double>)
+                  : (blocks ? sample_kernel<2, true, true, double> : sample_kernel<2, false, true, double>);
+}
 MFn nl_eval_math(int fn) { return pick_eval_math<1>(fn); }
 
 }  // namespace art

@@ -13,11 +13,32 @@
 namespace art {
 namespace host {
 
-static int sample_device_impl(const art_params* p, double max_r, uint64_t seed, int64_t ray_offset, int64_t n, double* x,
-                       double* k_init, double* erg_inf, double* vifty, int32_t* weights, int32_t* attempts,
-                       hipStream_t s) {
+// An art_halo checked (no device is touched) and resolved for the kernels: v_prop <= 0 is
+// sqrt(v0² + |v_ns|²).
+static int halo_of(const art_halo* h, art::HaloK* K) {
+  if (!std::isfinite(h->v0) || !(h->v0 > 0.0)) return fail(ART_E_INVALID, "halo: v0 must be finite and > 0");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(h->v_ns[i])) return fail(ART_E_INVALID, "halo: v_ns must be finite");
+  if (std::isnan(h->v_prop)) return fail(ART_E_INVALID, "halo: v_prop must not be NaN");
+  if (h->v_prop > 0.0 && h->v_prop < h->v0)
+    return fail(ART_E_INVALID, "halo: v_prop must be >= v0 (the weights are unbounded below it)");
+  K->v0 = h->v0;
+  for (int i = 0; i < 3; ++i) K->v_ns[i] = h->v_ns[i];
+  K->vp = h->v_prop > 0.0
+              ? h->v_prop
+              : std::sqrt(h->v0 * h->v0 + h->v_ns[0] * h->v_ns[0] + h->v_ns[1] * h->v_ns[1] + h->v_ns[2] * h->v_ns[2]);
+  if (!(K->vp <= 3000.0))
+    return fail(ART_E_INVALID, "halo: v_prop must be <= 3000 km/s (the largest draw is 6.1 v_prop, far below c)");
+  return ART_OK;
+}
+
+static int sample_device_impl(const art_params* p, const art_halo* halo, double max_r, uint64_t seed, int64_t ray_offset,
+                       int64_t n, double* x, double* k_init, double* erg_inf, double* vifty, int32_t* weights,
+                       int32_t* attempts, hipStream_t s) {
   int rc = validate(p);
   if (rc) return rc;
+  art::HaloK hk;
+  if (halo && (rc = halo_of(halo, &hk))) return rc;
   if (n == 0) return ART_OK;
   if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
   if (!(max_r > p->rNS)) return fail(ART_E_INVALID, "max_r must exceed rNS (MainRunner.jl:389-396 quits otherwise)");
@@ -29,7 +50,7 @@ static int sample_device_impl(const art_params* p, double max_r, uint64_t seed, 
   HIP_OK(hipMemsetAsync(q, 0, sizeof(unsigned long long), s));
   HIP_OK(hipMemsetAsync(q, 0, 256, s));
   HIP_OK(art::launch_sample(kparams(*p), max_r, seed, ray_offset, n, x, k_init, erg_inf, vifty, weights,
-                            attempts, (unsigned long long*)q, s, c->sampler_waves));
+                            attempts, (unsigned long long*)q, s, c->sampler_waves, halo ? &hk : nullptr));
 #ifdef ART_SAMPLER_SECTIONS  // (dev build: the sampler's section cycles to stderr)
   {
     unsigned long long w[16];
@@ -43,16 +64,20 @@ static int sample_device_impl(const art_params* p, double max_r, uint64_t seed, 
   return ART_OK;
 }
 
-static int event_weight_device_impl(const art_params* p, double max_r, double rho_dm, double mcmc_weight, int64_t n,
-                             const double* x, const double* k_init, const double* vifty, double* out, hipStream_t s) {
+static int event_weight_device_impl(const art_params* p, const art_halo* halo, double max_r, double rho_dm,
+                             double mcmc_weight, int64_t n, const double* x, const double* k_init, const double* vifty,
+                             double* out, hipStream_t s) {
   int rc = validate(p);
   if (rc) return rc;
+  art::HaloK hk;
+  if (halo && (rc = halo_of(halo, &hk))) return rc;
   if (n == 0) return ART_OK;
   if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
   if (!x || !k_init || !vifty || !out) return fail(ART_E_INVALID, "NULL buffer");
   DeviceCtx* c;
   if ((rc = current_ctx(&c))) return rc;
-  HIP_OK(art::launch_event_weight(art::make_kparams(*p), n, x, k_init, vifty, max_r, rho_dm, mcmc_weight, out, s));
+  HIP_OK(art::launch_event_weight(art::make_kparams(*p), n, x, k_init, vifty, max_r, rho_dm, mcmc_weight, out, s,
+                                  halo ? &hk : nullptr));
   return ART_OK;
 }
 
@@ -116,8 +141,17 @@ int art_get_prob_nonad_host(const art_params* p, int64_t nc, const double* pos, 
 int art_sample_conversion_points_device(const art_params* p, double max_r, uint64_t seed, int64_t ray_offset,
                                         int64_t n, double* x, double* k_init, double* erg_inf, double* vifty,
                                         int32_t* weights, int32_t* attempts, void* stream) {
+  return art_sample_conversion_points_halo_device(p, nullptr, max_r, seed, ray_offset, n, x, k_init, erg_inf, vifty,
+                                                  weights, attempts, stream);
+}
+
+// The sampler with the halo velocity model (include/art.h); halo == NULL: the kernels without it.
+int art_sample_conversion_points_halo_device(const art_params* p, const art_halo* halo, double max_r, uint64_t seed,
+                                             int64_t ray_offset, int64_t n, double* x, double* k_init,
+                                             double* erg_inf, double* vifty, int32_t* weights, int32_t* attempts,
+                                             void* stream) {
   std::lock_guard<std::mutex> lk(g_mu);
-  return sample_device_impl(p, max_r, seed, ray_offset, n, x, k_init, erg_inf, vifty, weights, attempts,
+  return sample_device_impl(p, halo, max_r, seed, ray_offset, n, x, k_init, erg_inf, vifty, weights, attempts,
                             (hipStream_t)stream);
 }
 
@@ -126,9 +160,18 @@ int art_sample_conversion_points_device(const art_params* p, double max_r, uint6
 int art_sample_conversion_points_host(const art_params* p, double max_r, uint64_t seed, int64_t ray_offset, int64_t n,
                                       double* x, double* k_init, double* erg_inf, double* vifty, int32_t* weights,
                                       int32_t* attempts) {
+  return art_sample_conversion_points_halo_host(p, nullptr, max_r, seed, ray_offset, n, x, k_init, erg_inf, vifty,
+                                                weights, attempts);
+}
+
+int art_sample_conversion_points_halo_host(const art_params* p, const art_halo* halo, double max_r, uint64_t seed,
+                                           int64_t ray_offset, int64_t n, double* x, double* k_init,
+                                           double* erg_inf, double* vifty, int32_t* weights, int32_t* attempts) {
   std::lock_guard<std::mutex> lk(g_mu);
   int rc = validate(p);
   if (rc) return rc;
+  art::HaloK hk;
+  if (halo && (rc = halo_of(halo, &hk))) return rc;
   if (n == 0) return ART_OK;
   if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
   if (!(max_r > p->rNS)) return fail(ART_E_INVALID, "max_r must exceed rNS (MainRunner.jl:389-396 quits otherwise)");
@@ -141,7 +184,7 @@ int art_sample_conversion_points_host(const art_params* p, double max_r, uint64_
   double* dd = (double*)d;
   int32_t* di = (int32_t*)(dd + 10 * nd);
   hipStream_t s = c->stream;
-  if ((rc = sample_device_impl(p, max_r, seed, ray_offset, n, dd, dd + 3 * nd, dd + 6 * nd, dd + 7 * nd, di, di + nd,
+  if ((rc = sample_device_impl(p, halo, max_r, seed, ray_offset, n, dd, dd + 3 * nd, dd + 6 * nd, dd + 7 * nd, di, di + nd,
                                s)))
     return rc;
   HIP_OK(hipMemcpyAsync(x, dd, nd * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -156,15 +199,30 @@ int art_sample_conversion_points_host(const art_params* p, double max_r, uint64_
 
 int art_event_weight_device(const art_params* p, double max_r, double rho_dm, double mcmc_weight, int64_t n,
                             const double* x, const double* k_init, const double* vifty, double* out, void* stream) {
+  return art_event_weight_halo_device(p, nullptr, max_r, rho_dm, mcmc_weight, n, x, k_init, vifty, out, stream);
+}
+
+// The event weight with the halo model's factor and vel_eng (include/art.h); halo == NULL: without.
+int art_event_weight_halo_device(const art_params* p, const art_halo* halo, double max_r, double rho_dm,
+                                 double mcmc_weight, int64_t n, const double* x, const double* k_init,
+                                 const double* vifty, double* out, void* stream) {
   std::lock_guard<std::mutex> lk(g_mu);
-  return event_weight_device_impl(p, max_r, rho_dm, mcmc_weight, n, x, k_init, vifty, out, (hipStream_t)stream);
+  return event_weight_device_impl(p, halo, max_r, rho_dm, mcmc_weight, n, x, k_init, vifty, out, (hipStream_t)stream);
 }
 
 int art_event_weight_host(const art_params* p, double max_r, double rho_dm, double mcmc_weight, int64_t n,
                           const double* x, const double* k_init, const double* vifty, double* out) {
+  return art_event_weight_halo_host(p, nullptr, max_r, rho_dm, mcmc_weight, n, x, k_init, vifty, out);
+}
+
+int art_event_weight_halo_host(const art_params* p, const art_halo* halo, double max_r, double rho_dm,
+                               double mcmc_weight, int64_t n, const double* x, const double* k_init,
+                               const double* vifty, double* out) {
   std::lock_guard<std::mutex> lk(g_mu);
   int rc = validate(p);
   if (rc) return rc;
+  art::HaloK hk;
+  if (halo && (rc = halo_of(halo, &hk))) return rc;
   if (n == 0) return ART_OK;
   if (n < 0 || n > 2147483647LL) return fail(ART_E_INVALID, "n must be in [0, 2^31)");
   if (!x || !k_init || !vifty || !out) return fail(ART_E_INVALID, "NULL buffer");
@@ -178,7 +236,7 @@ int art_event_weight_host(const art_params* p, double max_r, double rho_dm, doub
   HIP_OK(hipMemcpyAsync(dd, x, nd * 3 * sizeof(double), hipMemcpyHostToDevice, s));
   HIP_OK(hipMemcpyAsync(dd + 3 * nd, k_init, nd * 3 * sizeof(double), hipMemcpyHostToDevice, s));
   HIP_OK(hipMemcpyAsync(dd + 6 * nd, vifty, nd * 3 * sizeof(double), hipMemcpyHostToDevice, s));
-  if ((rc = event_weight_device_impl(p, max_r, rho_dm, mcmc_weight, n, dd, dd + 3 * nd, dd + 6 * nd, dd + 9 * nd, s)))
+  if ((rc = event_weight_device_impl(p, halo, max_r, rho_dm, mcmc_weight, n, dd, dd + 3 * nd, dd + 6 * nd, dd + 9 * nd, s)))
     return rc;
   HIP_OK(hipMemcpyAsync(out, dd + 9 * nd, nd * 5 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));

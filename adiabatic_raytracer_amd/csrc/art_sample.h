@@ -4,6 +4,7 @@
 
 #include "art_core.h"
 #include "art_event.h"
+#include "art_halo.h"
 #include "art_internal.h"
 
 namespace art {
@@ -75,13 +76,25 @@ __device__ inline int seg_cert(const KParams& P, const double* X0, const double*
 // loop-invariant values, reloaded once per scan step -- a good trade where a line has ~111
 // steps with uncertified ones among them, not where it has ~650 mostly skipped ones
 // (launch_sample picks by the line length).
-template <int WPS, bool BLOCKS>
+//
+// HALO (art_halo.h): the speed at infinity s is drawn per attempt from the proposal of scale vp
+// (halo_speed of U[6]; U[7] and U[8] are drawn and unused, so the stream does not move) and
+// vifty is the incoming asymptote of the Kepler orbit through the accepted point
+// (halo_asymptote). The proposal scale is the kernel's one more argument, `vp`: a parameter pack
+// that is empty without HALO, so those instantiations keep their argument list and their code.
+__device__ inline double halo_vp() { return 0.0; }
+__device__ inline double halo_vp(double vp) { return vp; }
+
+template <int WPS, bool BLOCKS, bool HALO = false, class... VP>
 __global__ __launch_bounds__(256, WPS) void sample_kernel(const KParams P, const double maxR, const uint64_t seed,
                                                      const int64_t ray_offset, const int64_t n, double* __restrict__ xo,
                                                      double* __restrict__ ko, double* __restrict__ ergo,
                                                      double* __restrict__ vifo, int32_t* __restrict__ wo,
-                                                     int32_t* __restrict__ ao, unsigned long long* __restrict__ queue) {
-  // line data of every lane [component][lane]: x0 (3), va (3), vl (3), E, 1/E², vIfty (3).
+                                                     int32_t* __restrict__ ao, unsigned long long* __restrict__ queue,
+                                                     const VP... vp) {
+  static_assert(sizeof...(VP) == (HALO ? 1 : 0), "the HALO builds take the proposal scale, the others nothing");
+  // line data of every lane [component][lane]: x0 (3), va (3), vl (3), E, 1/E², vIfty (3; HALO: s
+  // in row 11, rows 12 and 13 unused).
   // A lane reads its own line from here too (its registers hold none of it across the step
   // loop: the kernel fits 2 waves/SIMD without spills)
   __shared__ double sline[14 * 256];
@@ -175,10 +188,14 @@ __global__ __launch_bounds__(256, WPS) void sample_kernel(const KParams P, const
     const double x1 = rR * cR, x2 = rR * sR;
     // rotate (x1, x2, 0) by Inv[EulerMatrix(ϕi, θi, 0)] (:1523-1524); cos(-a) = cos a, sin(-a) = -sin a
     double x0[3] = {x1 * cpi * cti - x2 * spi, x2 * cpi + x1 * spi * cti, -x1 * sti};
-    double vI[3];
+    double vI[3], vmag;
+    if constexpr (HALO) {
+      vmag = halo_speed(U[6], halo_vp(vp...));
+    } else {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) vI[i] = (220.0 + U[6 + i] * 1.0e-5) / sqrt(3.0);
-    const double vmag = sqrt(vI[0] * vI[0] + vI[1] * vI[1] + vI[2] * vI[2]);
+      for (int i = 0; i < 3; ++i) vI[i] = (220.0 + U[6 + i] * 1.0e-5) / sqrt(3.0);
+      vmag = sqrt(vI[0] * vI[0] + vI[1] * vI[1] + vI[2] * vI[2]);
+    }
     const double gammaA = 1.0 / sqrt(1.0 - (vmag / C_KM) * (vmag / C_KM));
     const double E = P.mass_a * sqrt(1.0 + (vmag / C_KM * gammaA) * (vmag / C_KM * gammaA));
     const double iE2 = 1.0 / (E * E);
@@ -196,8 +213,12 @@ __global__ __launch_bounds__(256, WPS) void sample_kernel(const KParams P, const
     }
     Lx[9 * 256] = E;
     Lx[10 * 256] = iE2;
+    if constexpr (HALO) {
+      Lx[11 * 256] = vmag;
+    } else {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) Lx[(11 + i) * 256] = vI[i];
+      for (int i = 0; i < 3; ++i) Lx[(11 + i) * 256] = vI[i];
+    }
     double c_prev = sampler_condition_e(P, x0, vl, E, iE2);
     int qn = 0;  // queued brackets (wave-uniform)
     // This line's window: its chord through the sphere r <= r_win, outside which
@@ -679,8 +700,16 @@ __global__ __launch_bounds__(256, WPS) void sample_kernel(const KParams P, const
       if (count >= randInx || give_up) {
         if (count < randInx) { xsel[0] = xsel[1] = xsel[2] = NAN; count = 0; }
         const double rmag = sqrt(xsel[0] * xsel[0] + xsel[1] * xsel[1] + xsel[2] * xsel[2]);
-        const double vIl[3] = {Lx[11 * 256], Lx[12 * 256], Lx[13 * 256]};
-        const double vmagl = sqrt(vIl[0] * vIl[0] + vIl[1] * vIl[1] + vIl[2] * vIl[2]);  // = vmag
+        double vIl[3], vmagl;
+        if constexpr (HALO) {
+          // the asymptote of the Newtonian orbit through (xsel, vl) with the attempt's speed
+          vmagl = Lx[11 * 256];
+          const double dl[3] = {Lx[6 * 256], Lx[7 * 256], Lx[8 * 256]};
+          halo_asymptote(xsel, dl, vmagl, P.GM_c2 * C_KM * C_KM, vIl);
+        } else {
+          vIl[0] = Lx[11 * 256]; vIl[1] = Lx[12 * 256]; vIl[2] = Lx[13 * 256];
+          vmagl = sqrt(vIl[0] * vIl[0] + vIl[1] * vIl[1] + vIl[2] * vIl[2]);  // = vmag
+        }
         const double vml = sqrt(vmagl * vmagl + 2.0 * P.GM_c2 * C_KM * C_KM / rmag) / C_KM;  // :1644
         double vel[3], vc[3];
 #pragma unroll

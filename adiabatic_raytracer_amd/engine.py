@@ -44,19 +44,24 @@ class Engine:
         return torch.empty(*shape, dtype=dtype, device=self.device)
 
     # ---- conversion-surface sampler (RayTracer.jl:1480-1653, MainRunner.jl:463-529)
-    def sample(self, n: int, seed: int = 1769, ray_offset: int = 0, max_r=None) -> dict:
+    def sample(self, n: int, seed: int = 1769, ray_offset: int = 0, max_r=None, halo=None) -> dict:
         max_r = self.params.max_r() if max_r is None else max_r
         o = {"x": self.empty(3 * n), "k_init": self.empty(3 * n), "erg": self.empty(n), "vifty": self.empty(3 * n),
              "weights": self.empty(n, dtype=torch.int32), "attempts": self.empty(n, dtype=torch.int32)}
+        bufs = [_p(o[k]) for k in ("x", "k_init", "erg", "vifty", "weights", "attempts")]
+        if halo is not None:  # (a raytracer.Halo: the halo velocity model, include/art.h)
+            check(self.lib.art_sample_conversion_points_halo_device(
+                C.byref(self.cp), C.byref(halo.to_c()), float(max_r), int(seed), int(ray_offset), int(n), *bufs,
+                _stream()))
+            return o
         check(self.lib.art_sample_conversion_points_device(
-            C.byref(self.cp), float(max_r), int(seed), int(ray_offset), int(n),
-            *[_p(o[k]) for k in ("x", "k_init", "erg", "vifty", "weights", "attempts")], _stream()))
+            C.byref(self.cp), float(max_r), int(seed), int(ray_offset), int(n), *bufs, _stream()))
         return o
 
-    def forward_roots(self, n: int, seed: int = 1769, ray_offset: int = 0) -> dict:
+    def forward_roots(self, n: int, seed: int = 1769, ray_offset: int = 0, halo=None) -> dict:
         """Segment inputs of the forward-tree roots (MainRunner.jl:653-664 -> :179): photons
         at the sampled conversion points, Δω = -1, ln t0 = -30."""
-        s = self.sample(n, seed, ray_offset)
+        s = self.sample(n, seed, ray_offset, halo=halo)
         return {"x0": s["x"], "k0": s["k_init"], "erg": s["erg"],
                 "dw": torch.full((n,), -1.0, dtype=F64, device=self.device),
                 "ln_t0": torch.full((n,), -30.0, dtype=F64, device=self.device),
@@ -163,10 +168,15 @@ class Engine:
         return out
 
     # ---- per-sample event weight (MainRunner.jl:498-557): 5 x n SoA
-    def event_weight(self, sample: dict, max_r=None, rho_DM=0.45, n_maxSample=6):
+    def event_weight(self, sample: dict, max_r=None, rho_DM=0.45, n_maxSample=6, halo=None):
         n = sample["erg"].numel()
         max_r = self.params.max_r() if max_r is None else max_r
         out = self.empty(5 * n)
+        if halo is not None:  # (the Halo the sample was drawn with)
+            check(self.lib.art_event_weight_halo_device(C.byref(self.cp), C.byref(halo.to_c()), float(max_r),
+                                                        float(rho_DM), float(n_maxSample), n, _p(sample["x"]),
+                                                        _p(sample["k_init"]), _p(sample["vifty"]), _p(out), _stream()))
+            return out.view(5, n)
         check(self.lib.art_event_weight_device(C.byref(self.cp), float(max_r), float(rho_DM), float(n_maxSample), n,
                                                _p(sample["x"]), _p(sample["k_init"]), _p(sample["vifty"]), _p(out),
                                                _stream()))
@@ -314,7 +324,7 @@ class Engine:
 
     def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
                    max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
-                   cyclotron=False, rows=True) -> dict:
+                   cyclotron=False, rows=True, halo=None) -> dict:
         """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
         n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
         event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
@@ -332,6 +342,11 @@ class Engine:
 
         sky_map: a dict of n_theta, n_phi, n_dw, theta_axis, dw_range, mode ({}: the defaults), or None.
         n_dw > 1 needs a dw_range: ValueError without one. rows=False: no rows, the large-run mode.
+
+        halo (a raytracer.Halo): the sampler draws each event's speed at infinity from the halo model and
+        the weights carry its importance ratio; column 12 is u7_end/m_a + |vifty|²/2 of each event
+        ("Halo velocity model"). None (the default): the reference's single speed, every
+        row as before.
 
         Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
         or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
@@ -361,8 +376,8 @@ class Engine:
         parts = []
         for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
             c = min(chunk, int(event_offset) + n_events - lo)
-            s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r)
-            w5 = self.event_weight(s, max_r=max_r, rho_DM=rho_DM, n_maxSample=n_maxSample)
+            s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r, halo=halo)
+            w5 = self.event_weight(s, max_r=max_r, rho_DM=rho_DM, n_maxSample=n_maxSample, halo=halo)
             back = back_eng.grow_trees(s["x"], -s["k_init"], s["erg"], AXION, num_cutoff=0, splittings_cutoff=100000,
                                        crossing_cap=backtrace_cap, prob_cutoff=prob_cutoff, seed=seed, tree_offset=lo)
             fwd = self.grow_trees(s["x"], s["k_init"], s["erg"], PHOTON, num_cutoff=num_cutoff, mc_nodes=MC_nodes,

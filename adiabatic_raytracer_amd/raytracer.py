@@ -21,8 +21,8 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _lib
-from ._lib import (ART_AXION, ART_PHOTON, ART_RK4, ART_VERN6, ArtParams, CrossingBuf, CyclotronOut, SegmentOut,
-                   check)
+from ._lib import (ART_AXION, ART_PHOTON, ART_RK4, ART_VERN6, ArtHalo, ArtParams, CrossingBuf, CyclotronOut,
+                   SegmentOut, check)
 
 ART_NO_CALLBACKS = -(2 ** 31)  # include/art.h: max_crossings for make_tree = false
 
@@ -67,6 +67,30 @@ class Params:
 
     def max_r(self) -> float:
         return Find_Conversion_Surface(self)
+
+
+@dataclass
+class Halo:
+    """The halo velocity model (include/art.h art_halo; beyond the reference, whose sampler draws every
+    axion at one speed): f∞(u) ∝ exp(-|u + v_ns|²/v0²) in the star's frame, all speeds in km/s. v0:
+    the most probable speed (the reference's 220); v_ns: the star's velocity in the halo frame;
+    v_prop: the speed scale of the sampler's proposal, None for sqrt(v0² + |v_ns|²), never below v0.
+    Passed as `halo=` to the sampler and to the event weight, which must get the same one."""
+    v0: float = 220.0
+    v_ns: tuple = (0.0, 0.0, 0.0)
+    v_prop: Optional[float] = None
+
+    def to_c(self) -> ArtHalo:
+        v = [float(c) for c in self.v_ns]
+        if len(v) != 3:
+            raise ValueError("Halo: v_ns has three components")
+        return ArtHalo(float(self.v0), (C.c_double * 3)(*v), -1.0 if self.v_prop is None else float(self.v_prop))
+
+    def vp(self) -> float:
+        """the proposal's speed scale"""
+        if self.v_prop is not None and self.v_prop > 0:
+            return float(self.v_prop)
+        return float(np.sqrt(self.v0 ** 2 + sum(float(c) ** 2 for c in self.v_ns)))
 
 
 def params_from_mvars(Mvars, NumerP, is_axion: bool, Ax_g: float = 1e-12, **numerics) -> tuple:
@@ -353,34 +377,47 @@ def get_Prob_nonAD(pos, kpos, Mass_a, Ax_g, θm, ωPul, B0, rNS, erg_inf_ini, vI
     return out
 
 
-def sample_conversion_points(params: Params, n: int, seed: int = 1769, ray_offset: int = 0, max_r=None) -> dict:
+def sample_conversion_points(params: Params, n: int, seed: int = 1769, ray_offset: int = 0, max_r=None,
+                             halo: Optional[Halo] = None) -> dict:
     """find_samples_new (RayTracer.jl:1480-1653) + k_norm_Cart (MainRunner.jl:529) on the
-    GPU: one accepted conversion point per ray, Philox stream keyed by (seed, ray id)."""
+    GPU: one accepted conversion point per ray, Philox stream keyed by (seed, ray id).
+    halo (a Halo): the speed at infinity drawn per attempt and vifty the Kepler orbit's incoming
+    asymptote; None (the default): the reference's single speed."""
     max_r = params.max_r() if max_r is None else max_r
     out = {"x": np.zeros(3 * n), "k_init": np.zeros(3 * n), "erg": np.zeros(n), "vifty": np.zeros(3 * n),
            "weights": np.zeros(n, np.int32), "attempts": np.zeros(n, np.int32)}
     cp = params.to_c()
+    bufs = [_ptr(out[k]) for k in ("x", "k_init", "erg", "vifty", "weights", "attempts")]
+    if halo is not None:
+        check(_lib.load().art_sample_conversion_points_halo_host(
+            C.byref(cp), C.byref(halo.to_c()), float(max_r), int(seed), int(ray_offset), int(n), *bufs))
+        return out
     check(_lib.load().art_sample_conversion_points_host(
-        C.byref(cp), float(max_r), int(seed), int(ray_offset), int(n), *[_ptr(out[k]) for k in
-                                                                        ("x", "k_init", "erg", "vifty", "weights",
-                                                                         "attempts")]))
+        C.byref(cp), float(max_r), int(seed), int(ray_offset), int(n), *bufs))
     return out
 
 
 EVENT_FIELDS = ("cos_w", "jacobian_GR", "sln_prob", "erg_inf_ini", "vel_eng")
 
 
-def event_weight(params: Params, x, k_init, vifty, max_r=None, rho_DM=0.45, n_maxSample=6) -> dict:
+def event_weight(params: Params, x, k_init, vifty, max_r=None, rho_DM=0.45, n_maxSample=6,
+                 halo: Optional[Halo] = None) -> dict:
     """Per-sample event weight of main_runner_tree (MainRunner.jl:498-557) on the GPU:
     cos_w of RT.dwp_ds, jacobian_GR = RT.g_det and sln_prob = |cos_w| redshift phaseS
     (1e5)^2 c 1e5 mcmc_weights (before the final division by f_inx, :722). x, k_init and
-    vifty are the sampler's SoA outputs (3n)."""
+    vifty are the sampler's SoA outputs (3n). halo: the Halo the samples were drawn with; sln_prob
+    then carries the draw's importance ratio and vel_eng is |vifty|²/2 (include/art.h)."""
     max_r = params.max_r() if max_r is None else max_r
     x, k_init, vifty = (np.ascontiguousarray(a, np.float64).reshape(-1) for a in (x, k_init, vifty))
     n = x.size // 3
     out = np.zeros(5 * n)
-    check(_lib.load().art_event_weight_host(C.byref(params.to_c()), float(max_r), float(rho_DM), float(n_maxSample),
-                                            n, _ptr(x), _ptr(k_init), _ptr(vifty), _ptr(out)))
+    if halo is not None:
+        check(_lib.load().art_event_weight_halo_host(C.byref(params.to_c()), C.byref(halo.to_c()), float(max_r),
+                                                     float(rho_DM), float(n_maxSample), n, _ptr(x), _ptr(k_init),
+                                                     _ptr(vifty), _ptr(out)))
+    else:
+        check(_lib.load().art_event_weight_host(C.byref(params.to_c()), float(max_r), float(rho_DM),
+                                                float(n_maxSample), n, _ptr(x), _ptr(k_init), _ptr(vifty), _ptr(out)))
     o = out.reshape(5, n)
     return {k: o[i].copy() for i, k in enumerate(EVENT_FIELDS)}
 

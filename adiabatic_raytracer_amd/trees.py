@@ -179,7 +179,7 @@ def save_node(fh, node, tr, q):
 def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_DM=0.45, n_maxSample=6,
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
-                     sky_map=None, device_trees=False, device_events=False):
+                     sky_map=None, device_trees=False, device_events=False, halo=None):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -228,7 +228,12 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     host once, for the npy file and the return value, and the raw flux, sky map and totals feed the same
     all-reduce. The event_/final_ text files of saveMode > 1 need per-node data on the host: with a
     dir_tag that is a ValueError. A sky map with n_dw > 1 needs a dw_range. With the default False every
-    row, file and run_info key is unchanged."""
+    row, file and run_info key is unchanged.
+
+    halo (a raytracer.Halo, beyond the reference): the events' speeds at infinity are drawn from the halo
+    velocity model and their weights carry its importance ratio (sample_conversion_points, event_weight),
+    on all three paths; column 12 is then u7_end/m_a + |vifty|²/2 event by event ("Halo
+    velocity model"). With the default None every row, file and run_info key is unchanged."""
     if device_events:
         if saveMode > 1 and dir_tag is not None:
             raise ValueError("device_events: the text files and tree dumps of saveMode > 1 with a dir_tag need the "
@@ -237,7 +242,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                                         num_cutoff=num_cutoff, MC_nodes=MC_nodes, max_nodes=max_nodes,
                                         prob_cutoff=prob_cutoff, saveMode=saveMode, dir_tag=dir_tag, file_tag=file_tag,
                                         backtrace_cap=backtrace_cap, rank=rank, world=world, nbins=nbins, run_info=run_info,
-                                        cyclotron=cyclotron, sky_map=sky_map)
+                                        cyclotron=cyclotron, sky_map=sky_map, halo=halo)
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -260,8 +265,9 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     max_r = params.max_r()
     if max_r < params.rNS:
         raise ValueError("maxR < rNS: this neutron star has no conversion surface (MainRunner.jl:387-396)")
-    s = sample_conversion_points(params, n_ev, seed=seed, ray_offset=lo, max_r=max_r)
-    w = event_weight(params, s["x"], s["k_init"], s["vifty"], max_r=max_r, rho_DM=rho_DM, n_maxSample=n_maxSample)
+    s = sample_conversion_points(params, n_ev, seed=seed, ray_offset=lo, max_r=max_r, halo=halo)
+    w = event_weight(params, s["x"], s["k_init"], s["vifty"], max_r=max_r, rho_DM=rho_DM, n_maxSample=n_maxSample,
+                     halo=halo)
     x = s["x"].reshape(3, n_ev).T
     k = s["k_init"].reshape(3, n_ev).T
     erg = s["erg"]
@@ -355,7 +361,8 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
 
 
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
-                             saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map):
+                             saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map,
+                             halo=None):
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
@@ -376,7 +383,7 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
     r = Engine(params).run_events(hi - lo, seed=seed, event_offset=lo, saveMode=saveMode, num_cutoff=num_cutoff,
                                   MC_nodes=MC_nodes, max_nodes=max_nodes, prob_cutoff=prob_cutoff,
                                   backtrace_cap=backtrace_cap, rho_DM=rho_DM, n_maxSample=n_maxSample, nbins=nbins,
-                                  sky_map=sky_kw, cyclotron=cyclotron, rows=True)
+                                  sky_map=sky_kw, cyclotron=cyclotron, rows=True, halo=halo)
     rows = r["rows_raw"].cpu().numpy()
     t6 = r["totals"].cpu().numpy()
     sky_shape = None if sky_kw is None else (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
@@ -546,6 +553,37 @@ def pulse_profile(sky, theta_obs, theta_axis="cos", species=PHOTON):
         prof = prof / ((2.0 / n_theta) * (2.0 * np.pi / n_phi))
     phi_edges = np.linspace(-np.pi, np.pi, n_phi + 1)
     return prof, 0.5 * (phi_edges[:-1] + phi_edges[1:])
+
+
+def line_profile(sky, theta_obs, dw_range, theta_axis="cos", species=PHOTON, phase_resolved=False):
+    """The line profile an observer at inclination theta_obs [rad] sees, pulse_profile's companion: the
+    Δω rows of the θ bin that holds theta_obs (the same bin rule: an edge belongs to the bin on its
+    right, the upper end to the last), as power per steradian per unit Δω -- divided by the solid angle
+    of what is summed and by the Δω bin width (dw_range[1] - dw_range[0]) / n_dw. By default the φ
+    bins are summed, the average over the rotation: shape (n_dw,), the solid angle the θ bin's whole
+    ring. phase_resolved: one profile per φ bin, shape (n_phi, n_dw). With theta_axis "theta" the ring
+    [θ_lo, θ_hi] spans 2π (cos θ_lo - cos θ_hi). Returns (profile, the Δω bin centres).
+    sky: (2, n_theta, n_phi, n_dw), as sky_map and run_info give it, binned over dw_range."""
+    sky = np.asarray(sky)
+    _, n_theta, n_phi, n_dw = sky.shape
+    lo, hi = _theta_range(theta_axis)
+    x = math.cos(theta_obs) if theta_axis == "cos" else float(theta_obs)
+    if not lo <= x <= hi:
+        raise ValueError(f"theta_obs = {theta_obs} lies outside the map")
+    d_lo, d_hi = float(dw_range[0]), float(dw_range[1])
+    if not (np.isfinite(d_lo) and np.isfinite(d_hi) and d_lo < d_hi):
+        raise ValueError("line_profile: dw_range needs finite lo < hi")
+    edges = np.linspace(lo, hi, n_theta + 1)
+    row = min(int(np.searchsorted(edges, x, side="right")) - 1, n_theta - 1)
+    ring = 2.0 * np.pi * ((edges[row + 1] - edges[row]) if theta_axis == "cos"
+                          else (math.cos(edges[row]) - math.cos(edges[row + 1])))
+    width = (d_hi - d_lo) / n_dw
+    if phase_resolved:
+        prof = sky[species, row] / ((ring / n_phi) * width)
+    else:
+        prof = sky[species, row].sum(axis=0) / (ring * width)
+    dw_edges = np.linspace(d_lo, d_hi, n_dw + 1)
+    return prof, 0.5 * (dw_edges[:-1] + dw_edges[1:])
 
 
 def pack_totals(flux, f_inx, sum_axion, sum_photon, n_rows, sky=None) -> np.ndarray:

@@ -454,6 +454,38 @@ int art_event_weight_device(const art_params* p, double max_r, double rho_dm, do
                             const double* x, const double* k_init, const double* vifty, double* out,
                             void* stream);
 
+/* ---- halo velocity model (beyond the reference: its sampler draws every axion at one speed) ----
+ * f_inf(u) ~ exp(-|u + v_ns|^2 / v0^2) in the star's frame: u the axion's velocity at infinity,
+ * v0 the most probable speed (the reference's 220), v_ns the star's velocity in the halo frame.
+ * With a non-NULL halo the sampler draws the speed at infinity s = v_prop sqrt(-log(1 - U[6]))
+ * per attempt (the ten uniforms are drawn as without it), vifty is u/c with u the incoming
+ * asymptote of the Newtonian Kepler orbit through the accepted point (|u| = s), and the event
+ * weight's sln_prob is the reference's expression times
+ *   F = (220/v0) (v_prop/v0)^2 exp(s^2/v_prop^2 - |u + v_ns|^2/v0^2),
+ * with vel_eng = |vifty|^2 / 2 (the reference divides by c once more; not here, so that the rows'
+ * column 12 is the line position). F is 1 for v_ns = 0, v_prop = v0 = 220.
+ * halo == NULL: the entry points without _halo, bit for bit. ART_E_INVALID before any device is
+ * touched: v0 <= 0 or not finite, a v_ns that is not finite, 0 < v_prop < v0, v_prop > 3000. */
+typedef struct art_halo {
+  double v0;       /* km/s */
+  double v_ns[3];  /* km/s */
+  double v_prop;   /* <= 0: sqrt(v0^2 + |v_ns|^2) */
+} art_halo;
+
+int art_sample_conversion_points_halo_host(const art_params* p, const art_halo* halo, double max_r, uint64_t seed,
+                                           int64_t ray_offset, int64_t n, double* x, double* k_init,
+                                           double* erg_inf, double* vifty, int32_t* weights, int32_t* attempts);
+int art_sample_conversion_points_halo_device(const art_params* p, const art_halo* halo, double max_r, uint64_t seed,
+                                             int64_t ray_offset, int64_t n, double* x, double* k_init,
+                                             double* erg_inf, double* vifty, int32_t* weights, int32_t* attempts,
+                                             void* stream);
+int art_event_weight_halo_host(const art_params* p, const art_halo* halo, double max_r, double rho_dm,
+                               double mcmc_weight, int64_t n, const double* x, const double* k_init,
+                               const double* vifty, double* out);
+int art_event_weight_halo_device(const art_params* p, const art_halo* halo, double max_r, double rho_dm,
+                                 double mcmc_weight, int64_t n, const double* x, const double* k_init,
+                                 const double* vifty, double* out, void* stream);
+
 /* ---- binned flux (plot/flux.py:38-48): histogram of the final momentum azimuth
  * φf = atan2(ky, kx) over [-π, π) in nbins bins, separately for axions (row 0) and
  * photons (row 1), weight w[i] (NULL = 1), only rays that ended without a crossing

@@ -23,8 +23,9 @@ KFn nl_propagate(int, int, bool, int, int) { return nullptr; }
 KFn nl_propagate_cyc(int, int) { return nullptr; }
 TFn nl_tail(int) { return nullptr; }
 SFn nl_sample(int, bool) { return nullptr; }
+SHFn nl_sample_halo(int, bool) { return nullptr; }
 hipError_t launch_sample(const KParams&, double, uint64_t, int64_t, int64_t, double*, double*, double*, double*, int32_t*,
-                         int32_t*, unsigned long long*, hipStream_t, int) { return hipErrorNoDevice; }
+                         int32_t*, unsigned long long*, hipStream_t, int, const HaloK*) { return hipErrorNoDevice; }
 hipError_t launch_prob(const KParams&, int64_t, const double*, const double*, const double*, int64_t, const int64_t*,
                        double*, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_flux(const KParams&, int64_t, const double*, const double*, const int32_t*, const int8_t*,
@@ -42,7 +43,7 @@ hipError_t launch_eval_rhs(const KParams&, int64_t, const double*, const double*
 hipError_t launch_eval_hamiltonian(const KParams&, int64_t, const double*, const double*, const double*, const double*,
                                    double*, double*, double*, double*, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_event_weight(const KParams&, int64_t, const double*, const double*, const double*, double, double,
-                               double, double*, hipStream_t) { return hipErrorNoDevice; }
+                               double, double*, hipStream_t, const HaloK*) { return hipErrorNoDevice; }
 hipError_t launch_eval_condition(const KParams&, int64_t, const double*, const double*, double*, hipStream_t) {
   return hipErrorNoDevice;
 }
