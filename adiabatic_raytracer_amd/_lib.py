@@ -53,11 +53,18 @@ class EventRowsOut(C.Structure):  # include/art.h art_event_rows_out
                 ("totals", C.c_void_p)]
 
 
+class EventMomentsOut(C.Structure):  # include/art.h art_event_moments_out
+    _fields_ = [("nbins", C.c_int32), ("reserved", C.c_int32), ("flux_sq", C.c_void_p), ("flux_xa", C.c_void_p),
+                ("sky", C.POINTER(SkySpec)), ("sky_sq", C.c_void_p), ("sky_xa", C.c_void_p), ("totals", C.c_void_p)]
+
+
 class ArtHalo(C.Structure):  # include/art.h art_halo
     _fields_ = [("v0", C.c_double), ("v_ns", C.c_double * 3), ("v_prop", C.c_double)]
 
 
 EVENT_TOTALS = ("rows", "photon_rows", "sum_axion", "sum_photon", "attempts_minus_1", "cyclotron_mismatches")
+# art_event_moments_out::totals
+MOMENT_TOTALS = ("events", "A1", "A2", "Q_axion", "Q_photon", "C_axion", "C_photon", "bad_nodes")
 
 
 # name -> (restype, argtypes); the test suite checks this table against include/art.h
@@ -130,6 +137,7 @@ SIGNATURES = {
     "art_event_rows_device": (C.c_int, [_P, C.POINTER(EventRowsIn), C.POINTER(EventRowsOut), _v]),
     "art_event_gather_photons_device": (C.c_int, [_P, _i64, _v, _i64, _v, _i64, _v, _v, _v, _v, _v, _v, _v,
                                                   C.POINTER(_i64), _v]),
+    "art_event_moments_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventMomentsOut), _v]),
     "art_comm_unique_id": (C.c_int, [_v]),
     "art_comm_init": (C.c_int, [_i32, _i32, _v]),
     "art_flux_allreduce": (C.c_int, [_v, _i64, _v]),

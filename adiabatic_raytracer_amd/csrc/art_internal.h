@@ -336,4 +336,17 @@ hipError_t launch_event_gather(int64_t n_nodes, const art_tree_node* nodes, cons
                                hipStream_t s);
 // rows, flux, sky map (A, cos_axis, mode as launch_sky_map_segments; sky_hist null: none) and totals in one pass
 hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_axis, int mode, hipStream_t s);
+// Event moments (art_event_moments_device; the kernels and the per-tree group-by of art_event_moments.h):
+// the inputs are an EventRowsArgs (its outputs unused); node_start (n_events + 1) the forest's ranges,
+// the tables of art_event_moments_out (sky_sq null: no sky tables) and entries, n_nodes MomentEntry of
+// scratch (16 B each).
+struct MomentEntry;
+struct EventMomentsArgs {
+  const int64_t* node_start;
+  int32_t nbins;
+  double *flux_sq, *flux_xa, *sky_sq, *sky_xa, *totals;
+  MomentEntry* entries;
+};
+hipError_t launch_event_moments(const EventRowsArgs& a, const EventMomentsArgs& m, const SkyAxes& A, int cos_axis,
+                                hipStream_t s);
 }  // namespace art

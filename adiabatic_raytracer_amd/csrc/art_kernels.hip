@@ -1135,5 +1135,9 @@ hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_a
   return hipGetLastError();
 }
 
-
 }  // namespace art
+
+// Event moments (art_event_moments_device): the header's kernels, which bin through np_hist_bin,
+// sky_bin_of, EventLoad and event_row above
+#define ART_EVENT_MOMENTS_KERNELS
+#include "art_event_moments.h"

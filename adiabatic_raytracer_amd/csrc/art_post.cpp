@@ -1,5 +1,5 @@
 // art_post.cpp -- the entry points around the propagate calls (declared in include/art.h): the
-// non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows and
+// non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows, event moments and
 // the eval entry points the tests compare against the oracle. Each checks its arguments, then
 // launches on the caller's stream (or stages through the context's pool, the *_host ones).
 #include <algorithm>
@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <string>
 
+#include "art_event_moments.h"
 #include "art_event_rows.h"
 #include "art_host.h"
 
@@ -471,6 +472,69 @@ int art_event_gather_photons_device(const art_params* p, int64_t n_events, const
   const double dt0 = std::exp(-30.0), ln_dt0 = std::log(dt0);  // art_grow_trees_device's
   HIP_OK(art::launch_event_gather(n_nodes, nodes, pos, n_events, erg, m, B, slot, dt0, ln_dt0, s));
   return ART_OK;  // (ts releases pos in the stream's order, after the gather)
+}
+
+// The second moments of a chunk's binned event power (include/art.h): one entry per node record in
+// scratch, then the per-tree group-by (art_event_moments.h), both on `stream`.
+int art_event_moments_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                             const art_event_moments_out* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
+  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
+  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
+  if (out->reserved != 0) return fail(ART_E_INVALID, "reserved must be 0");
+  if (out->nbins < 0 || out->nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
+  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
+  int cos_axis = 1;
+  if (out->sky) {
+    const art_sky_spec* spec = out->sky;
+    if (spec->theta_axis != 0 && spec->theta_axis != 1)
+      return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
+    const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
+    const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
+    const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
+    if ((rc = sky_axes(nb, lo, hi, spec->n_dw == 1, 0, &A))) return rc;  // (the tables are added to in HBM: no mode)
+    cos_axis = spec->theta_axis;
+  }
+  if (in->n_events == 0) return ART_OK;
+  if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
+  if (out->nbins > 0 && (!out->flux_sq || !out->flux_xa)) return fail(ART_E_INVALID, "flux_sq or flux_xa is NULL");
+  if (out->sky && (!out->sky_sq || !out->sky_xa)) return fail(ART_E_INVALID, "sky_sq or sky_xa is NULL");
+  if (in->n_nodes > 0 && !node_start) return fail(ART_E_INVALID, "node_start is NULL");
+  if (in->n_nodes > 0 && (!in->x || !in->k_init || !in->weight5 || !in->back || !in->back_counts || !in->nodes ||
+                          !in->counts || !in->infos))
+    return fail(ART_E_INVALID, "NULL input buffer");
+  const art_segment_out* ce = in->cyc_end;
+  if (in->cyc_slot && (in->cyc_n < 0 || (in->cyc_n > 0 && (!in->cyc_tau || !ce || !ce->x_end || !ce->k_end ||
+                                                           !ce->u7_end || !ce->tau_end || !ce->status))))
+    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0, cyc_tau and the re-run's end states");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  art::EventRowsArgs a{};
+  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
+  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
+  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
+  if (in->cyc_slot) {
+    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
+  }
+  a.mass_a = p->mass_a;
+  a.ncols = art::EVENT_COLS_SHORT;
+  art::EventMomentsArgs m{};
+  m.node_start = node_start; m.nbins = out->nbins;
+  m.flux_sq = out->flux_sq; m.flux_xa = out->flux_xa; m.totals = out->totals;
+  if (out->sky) {
+    m.sky_sq = out->sky_sq; m.sky_xa = out->sky_xa;
+  }
+  void* block = nullptr;
+  if (in->n_nodes > 0 && (rc = scratch_alloc(s, (size_t)in->n_nodes * sizeof(art::MomentEntry), &block))) return rc;
+  m.entries = (art::MomentEntry*)block;
+  const hipError_t e = art::launch_event_moments(a, m, A, cos_axis, s);
+  if (block) (void)hipFreeAsync(block, s);
+  HIP_OK(e);
+  return ART_OK;
 }
 
 int art_eval_rhs_device(const art_params* p, int64_t n, const double* u, const double* tau, const double* erg,

@@ -259,7 +259,8 @@ class Engine:
         not reproduce its node's end state is counted in totals[5]. return_bins: also each row's flat
         sky bin (int32, -1 for not counted). Returns a dict: rows ((n_rows, ncols) or None), n_rows
         (an int when rows or bins were asked for, which costs one synchronisation, else None), flux,
-        sky_hist, totals, chunk_totals (this call's part of totals), bins."""
+        sky_hist, totals, chunk_totals (this call's part of totals), bins, and cyclotron_rerun (the re-run
+        this call made, for event_moments of the same chunk; None without cyclotron)."""
         n = sample["erg"].numel()
         nn = int(forward["n_nodes"])
         ncols = 29 if saveMode > 0 else 13
@@ -276,16 +277,8 @@ class Engine:
         part = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
         out_rows = self.empty(max(nn, 1), ncols) if rows else None
         bins = self.empty(max(nn, 1), dtype=torch.int32) if return_bins else None
-        ei = _lib.EventRowsIn(n, int(event_offset), sample["x"].data_ptr(), sample["k_init"].data_ptr(),
-                              sample["attempts"].data_ptr() if sample.get("attempts") is not None else None,
-                              weight5.data_ptr(), back["nodes"].data_ptr(), back["counts"].data_ptr(),
-                              forward["nodes"].data_ptr(), nn, forward["counts"].data_ptr(), forward["infos"].data_ptr(),
-                              None, 0, None, None)
-        keep = None
-        if cyclotron:
-            keep = self._cyclotron_rerun(sample, forward, nn, n)
-            ei.cyc_slot, ei.cyc_n, ei.cyc_tau = keep["slot"].data_ptr(), keep["m"], keep["tau"].data_ptr()
-            ei.cyc_end = C.pointer(keep["end"])
+        keep = self._cyclotron_rerun(sample, forward, nn, n) if cyclotron else None
+        ei = self._event_rows_in(sample, weight5, back, forward, event_offset, keep)
         eo = _lib.EventRowsOut(ncols, nbins, _p(out_rows), nn if (rows or return_bins) else 0, _p(flux),
                                C.pointer(spec) if spec is not None else None, _p(sky_hist), _p(bins), _p(part))
         check(self.lib.art_event_rows_device(C.byref(self.cp), C.byref(ei), C.byref(eo), _stream()))
@@ -299,7 +292,52 @@ class Engine:
             out_rows = out_rows[:n_rows] if rows else None
             bins = bins[:n_rows] if return_bins else None
         return {"rows": out_rows, "n_rows": n_rows, "flux": flux, "sky_hist": sky_hist, "totals": totals,
-                "chunk_totals": part, "bins": bins}
+                "chunk_totals": part, "bins": bins, "cyclotron_rerun": keep}
+
+    def _event_rows_in(self, sample, weight5, back, forward, event_offset, rerun):
+        """art_event_rows_in of one chunk (rerun: _cyclotron_rerun's dict, or None)"""
+        ei = _lib.EventRowsIn(sample["erg"].numel(), int(event_offset), sample["x"].data_ptr(), sample["k_init"].data_ptr(),
+                              sample["attempts"].data_ptr() if sample.get("attempts") is not None else None,
+                              weight5.data_ptr(), back["nodes"].data_ptr(), back["counts"].data_ptr(),
+                              forward["nodes"].data_ptr(), int(forward["n_nodes"]), forward["counts"].data_ptr(),
+                              forward["infos"].data_ptr(), None, 0, None, None)
+        if rerun is not None:
+            ei.cyc_slot, ei.cyc_n, ei.cyc_tau = rerun["slot"].data_ptr(), rerun["m"], rerun["tau"].data_ptr()
+            ei.cyc_end = C.pointer(rerun["end"])
+        return ei
+
+    def _zero_moments(self, nbins, shape):
+        z = lambda *s: torch.zeros(*s, dtype=F64, device=self.device)  # noqa: E731
+        return {"flux_sq": z(2 * nbins), "flux_xa": z(2 * nbins), "sky_sq": z(*shape) if shape else None,
+                "sky_xa": z(*shape) if shape else None, "totals": z(len(_lib.MOMENT_TOTALS))}
+
+    def event_moments(self, sample, weight5, back, forward, *, event_offset=0, nbins=50, sky=None, moments=None,
+                      cyclotron_rerun=None) -> dict:
+        """The second moments of one chunk's binned event power (art_event_moments_device), on the current
+        stream and without a synchronisation: the arguments of event_rows for the same chunk, whose bins
+        and powers (column 8 * column 7) it takes. Per event e and bin b the content X = Σ power of e's
+        final rows in b is formed first; the tables take Q = Σ_e X² and C = Σ_e X a_e with
+        a_e = attempts[e] - 1 + e's final photon rows. Returns a dict of device tensors, float64: flux_sq,
+        flux_xa (2 nbins), sky_sq, sky_xa (the map's shape; None without sky) and totals (8: events, Σ a_e,
+        Σ a_e², Q of axions and photons over all their rows, C of axions and photons, misplaced records,
+        which must stay 0). moments: such a dict of an earlier chunk, ACCUMULATED into and returned.
+        cyclotron_rerun: event_rows' "cyclotron_rerun" of this chunk, so exp(-τ) is in the powers as it is
+        in column 8; nothing is propagated here. trees.moments_sigma turns the tables into errors."""
+        nbins = int(nbins)
+        spec = shape = None
+        if sky is not None:
+            spec, shape, _ = self._sky_spec(sky)
+        if moments is None:
+            moments = self._zero_moments(nbins, shape)
+        if moments["flux_sq"].numel() != 2 * nbins or (shape and tuple(moments["sky_sq"].shape) != shape):
+            raise ValueError("event_moments: `moments` was made for other tables")
+        ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
+        mo = _lib.EventMomentsOut(nbins, 0, _p(moments["flux_sq"]), _p(moments["flux_xa"]),
+                                  C.pointer(spec) if spec is not None else None, _p(moments["sky_sq"]) if shape else None,
+                                  _p(moments["sky_xa"]) if shape else None, _p(moments["totals"]))
+        check(self.lib.art_event_moments_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]), C.byref(mo),
+                                                _stream()))
+        return moments
 
     def _cyclotron_rerun(self, sample, forward, nn, n):
         """The final photon segments of a forward forest, packed (art_event_gather_photons_device) and run
@@ -324,7 +362,7 @@ class Engine:
 
     def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
                    max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
-                   cyclotron=False, rows=True, halo=None) -> dict:
+                   cyclotron=False, rows=True, halo=None, errors=False) -> dict:
         """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
         n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
         event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
@@ -347,6 +385,14 @@ class Engine:
         the weights carry its importance ratio; column 12 is u7_end/m_a + |vifty|²/2 of each event
         ("Halo velocity model"). None (the default): the reference's single speed, every
         row as before.
+
+        errors: also the Monte-Carlo standard errors (event_moments per chunk; DESIGN.md §3, "Monte-Carlo
+        errors"): flux_sigma (2, nbins), sky_map_sigma (the map's shape, with a sky map) and
+        sum_weight_sln_prob_sigma (2), in the units of flux, sky_map and sum_weight_sln_prob, and moments,
+        the raw tables and totals for a caller that reduces over ranks first (trees.moments_sigma). The
+        events are the independent unit, so this works with rows=False. NaN below two events or with
+        f_inx = 0. The bins of one event are correlated: the σ of a sum of bins is NOT the quadrature sum of
+        these. False (the default): exactly the keys below.
 
         Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
         or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
@@ -374,6 +420,7 @@ class Engine:
         flux = torch.zeros(2 * int(nbins), dtype=F64, device=self.device)
         totals = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
         parts = []
+        moments = None
         for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
             c = min(chunk, int(event_offset) + n_events - lo)
             s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r, halo=halo)
@@ -384,6 +431,9 @@ class Engine:
                                   max_nodes=max_nodes, prob_cutoff=prob_cutoff, seed=seed, tree_offset=lo)
             r = self.event_rows(s, w5, back, fwd, event_offset=lo, saveMode=saveMode, nbins=nbins, flux=flux,
                                 sky=sky_map, sky_hist=sky_hist, totals=totals, rows=rows, cyclotron=cyclotron)
+            if errors:
+                moments = self.event_moments(s, w5, back, fwd, event_offset=lo, nbins=nbins, sky=sky_map, moments=moments,
+                                             cyclotron_rerun=r["cyclotron_rerun"])
             if rows:
                 parts.append(r["rows"] if len(r["rows"]) * 2 >= fwd["n_nodes"] else r["rows"].clone())
         tot = totals.cpu().numpy()
@@ -406,6 +456,25 @@ class Engine:
         if sky_map is not None:
             ekw = {k: sky_kw[k] for k in ("n_theta", "n_phi", "n_dw", "theta_axis", "dw_range")}
             res.update(sky_map=sky_hist / div, sky_raw=sky_hist, sky_map_edges=sky_map_edges(**ekw))
+        if errors:
+            from .trees import moments_sigma
+            if moments is None:  # (no events)
+                moments = self._zero_moments(int(nbins), None if sky_hist is None else tuple(sky_hist.shape))
+            mt = moments["totals"].cpu().numpy()
+            if mt[7] != 0:
+                raise _lib.ArtError(f"run_events: {int(mt[7])} node records lie in the range of another tree")
+
+            def sigma(S, key, like):
+                """σ of the table S / f_inx, on the device in the shape of `like` (the tables are small: on the host)"""
+                Q, Cx = (moments[key + k].cpu().numpy().reshape(-1) for k in ("_sq", "_xa"))
+                s = moments_sigma(S.cpu().numpy().reshape(-1), Q, Cx, f_inx, mt[2], mt[0])
+                return torch.from_numpy(s).to(self.device).view(like.shape)
+
+            tot_sigma = moments_sigma(tot[2:4], mt[3:5], mt[5:7], f_inx, mt[2], mt[0])
+            res.update(flux_sigma=sigma(flux, "flux", res["flux"]), moments=moments,
+                       sum_weight_sln_prob_sigma=(float(tot_sigma[0]), float(tot_sigma[1])))
+            if sky_map is not None:
+                res["sky_map_sigma"] = sigma(sky_hist, "sky", sky_hist)
         return res
 
     # ---- pointwise physics (parity tests)

@@ -179,7 +179,7 @@ def save_node(fh, node, tr, q):
 def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_DM=0.45, n_maxSample=6,
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
-                     sky_map=None, device_trees=False, device_events=False, halo=None):
+                     sky_map=None, device_trees=False, device_events=False, halo=None, errors=False):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -233,7 +233,16 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     halo (a raytracer.Halo, beyond the reference): the events' speeds at infinity are drawn from the halo
     velocity model and their weights carry its importance ratio (sample_conversion_points, event_weight),
     on all three paths; column 12 is then u7_end/m_a + |vifty|²/2 event by event ("Halo
-    velocity model"). With the default None every row, file and run_info key is unchanged."""
+    velocity model"). With the default None every row, file and run_info key is unchanged.
+
+    errors (beyond the reference): the Monte-Carlo standard errors of the reduced estimates, on all three
+    paths: run_info["flux_sigma"] (2, nbins), ["sky_map_sigma"] (with a sky map, also saved into the
+    skymap npz) and ["sum_weight_sln_prob_sigma"] (2), by moments_sigma from per-event second moments
+    (event_moments; the event, not the row, is the independent unit) that follow the sky map in the same
+    all-reduce: σ comes from the global tables, the global f_inx and the global number of events. The
+    host paths bin the rows' own columns with numpy's rule; device_events takes the tables from
+    art_event_moments_device. With the default False every row, file, run_info key and the reduced vector
+    are unchanged."""
     if device_events:
         if saveMode > 1 and dir_tag is not None:
             raise ValueError("device_events: the text files and tree dumps of saveMode > 1 with a dir_tag need the "
@@ -242,7 +251,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                                         num_cutoff=num_cutoff, MC_nodes=MC_nodes, max_nodes=max_nodes,
                                         prob_cutoff=prob_cutoff, saveMode=saveMode, dir_tag=dir_tag, file_tag=file_tag,
                                         backtrace_cap=backtrace_cap, rank=rank, world=world, nbins=nbins, run_info=run_info,
-                                        cyclotron=cyclotron, sky_map=sky_map, halo=halo)
+                                        cyclotron=cyclotron, sky_map=sky_map, halo=halo, errors=errors)
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -333,11 +342,13 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
         sky = np.zeros(sky_shape)
         if len(rows):
             sky = _sky_map_rows(rows[:, 2], rows[:, 3], rows[:, 12], rows[:, 1], pps, **sky_kw)
+    mom = rows_moments(rows, lo, s["attempts"], nbins, sky_kw if sky_map is not None else None) if errors else None
     tot = pack_totals(flux, f_inx, pps[rows[:, 1] == 0].sum() if len(rows) else 0.0,
-                      pps[rows[:, 1] == 1].sum() if len(rows) else 0.0, len(rows), sky)
+                      pps[rows[:, 1] == 1].sum() if len(rows) else 0.0, len(rows), sky, mom)
     if world > 1:
         tot = allreduce_sum(tot)
-    tt = unpack_totals(tot, nbins, sky_shape)
+    tt = unpack_totals(tot, nbins, sky_shape, moments=errors)
+    sigma = _sigma_info(tt, nbins) if errors else {}
     f_glob = tt["f_inx"]
     if len(rows):
         rows[:, 7] /= f_glob  # saveAll[:, 8] ./= f_inx (:747), the whole run's f_inx
@@ -347,6 +358,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                         rows=int(round(tt["rows"])), events=(lo, hi), n_events=n_glob)
         if sky_map is not None:
             run_info.update(sky_map=tt["sky"] / f_glob, sky_map_edges=sky_map_edges(**sky_kw))
+        run_info.update(sigma)
     if dir_tag is not None:
         path = tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul, params.B0, Ntajs,
                               ntimes, num_cutoff, MC_nodes, max_nodes, tag)
@@ -356,13 +368,14 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
             te, pe, de = sky_map_edges(**sky_kw)
             stem = os.path.splitext(os.path.basename(path))[0]
             np.savez(os.path.join(os.path.dirname(path), f"skymap_{stem}.npz"), sky_map=tt["sky"] / f_glob,
-                     theta_edges=te, phi_edges=pe, dw_edges=de, theta_axis=sky_kw["theta_axis"], f_inx=int(round(f_glob)))
+                     theta_edges=te, phi_edges=pe, dw_edges=de, theta_axis=sky_kw["theta_axis"], f_inx=int(round(f_glob)),
+                     **({"sky_map_sigma": sigma["sky_map_sigma"]} if errors else {}))
     return rows
 
 
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
                              saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map,
-                             halo=None):
+                             halo=None, errors=False):
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
@@ -383,15 +396,17 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
     r = Engine(params).run_events(hi - lo, seed=seed, event_offset=lo, saveMode=saveMode, num_cutoff=num_cutoff,
                                   MC_nodes=MC_nodes, max_nodes=max_nodes, prob_cutoff=prob_cutoff,
                                   backtrace_cap=backtrace_cap, rho_DM=rho_DM, n_maxSample=n_maxSample, nbins=nbins,
-                                  sky_map=sky_kw, cyclotron=cyclotron, rows=True, halo=halo)
+                                  sky_map=sky_kw, cyclotron=cyclotron, rows=True, halo=halo, errors=errors)
     rows = r["rows_raw"].cpu().numpy()
     t6 = r["totals"].cpu().numpy()
     sky_shape = None if sky_kw is None else (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
     tot = pack_totals(r["flux_raw"].cpu().numpy(), t6[4] + t6[1], t6[2], t6[3], t6[0],
-                      None if sky_kw is None else r["sky_raw"].cpu().numpy())
+                      None if sky_kw is None else r["sky_raw"].cpu().numpy(),
+                      {k: (None if v is None else v.cpu().numpy()) for k, v in r["moments"].items()} if errors else None)
     if world > 1:
         tot = allreduce_sum(tot)
-    tt = unpack_totals(tot, nbins, sky_shape)
+    tt = unpack_totals(tot, nbins, sky_shape, moments=errors)
+    sigma = _sigma_info(tt, nbins) if errors else {}
     f_glob = tt["f_inx"]
     if len(rows):
         rows[:, 7] /= f_glob  # saveAll[:, 8] ./= f_inx (:747), the whole run's f_inx
@@ -401,6 +416,7 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                         rows=int(round(tt["rows"])), events=(lo, hi), n_events=n_glob)
         if sky_kw is not None:
             run_info.update(sky_map=tt["sky"] / f_glob, sky_map_edges=sky_map_edges(**sky_kw))
+        run_info.update(sigma)
     if dir_tag is not None:
         path = tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul, params.B0, Ntajs,
                               ntimes, num_cutoff, MC_nodes, max_nodes, tag)
@@ -410,7 +426,8 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
             te, pe, de = sky_map_edges(**sky_kw)
             stem = os.path.splitext(os.path.basename(path))[0]
             np.savez(os.path.join(os.path.dirname(path), f"skymap_{stem}.npz"), sky_map=tt["sky"] / f_glob,
-                     theta_edges=te, phi_edges=pe, dw_edges=de, theta_axis=sky_kw["theta_axis"], f_inx=int(round(f_glob)))
+                     theta_edges=te, phi_edges=pe, dw_edges=de, theta_axis=sky_kw["theta_axis"], f_inx=int(round(f_glob)),
+                     **({"sky_map_sigma": sigma["sky_map_sigma"]} if errors else {}))
     return rows
 
 
@@ -586,19 +603,152 @@ def line_profile(sky, theta_obs, dw_range, theta_axis="cos", species=PHOTON, pha
     return prof, 0.5 * (dw_edges[:-1] + dw_edges[1:])
 
 
-def pack_totals(flux, f_inx, sum_axion, sum_photon, n_rows, sky=None) -> np.ndarray:
+def event_moments(event, bins, power, size, trials=None):
+    """The first and second moments of binned event power, the numpy statement of
+    art_event_moments_device: event (per row, the integer id of the row's event), bins (per row, the
+    flat label in a table of `size` bins; a negative label drops the row), power (per row, column 8 *
+    column 7). The rows of one event are correlated, so per event e and bin b the content
+    X = Σ power of e's rows in b is formed first (in row order). Returns (S, Q, C), each (size,):
+    S = Σ_e X, Q = Σ_e X², C = Σ_e X a_e with a_e = trials[e], the event's part of f_inx
+    (attempts - 1 + its photon rows), indexed by the ids in `event`. trials=None, for row files, which
+    do not store the attempts: a_e is taken constant and C is None (moments_sigma's constant form)."""
+    event, bins = np.asarray(event, np.int64).reshape(-1), np.asarray(bins, np.int64).reshape(-1)
+    power = np.asarray(power, np.float64).reshape(-1)
+    size = int(size)
+    keep = bins >= 0
+    event, bins, power = event[keep], bins[keep], power[keep]
+    if bins.size and bins.max() >= size:
+        raise ValueError("event_moments: a label lies outside the table")
+    groups, inv = np.unique(event * size + bins, return_inverse=True)
+    X = np.bincount(inv.reshape(-1), weights=power, minlength=groups.size)  # (adds in row order)
+    gb, ge = groups % size, groups // size
+    S = np.bincount(gb, weights=X, minlength=size)
+    Q = np.bincount(gb, weights=X * X, minlength=size)
+    if trials is None:
+        return S, Q, None
+    a = np.asarray(trials, np.float64).reshape(-1)
+    return S, Q, np.bincount(gb, weights=X * a[ge], minlength=size)
+
+
+def moments_sigma(S, Q, C, f_inx, A2, n_events):
+    """The Monte-Carlo standard error of F = S / f_inx per bin, from event_moments' tables (or the
+    device's): F is a ratio of two sums over n_events independent events, Σ_e X_e / Σ_e a_e, and its
+    linearised (delta-method) error is
+        σ = sqrt(max(Q - 2 F C + F² A2, 0) n / (n - 1)) / f_inx,        A2 = Σ_e a_e²,
+    which is n / (n - 1) Σ_e (X_e - F a_e)² / f_inx² expanded; an event without a row in the bin adds
+    (F a_e)², carried by A2. C = None (and A2 ignored): a_e constant, the textbook
+    n / (n - 1) (Q - S² / n) / f_inx². NaN for n_events < 2 or f_inx <= 0. Under heavy-tailed weights a
+    variance estimate is biased low (the largest weights are rarely drawn): read σ as a lower scale of
+    the scatter. The bins of one event are correlated, so the σ of a sum of bins is not the quadrature
+    sum of the bins' σ."""
+    S, Q = np.asarray(S, np.float64), np.asarray(Q, np.float64)
+    n, f = float(n_events), float(f_inx)
+    if not (n >= 2 and f > 0):
+        return np.full(S.shape, np.nan)
+    if C is None:
+        var = Q - S * S / n
+    else:
+        F = S / f
+        var = Q - 2.0 * F * np.asarray(C, np.float64) + F * F * float(A2)
+    return np.sqrt(np.maximum(var, 0.0) * (n / (n - 1.0))) / f
+
+
+def hist_bins(x, nbins, lo=-np.pi, hi=np.pi) -> np.ndarray:
+    """np.histogram's bin of each x for nbins equal bins over [lo, hi]: an edge belongs to the bin on
+    its right, hi to the last; -1 outside the range and for NaN."""
+    x = np.asarray(x, np.float64)
+    edges = np.linspace(lo, hi, int(nbins) + 1)
+    i = np.searchsorted(edges, x, side="right") - 1
+    i[x == edges[-1]] = int(nbins) - 1
+    with np.errstate(invalid="ignore"):
+        return np.where((x >= lo) & (x <= hi), i, -1)
+
+
+def sky_bins(theta_f, phi_f, dw, ident, *, n_theta=32, n_phi=64, n_dw=1, theta_axis="cos", dw_range=None) -> np.ndarray:
+    """The flat sky-map label of each npy row (columns 2, 3, 12 and 1), np.histogramdd's bins of what
+    sky_map() hands the device: np.cos(θf) or θf, φf, Δω; -1 for a row the map does not count."""
+    th = np.asarray(theta_f, np.float64)
+    lo, hi = _theta_range(theta_axis)
+    ia = hist_bins(np.cos(th) if theta_axis == "cos" else th, n_theta, lo, hi)
+    ib = hist_bins(phi_f, n_phi)
+    c = np.asarray(dw, np.float64)
+    if dw_range is None:
+        if n_dw != 1:
+            raise ValueError("sky_map: n_dw > 1 needs dw_range")
+        ic = np.where(np.isfinite(c), 0, -1)
+    else:
+        ic = hist_bins(c, n_dw, float(dw_range[0]), float(dw_range[1]))
+    sp = (np.asarray(ident) != 0).astype(np.int64)
+    flat = ((sp * n_theta + ia) * n_phi + ib) * n_dw + ic
+    return np.where((ia >= 0) & (ib >= 0) & (ic >= 0), flat, -1)
+
+
+def rows_moments(rows, event_lo, attempts, nbins, sky_kw=None) -> dict:
+    """art_event_moments_device's tables in numpy from the npy rows of the events event_lo ..
+    event_lo + len(attempts) (column 7 raw or divided alike: pass the powers' own rows): flux_sq,
+    flux_xa, sky_sq, sky_xa (None without sky_kw) and totals (8), for pack_totals(moments=)."""
+    n = len(attempts)
+    ev = np.rint(rows[:, 0]).astype(np.int64) - 1 - int(event_lo)
+    sp = (rows[:, 1] != 0).astype(np.int64)
+    pps = rows[:, 8] * rows[:, 7]
+    a = np.asarray(attempts, np.int64) - 1 + np.bincount(ev[sp == 1], minlength=n)
+    fb = hist_bins(rows[:, 3], nbins)
+    _, fq, fc = event_moments(ev, np.where(fb >= 0, sp * nbins + fb, -1), pps, 2 * nbins, a)
+    _, tq, tc = event_moments(ev, sp, pps, 2, a)
+    out = {"flux_sq": fq, "flux_xa": fc, "sky_sq": None, "sky_xa": None,
+           "totals": np.array([n, a.sum(), (a * a).sum(), tq[0], tq[1], tc[0], tc[1], 0.0], np.float64)}
+    if sky_kw is not None:
+        size = 2 * sky_kw["n_theta"] * sky_kw["n_phi"] * sky_kw["n_dw"]
+        _, out["sky_sq"], out["sky_xa"] = event_moments(ev, sky_bins(rows[:, 2], rows[:, 3], rows[:, 12], rows[:, 1], **sky_kw),
+                                                        pps, size, a)
+    return out
+
+
+def pack_totals(flux, f_inx, sum_axion, sum_photon, n_rows, sky=None, moments=None) -> np.ndarray:
     """A rank's part of main_runner_tree's single all-reduce: [flux (2 nbins) | f_inx | Σ weight *
-    sln_prob (axions, photons) | rows], then the sky map's table when there is one."""
+    sln_prob (axions, photons) | rows], then the sky map's table when there is one, then with moments
+    (errors=True; a dict of event_moments' tables, all additive over the ranks) [flux_sq | flux_xa |
+    sky_sq | sky_xa (with a sky map) | totals (8)]."""
     tot = np.concatenate([flux, [float(f_inx), float(sum_axion), float(sum_photon), float(n_rows)]])
-    return tot if sky is None else np.concatenate([tot, np.asarray(sky, np.float64).reshape(-1)])
+    if sky is not None:
+        tot = np.concatenate([tot, np.asarray(sky, np.float64).reshape(-1)])
+    if moments is None:
+        return tot
+    keys = ("flux_sq", "flux_xa") + (("sky_sq", "sky_xa") if sky is not None else ()) + ("totals",)
+    return np.concatenate([tot] + [np.asarray(moments[k], np.float64).reshape(-1) for k in keys])
 
 
-def unpack_totals(tot, nbins, sky_shape=None) -> dict:
-    """The parts of a pack_totals vector (sky_shape: the map's (2, n_theta, n_phi, n_dw), or None)."""
+def unpack_totals(tot, nbins, sky_shape=None, moments=False) -> dict:
+    """The parts of a pack_totals vector (sky_shape: the map's (2, n_theta, n_phi, n_dw), or None;
+    moments: the vector ends with pack_totals' moments part, returned as a dict under "moments")."""
     m = 2 * nbins
     out = {"flux": tot[:m], "f_inx": tot[m], "sum_axion": tot[m + 1], "sum_photon": tot[m + 2], "rows": tot[m + 3]}
+    at = m + 4
+    ns = 0 if sky_shape is None else int(np.prod(sky_shape))
     if sky_shape is not None:
-        out["sky"] = tot[m + 4:m + 4 + int(np.prod(sky_shape))].reshape(sky_shape)
+        out["sky"] = tot[at:at + ns].reshape(sky_shape)
+        at += ns
+    if moments:
+        mo = {"sky_sq": None, "sky_xa": None}
+        parts = [("flux_sq", m), ("flux_xa", m)] + ([("sky_sq", ns), ("sky_xa", ns)] if sky_shape is not None else [])
+        for k, size in parts + [("totals", len(_lib.MOMENT_TOTALS))]:
+            v = tot[at:at + size]
+            mo[k] = v.reshape(sky_shape) if k.startswith("sky") else v
+            at += size
+        out["moments"] = mo
+    return out
+
+
+def _sigma_info(tt, nbins) -> dict:
+    """run_info's σ keys from the reduced totals (unpack_totals(moments=True)): the global tables, the
+    global f_inx and the global number of events"""
+    mo, f = tt["moments"], tt["f_inx"]
+    t8 = mo["totals"]
+    out = {"flux_sigma": moments_sigma(tt["flux"], mo["flux_sq"], mo["flux_xa"], f, t8[2], t8[0]).reshape(2, nbins),
+           "sum_weight_sln_prob_sigma": tuple(float(v) for v in moments_sigma(
+               np.array([tt["sum_axion"], tt["sum_photon"]]), t8[3:5], t8[5:7], f, t8[2], t8[0]))}
+    if "sky" in tt:
+        out["sky_map_sigma"] = moments_sigma(tt["sky"], mo["sky_sq"], mo["sky_xa"], f, t8[2], t8[0])
     return out
 
 

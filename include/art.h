@@ -618,6 +618,39 @@ int art_event_gather_photons_device(const art_params* p, int64_t n_events, const
                                     double* erg_out, double* dw, double* ln_t0, int8_t* species, int32_t* slot,
                                     int64_t* n_out, void* stream);
 
+/* ---- event moments: the Monte-Carlo errors of the flux table, the sky map and the totals ----
+ * The independent unit of a run is the event; the rows of one event (the leaves of one forward tree)
+ * are correlated. With p_r = column 8 * column 7 of final row r (what art_event_rows_device adds to
+ * its tables, exp(-τ) included with cyclotron) and the same bins, per event e:
+ *   a_e     = (attempts[e] - 1) + (final photon rows of e)   (Σ_e a_e is the run's f_inx; attempts
+ *             NULL: the photon rows only),
+ *   X_{e,b} = Σ p_r over e's final rows in bin b, summed in node order,
+ *   X_{e,s} = Σ p_r over all of e's final rows of species s, binned or not,
+ * and the call ADDS, per table, Q_b = Σ_e X_{e,b}² to *_sq and C_b = Σ_e X_{e,b} a_e to *_xa, each
+ * (event, bin) group once, and to totals [0] the events n, [1] A1 = Σ a_e, [2] A2 = Σ a_e²,
+ * [3], [4] Q of axions and photons, [5], [6] C of axions and photons, [7] records that lie in the range
+ * of a tree other than their own (skipped; must stay 0). All of these add over chunks and ranks.
+ * With S_b the first-moment table, f = f_inx and F_b = S_b / f, the delta-method standard error of
+ * F_b is sqrt(max(Q_b - 2 F_b C_b + F_b² A2, 0) n / (n - 1)) / f  (n >= 2, f > 0).
+ * in: art_event_rows_device's input (cyclotron fields included; cyc_end is not read).
+ * node_start (n_events + 1, device): tree e owns records node_start[e] .. node_start[e + 1], as
+ * art_grow_trees_device leaves them; required when n_nodes > 0. */
+typedef struct art_event_moments_out {
+  int32_t nbins;               /* flux bins over [-π, π], 0 .. 4096 (0: no flux tables)            */
+  int32_t reserved;            /* 0                                                                 */
+  double* flux_sq; double* flux_xa;   /* 2 nbins each: Q_b, C_b                                     */
+  const art_sky_spec* sky;     /* NULL: no sky tables; mode is ignored                              */
+  double* sky_sq;  double* sky_xa;    /* 2 n_theta n_phi n_dw each                                  */
+  double* totals;              /* 8: n, A1, A2, Q_axion, Q_photon, C_axion, C_photon, bad nodes     */
+} art_event_moments_out;
+/* Asynchronous on `stream`; its scratch (16 B per node record) comes from the stream-ordered
+ * allocator; no host synchronisation. Every table is ordinary device memory and takes float64
+ * hardware adds. ART_E_INVALID before any device is touched: art_event_rows_device's argument faults
+ * on p, in and the sky spec; reserved != 0; nbins < 0 or > 4096; a NULL node_start with n_nodes > 0;
+ * a NULL table that the call needs. n_events == 0: ART_OK, nothing touched. */
+int art_event_moments_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                             const art_event_moments_out* out, void* stream);
+
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the
  * other ranks (a file, MPI, the launcher); every rank then calls art_comm_init on its device.

@@ -121,6 +121,21 @@ int main() {
           ART_E_INVALID);
     CHECK(art_event_gather_photons_device(&p, 4, d, 0, nullptr, 4, d, d, d, d, d, nullptr, nullptr, &m, nullptr) == ART_OK &&
           m == 0);
+    // event moments: the same struct and sky checks, reserved, node_start and the tables, all before the device
+    art_event_moments_out mo{};
+    mo.nbins = 50; mo.flux_sq = mo.flux_xa = mo.totals = d;
+    ei.n_events = ei.n_nodes = 4;
+    CHECK(art_event_moments_device(&p, nullptr, nullptr, &mo, nullptr) == ART_E_INVALID);
+    CHECK(art_event_moments_device(&p, &ei, nullptr, nullptr, nullptr) == ART_E_INVALID);
+    CHECK(art_event_moments_device(&p, &ei, nullptr, &mo, nullptr) == ART_E_INVALID);  // node_start
+    mo.reserved = 1;
+    CHECK(art_event_moments_device(&p, &ei, nullptr, &mo, nullptr) == ART_E_INVALID);
+    mo.reserved = 0; mo.sky = &sk;  // n_dw = 4 without a range
+    CHECK(art_event_moments_device(&p, &ei, nullptr, &mo, nullptr) == ART_E_INVALID);
+    mo.sky = &full;  // a good spec (mode is not looked at) without its tables
+    CHECK(art_event_moments_device(&p, &ei, nullptr, &mo, nullptr) == ART_E_INVALID);
+    ei.n_events = ei.n_nodes = 0;
+    CHECK(art_event_moments_device(&p, &ei, nullptr, &mo, nullptr) == ART_OK);
   }
   // the device forest: every argument check comes before the device; with roots it reaches the HIP runtime
   {

@@ -76,6 +76,9 @@ hipError_t launch_event_gather(int64_t, const art_tree_node*, const int32_t*, in
   return hipErrorNoDevice;
 }
 hipError_t launch_event_rows(const EventRowsArgs&, const SkyAxes&, int, int, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_event_moments(const EventRowsArgs&, const EventMomentsArgs&, const SkyAxes&, int, hipStream_t) {
+  return hipErrorNoDevice;
+}
 MFn nl_eval_math(int) { return nullptr; }
 hipError_t launch_eval_math(int, int, int64_t, const double*, const double*, double*, double*, hipStream_t) {
   return hipErrorNoDevice;
