@@ -56,6 +56,21 @@ __host__ __device__ inline int moment_group(const MomentEntry* t, int64_t c, int
   return key;
 }
 
+// moment_group with the powers taken from pw[0, c), the tree's records' powers at another coupling
+// (art_event_reweight.h), in the place of the entries' own: the same groups, keys and order of adds
+__host__ __device__ inline int moment_group_scaled(const MomentEntry* t, const double* pw, int64_t c, int64_t j, int which,
+                                                   int nbins, double* X) {
+  const int key = moment_key(t[j], which, nbins);
+  if (key < 0) return -1;
+  for (int64_t i = 0; i < j; ++i)
+    if (moment_key(t[i], which, nbins) == key) return -1;
+  double x = pw[j];
+  for (int64_t i = j + 1; i < c; ++i)
+    if (moment_key(t[i], which, nbins) == key) x += pw[i];
+  *X = x;
+  return key;
+}
+
 // the final photon rows among a tree's entries: with attempts - 1 the event's a_e
 __host__ __device__ inline int64_t moment_photon_rows(const MomentEntry* t, int64_t c, int nbins) {
   int64_t m = 0;

@@ -349,4 +349,23 @@ struct EventMomentsArgs {
 };
 hipError_t launch_event_moments(const EventRowsArgs& a, const EventMomentsArgs& m, const SkyAxes& A, int cos_axis,
                                 hipStream_t s);
+// The coupling scan (art_event_reweight_device; the kernels and the per-tree reweight of
+// art_event_reweight.h): the inputs are an EventRowsArgs (its outputs unused), the forests' erg and
+// node_start; s the n_k scales (g_k / g0)². W (n_k n_nodes), B (n_k n_events) and X0 (n_nodes) are
+// caller memory or scratch; flux, sky (sky_size per coupling; null: none) and totals are art_event_reweight_out's.
+// mtotals null: no second moments; else Pw (n_k n_nodes) and entries (n_nodes) of scratch and the moment tables.
+struct EventReweightArgs {
+  const int64_t* node_start;
+  const double* erg;
+  int32_t mc_nodes, n_k, nbins;
+  int64_t sky_size;
+  double s[32];
+  double *W, *B, *Bp, *X0;  // (Bp: n_k n_events, the back factors' first factor; null: not wanted)
+  double *flux, *sky, *totals;
+  double *Pw, *flux_sq, *flux_xa, *sky_sq, *sky_xa, *mtotals;
+  MomentEntry* entries;
+};
+// P: the forward forest's parameters (g0), Pb: the backtrace's (B0 negated)
+hipError_t launch_event_reweight(const KParams& P, const KParams& Pb, const EventRowsArgs& a, const EventReweightArgs& r,
+                                 const SkyAxes& A, int cos_axis, hipStream_t s);
 }  // namespace art

@@ -1141,3 +1141,8 @@ hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_a
 // sky_bin_of, EventLoad and event_row above
 #define ART_EVENT_MOMENTS_KERNELS
 #include "art_event_moments.h"
+
+// The coupling scan (art_event_reweight_device): the header's kernels, which bin as the event rows do
+// and group as the event moments do
+#define ART_EVENT_REWEIGHT_KERNELS
+#include "art_event_reweight.h"

@@ -1,6 +1,6 @@
 // art_post.cpp -- the entry points around the propagate calls (declared in include/art.h): the
-// non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows, event moments and
-// the eval entry points the tests compare against the oracle. Each checks its arguments, then
+// non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows, event moments, the coupling
+// scan and the eval entry points the tests compare against the oracle. Each checks its arguments, then
 // launches on the caller's stream (or stages through the context's pool, the *_host ones).
 #include <algorithm>
 #include <cmath>
@@ -8,6 +8,7 @@
 #include <string>
 
 #include "art_event_moments.h"
+#include "art_event_reweight.h"
 #include "art_event_rows.h"
 #include "art_host.h"
 
@@ -533,6 +534,104 @@ int art_event_moments_device(const art_params* p, const art_event_rows_in* in, c
   m.entries = (art::MomentEntry*)block;
   const hipError_t e = art::launch_event_moments(a, m, A, cos_axis, s);
   if (block) (void)hipFreeAsync(block, s);
+  HIP_OK(e);
+  return ART_OK;
+}
+
+// The coupling scan of a chunk (include/art.h): the per-tree reweight, then the bins and, when asked
+// for, the second moments per coupling (art_event_reweight.h), all on `stream`.
+int art_event_reweight_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                              const art_tree_opts* opts, int32_t n_couplings, const double* couplings,
+                              const art_event_reweight_out* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out || !opts) return fail(ART_E_INVALID, "NULL in, out or opts");
+  if (!couplings) return fail(ART_E_INVALID, "couplings is NULL");
+  if (n_couplings < 1 || n_couplings > art::REWEIGHT_MAX_COUPLINGS)
+    return fail(ART_E_INVALID, "n_couplings must be in [1, 32]");
+  if (!(p->g_agg > 0.0) || !std::isfinite(p->g_agg)) return fail(ART_E_INVALID, "the base coupling g_agg must be finite and > 0");
+  for (int k = 0; k < n_couplings; ++k)
+    if (!(couplings[k] > 0.0) || !std::isfinite(couplings[k]))
+      return fail(ART_E_INVALID, "every coupling must be finite and > 0");
+  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
+  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
+  if (out->reserved != 0) return fail(ART_E_INVALID, "reserved must be 0");
+  if (out->nbins < 0 || out->nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
+  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
+  int cos_axis = 1;
+  int64_t sky_size = 0;
+  if (out->sky) {
+    const art_sky_spec* spec = out->sky;
+    if (spec->theta_axis != 0 && spec->theta_axis != 1)
+      return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
+    const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
+    const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
+    const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
+    if ((rc = sky_axes(nb, lo, hi, spec->n_dw == 1, 0, &A))) return rc;  // (the tables are added to in HBM: no mode)
+    cos_axis = spec->theta_axis;
+    sky_size = 2 * (int64_t)nb[0] * nb[1] * nb[2];
+  }
+  if (in->n_nodes > 0 && !node_start) return fail(ART_E_INVALID, "node_start is NULL");
+  if (in->n_events == 0) return ART_OK;
+  if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
+  if (!out->erg) return fail(ART_E_INVALID, "erg is NULL");
+  if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
+  if (out->sky && !out->sky_hist) return fail(ART_E_INVALID, "sky_hist is NULL");
+  const bool moments = out->moment_totals != nullptr;
+  if (moments && out->nbins > 0 && (!out->flux_sq || !out->flux_xa)) return fail(ART_E_INVALID, "flux_sq or flux_xa is NULL");
+  if (moments && out->sky && (!out->sky_sq || !out->sky_xa)) return fail(ART_E_INVALID, "sky_sq or sky_xa is NULL");
+  if (!in->x || !in->k_init || !in->weight5 || !in->back) return fail(ART_E_INVALID, "NULL input buffer");
+  if (in->n_nodes > 0 && (!in->back_counts || !in->nodes || !in->counts || !in->infos))
+    return fail(ART_E_INVALID, "NULL input buffer");
+  if (in->cyc_slot && (in->cyc_n < 0 || (in->cyc_n > 0 && !in->cyc_tau)))
+    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0 and cyc_tau");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  art::EventRowsArgs a{};
+  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
+  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
+  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
+  if (in->cyc_slot) {
+    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
+  }
+  a.mass_a = p->mass_a;
+  a.ncols = art::EVENT_COLS_SHORT;
+  art::EventReweightArgs r{};
+  r.node_start = node_start; r.erg = out->erg;
+  r.mc_nodes = opts->mc_nodes; r.n_k = n_couplings; r.nbins = out->nbins; r.sky_size = sky_size;
+  for (int k = 0; k < n_couplings; ++k) {
+    const double q = couplings[k] / p->g_agg;
+    r.s[k] = q * q;
+  }
+  r.flux = out->flux; r.sky = out->sky ? out->sky_hist : nullptr; r.totals = out->totals;
+  if (moments) {
+    r.flux_sq = out->flux_sq; r.flux_xa = out->flux_xa; r.mtotals = out->moment_totals;
+    if (out->sky) {
+      r.sky_sq = out->sky_sq; r.sky_xa = out->sky_xa;
+    }
+  }
+  // one block of scratch: [X0 | W | B | Pw | entries], each part a multiple of 256 bytes
+  const size_t K = (size_t)n_couplings, nn = (size_t)in->n_nodes, ne = (size_t)in->n_events;
+  auto part = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+  const size_t b_x0 = part(nn * 8), b_w = out->weights ? 0 : part(K * nn * 8), b_b = out->back ? 0 : part(K * ne * 8),
+               b_pw = moments ? part(K * nn * 8) : 0, b_en = moments ? part(nn * sizeof(art::MomentEntry)) : 0;
+  void* block = nullptr;
+  if ((rc = scratch_alloc(s, b_x0 + b_w + b_b + b_pw + b_en + 256, &block))) return rc;
+  char* at = (char*)block;
+  r.X0 = (double*)at; at += b_x0;
+  r.W = out->weights ? out->weights : (double*)at; at += b_w;
+  r.B = out->back ? out->back : (double*)at; at += b_b;
+  r.Bp = out->back_prob;
+  if (moments) {
+    r.Pw = (double*)at; at += b_pw;
+    r.entries = (art::MomentEntry*)at;
+  }
+  art_params pb = *p;
+  pb.B0 = -p->B0;  // the backtrace's field (main_runner_tree: the backtrace runs with B0 negated)
+  const hipError_t e = art::launch_event_reweight(art::make_kparams(*p), art::make_kparams(pb), a, r, A, cos_axis, s);
+  (void)hipFreeAsync(block, s);
   HIP_OK(e);
   return ART_OK;
 }

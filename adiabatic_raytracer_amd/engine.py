@@ -339,6 +339,71 @@ class Engine:
                                                 _stream()))
         return moments
 
+    def _couplings(self, couplings):
+        """The list of a coupling scan as floats, checked as art_event_reweight_device checks it"""
+        import math
+        g = [float(v) for v in couplings]
+        if not 1 <= len(g) <= _lib.REWEIGHT_MAX_COUPLINGS:
+            raise ValueError(f"couplings: 1 to {_lib.REWEIGHT_MAX_COUPLINGS} values, not {len(g)}")
+        if not all(math.isfinite(v) and v > 0.0 for v in g):
+            raise ValueError("couplings: every coupling must be finite and > 0")
+        if not (math.isfinite(self.params.g_agg) and self.params.g_agg > 0.0):
+            raise ValueError("couplings: the base coupling params.g_agg must be finite and > 0")
+        return g
+
+    def _zero_scan(self, g, nbins, shape, errors):
+        z = lambda *d: torch.zeros(*d, dtype=F64, device=self.device)  # noqa: E731
+        K = len(g)
+        scan = {"g": list(g), "flux": z(K, 2 * nbins), "sky": z(K, *shape) if shape else None,
+                "totals": z(K, len(_lib.REWEIGHT_TOTALS)), "n_events": 0}
+        if errors:
+            scan.update(flux_sq=z(K, 2 * nbins), flux_xa=z(K, 2 * nbins), sky_sq=z(K, *shape) if shape else None,
+                        sky_xa=z(K, *shape) if shape else None, moment_totals=z(K, len(_lib.MOMENT_TOTALS)))
+        return scan
+
+    def event_reweight(self, sample, weight5, back, forward, couplings, *, mc_nodes, event_offset=0, nbins=50, sky=None,
+                       errors=False, cyclotron_rerun=None, scan=None, return_weights=False) -> dict:
+        """The coupling scan of one chunk (art_event_reweight_device; DESIGN.md §3, "Coupling scan"), on the
+        current stream and without a synchronisation: the arguments of event_rows for the same chunk, whose
+        forests were grown at the base coupling g0 = params.g_agg, reweighted to every g of `couplings` (1 to
+        32 finite, positive values). mc_nodes: the forward forest's (grow_trees' mc_nodes), which says which
+        children were Monte-Carlo draws. Returns a dict of device tensors, float64, each with a leading axis
+        over the couplings: flux (K, 2 nbins), sky (K, the map's shape; None without sky), totals (K, 6:
+        Σ power of axions and of photons, coverage summed over the trees, saturated, unlinked,
+        recomputed_differs -- _lib.REWEIGHT_TOTALS), n_events (a number, summed over the chunks), and with
+        errors flux_sq, flux_xa, sky_sq, sky_xa and moment_totals (K, 8), art_event_moments_device's tables
+        per coupling. scan: such a dict of an earlier chunk, ACCUMULATED into and returned. cyclotron_rerun:
+        event_rows' "cyclotron_rerun" of this chunk, so exp(-τ) is in the powers (τ does not depend on g).
+        return_weights: also weights (K, n_nodes), W_k of every node record of THIS chunk, back
+        (K, n_events), its events' backtrace factors, and back_prob, their first factor 1 - exp(-s x_root)."""
+        g = self._couplings(couplings)
+        K, nbins = len(g), int(nbins)
+        n, nn = sample["erg"].numel(), int(forward["n_nodes"])
+        spec = shape = None
+        if sky is not None:
+            spec, shape, _ = self._sky_spec(sky)
+        if scan is None:
+            scan = self._zero_scan(g, nbins, shape, errors)
+        if (scan["g"] != g or scan["flux"].shape[1] != 2 * nbins or errors != ("moment_totals" in scan) or
+                (None if scan["sky"] is None else tuple(scan["sky"].shape[1:])) != shape):
+            raise ValueError("event_reweight: `scan` was made for other couplings or tables")
+        # (zeros: a record outside its own tree's range is written by no lane)
+        W = torch.zeros(K, max(nn, 1), dtype=F64, device=self.device) if return_weights else None
+        B = self.empty(K, max(n, 1)) if return_weights else None
+        Bp = self.empty(K, max(n, 1)) if return_weights else None
+        ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
+        mo = [_p(scan.get(k)) for k in ("flux_sq", "flux_xa", "sky_sq", "sky_xa", "moment_totals")]
+        ro = _lib.EventReweightOut(_p(sample["erg"]), nbins, 0, _p(scan["flux"]),
+                                   C.pointer(spec) if spec is not None else None, _p(scan["sky"]) if shape else None,
+                                   _p(scan["totals"]), _p(W), _p(B), _p(Bp), *mo)
+        opts = _lib.TreeOpts(0, int(mc_nodes), 0, -1, 0, 0, 0.0, 0)  # (only mc_nodes is read)
+        check(self.lib.art_event_reweight_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]), C.byref(opts),
+                                                 K, (C.c_double * K)(*g), C.byref(ro), _stream()))
+        scan["n_events"] += n
+        if return_weights:
+            scan["weights"], scan["back"], scan["back_prob"] = W[:, :nn], B[:, :n], Bp[:, :n]
+        return scan
+
     def _cyclotron_rerun(self, sample, forward, nn, n):
         """The final photon segments of a forward forest, packed (art_event_gather_photons_device) and run
         again with the cyclotron observation: slot per node, the batch size m, its tau and end states."""
@@ -362,7 +427,7 @@ class Engine:
 
     def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
                    max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
-                   cyclotron=False, rows=True, halo=None, errors=False) -> dict:
+                   cyclotron=False, rows=True, halo=None, errors=False, couplings=None) -> dict:
         """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
         n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
         event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
@@ -394,6 +459,15 @@ class Engine:
         f_inx = 0. The bins of one event are correlated: the σ of a sum of bins is NOT the quadrature sum of
         these. False (the default): exactly the keys below.
 
+        couplings (a list of 1 to 32 values of g_agg; DESIGN.md §3, "Coupling scan"): the run's forests, grown
+        at params.g_agg, are also reweighted to every coupling of the list (event_reweight per chunk), and
+        the result gets "coupling_scan", trees.scan_result's dict of host arrays: g, scale, flux (K, 2, nbins)
+        and sky_map (K, the map's shape), both divided by f_inx, sum_weight_sln_prob (K, 2), coverage (K, the
+        mean over the events), saturated, unlinked, recomputed_differs, raw (the undivided tables, for a
+        caller that reduces over ranks first) and, with errors, flux_sigma, sky_map_sigma and
+        sum_weight_sln_prob_sigma per coupling. A record without exactly one parent (unlinked != 0) is an
+        ArtError. None (the default): exactly the keys below.
+
         Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
         or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
         f_inx, sum_weight_sln_prob, n_rows, n_photon_rows, and the raw, undivided parts for a caller that
@@ -405,6 +479,8 @@ class Engine:
         n_events = int(n_events)
         if n_events < 0:
             raise ValueError("run_events: n_events must be >= 0")
+        if couplings is not None:
+            couplings = self._couplings(couplings)  # (before any work is done)
         chunk = max(1, n_events) if chunk is None else int(chunk)
         if chunk < 1:
             raise ValueError("run_events: chunk must be >= 1")
@@ -420,7 +496,7 @@ class Engine:
         flux = torch.zeros(2 * int(nbins), dtype=F64, device=self.device)
         totals = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
         parts = []
-        moments = None
+        moments = scan = None
         for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
             c = min(chunk, int(event_offset) + n_events - lo)
             s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r, halo=halo)
@@ -434,6 +510,9 @@ class Engine:
             if errors:
                 moments = self.event_moments(s, w5, back, fwd, event_offset=lo, nbins=nbins, sky=sky_map, moments=moments,
                                              cyclotron_rerun=r["cyclotron_rerun"])
+            if couplings is not None:
+                scan = self.event_reweight(s, w5, back, fwd, couplings, mc_nodes=MC_nodes, event_offset=lo, nbins=nbins,
+                                           sky=sky_map, errors=errors, cyclotron_rerun=r["cyclotron_rerun"], scan=scan)
             if rows:
                 parts.append(r["rows"] if len(r["rows"]) * 2 >= fwd["n_nodes"] else r["rows"].clone())
         tot = totals.cpu().numpy()
@@ -475,6 +554,15 @@ class Engine:
                        sum_weight_sln_prob_sigma=(float(tot_sigma[0]), float(tot_sigma[1])))
             if sky_map is not None:
                 res["sky_map_sigma"] = sigma(sky_hist, "sky", sky_hist)
+        if couplings is not None:
+            from .trees import scan_raw, scan_result
+            if scan is None:  # (no events)
+                scan = self._zero_scan(couplings, int(nbins),
+                                       None if sky_hist is None else tuple(sky_hist.shape), errors)
+            res["coupling_scan"] = scan_result(scan_raw(scan), self.params.g_agg, f_inx)
+            if res["coupling_scan"]["unlinked"] != 0:
+                raise _lib.ArtError(f"run_events: {res['coupling_scan']['unlinked']} node records of the forward "
+                                    "forest have no parent, or more than one")
         return res
 
     # ---- pointwise physics (parity tests)

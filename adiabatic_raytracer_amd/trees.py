@@ -179,7 +179,8 @@ def save_node(fh, node, tr, q):
 def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_DM=0.45, n_maxSample=6,
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
-                     sky_map=None, device_trees=False, device_events=False, halo=None, errors=False):
+                     sky_map=None, device_trees=False, device_events=False, halo=None, errors=False,
+                     couplings=None):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -242,7 +243,16 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     all-reduce: σ comes from the global tables, the global f_inx and the global number of events. The
     host paths bin the rows' own columns with numpy's rule; device_events takes the tables from
     art_event_moments_device. With the default False every row, file, run_info key and the reduced vector
-    are unchanged."""
+    are unchanged.
+
+    couplings (beyond the reference, which sweeps --Axg with one process per value; device_events only,
+    ValueError on the other two paths): a list of 1 to 32 values of g_agg to which the run's forests, grown
+    at params.g_agg, are reweighted in HBM (Engine.run_events(couplings=); DESIGN.md §3, "Coupling scan").
+    run_info["coupling_scan"] is scan_result's dict from the tables summed over the ranks, which follow
+    everything else in the same all-reduce; the rows and files are those of params.g_agg. With the default
+    None every row, file, run_info key and the reduced vector are unchanged."""
+    if couplings is not None and not device_events:
+        raise ValueError("couplings: the coupling scan reweights forests held in HBM and needs device_events=True")
     if device_events:
         if saveMode > 1 and dir_tag is not None:
             raise ValueError("device_events: the text files and tree dumps of saveMode > 1 with a dir_tag need the "
@@ -251,7 +261,8 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                                         num_cutoff=num_cutoff, MC_nodes=MC_nodes, max_nodes=max_nodes,
                                         prob_cutoff=prob_cutoff, saveMode=saveMode, dir_tag=dir_tag, file_tag=file_tag,
                                         backtrace_cap=backtrace_cap, rank=rank, world=world, nbins=nbins, run_info=run_info,
-                                        cyclotron=cyclotron, sky_map=sky_map, halo=halo, errors=errors)
+                                        cyclotron=cyclotron, sky_map=sky_map, halo=halo, errors=errors,
+                                        couplings=couplings)
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -375,7 +386,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
 
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
                              saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map,
-                             halo=None, errors=False):
+                             halo=None, errors=False, couplings=None):
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
@@ -396,16 +407,20 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
     r = Engine(params).run_events(hi - lo, seed=seed, event_offset=lo, saveMode=saveMode, num_cutoff=num_cutoff,
                                   MC_nodes=MC_nodes, max_nodes=max_nodes, prob_cutoff=prob_cutoff,
                                   backtrace_cap=backtrace_cap, rho_DM=rho_DM, n_maxSample=n_maxSample, nbins=nbins,
-                                  sky_map=sky_kw, cyclotron=cyclotron, rows=True, halo=halo, errors=errors)
+                                  sky_map=sky_kw, cyclotron=cyclotron, rows=True, halo=halo, errors=errors,
+                                  **({} if couplings is None else {"couplings": couplings}))
     rows = r["rows_raw"].cpu().numpy()
     t6 = r["totals"].cpu().numpy()
     sky_shape = None if sky_kw is None else (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
     tot = pack_totals(r["flux_raw"].cpu().numpy(), t6[4] + t6[1], t6[2], t6[3], t6[0],
                       None if sky_kw is None else r["sky_raw"].cpu().numpy(),
                       {k: (None if v is None else v.cpu().numpy()) for k, v in r["moments"].items()} if errors else None)
+    n_tot = len(tot)
+    if couplings is not None:  # the scan's raw tables follow, and only when asked for
+        tot = np.concatenate([tot, scan_pack(r["coupling_scan"]["raw"])])
     if world > 1:
         tot = allreduce_sum(tot)
-    tt = unpack_totals(tot, nbins, sky_shape, moments=errors)
+    tt = unpack_totals(tot[:n_tot], nbins, sky_shape, moments=errors)
     sigma = _sigma_info(tt, nbins) if errors else {}
     f_glob = tt["f_inx"]
     if len(rows):
@@ -417,6 +432,9 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
         if sky_kw is not None:
             run_info.update(sky_map=tt["sky"] / f_glob, sky_map_edges=sky_map_edges(**sky_kw))
         run_info.update(sigma)
+        if couplings is not None:
+            raw = scan_unpack(tot[n_tot:], r["coupling_scan"]["raw"])
+            run_info["coupling_scan"] = scan_result(raw, params.g_agg, int(round(f_glob)))
     if dir_tag is not None:
         path = tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul, params.B0, Ntajs,
                               ntimes, num_cutoff, MC_nodes, max_nodes, tag)
@@ -651,6 +669,149 @@ def moments_sigma(S, Q, C, f_inx, A2, n_events):
         F = S / f
         var = Q - 2.0 * F * np.asarray(C, np.float64) + F * F * float(A2)
     return np.sqrt(np.maximum(var, 0.0) * (n / (n - 1.0))) / f
+
+
+def reweight_nodes(nodes, node_start, x_nonad, scales, mc_nodes):
+    """The numpy statement of art_event_reweight_device's per-tree reweight (csrc/art_event_reweight.h;
+    DESIGN.md §3, "Coupling scan") over NODE_DTYPE records: tree e owns node_start[e] .. node_start[e + 1],
+    in the order it processed them. x_nonad: per record, P_nonAD at the base coupling of the record's
+    stored first crossing (xc, kc, erg |dwc|, e.g. by Engine.get_prob_nonad; read where n_cross > 0), so
+    forests saved earlier can be reweighted too. scales: (g_k / g0)². The parent of a record is the one
+    earlier record of its tree with n_cross > 0 whose (tc, xc) equal its (t0, x0) bit for bit; a child of
+    the other species takes f = 1 - exp(-s x), one of the same species exp(-s x); W(root) = 1,
+    W = f W(parent) where the parent was pop number <= mc_nodes, else W = W(parent) (f / f at s = 1).
+    A record with n_cross > 1 took its pc from the group of its segment's crossings, which one stored
+    crossing cannot give back: its exponent is -log(1 - pc) whatever x_nonad says (the grouped exponent is
+    ∝ g² too), and with pc == 1 its children keep the probabilities 1 and 0 at every scale. The device and
+    host drivers store one crossing per forward segment, so their records have n_cross <= 1.
+    Returns (W (K, n_nodes), coverage (K, trees): Σ W over each tree's records with n_cross == 0, unlinked:
+    the records without exactly one parent, whose W is 0)."""
+    nodes = np.asarray(nodes)
+    start = np.asarray(node_start, np.int64).reshape(-1)
+    s = np.asarray(scales, np.float64).reshape(-1)
+    x_nonad = np.array(x_nonad, np.float64).reshape(-1)
+    grouped = nodes["n_cross"] > 1
+    with np.errstate(divide="ignore"):
+        x_nonad[grouped] = -np.log(1.0 - nodes["pc"][grouped])  # (inf for pc == 1: exp(-s inf) = 0)
+    n, n_trees = len(nodes), len(start) - 1
+    W, cov, unlinked = np.zeros((len(s), n)), np.zeros((len(s), n_trees)), 0
+    bits = lambda v: np.ascontiguousarray(v, np.float64).view(np.uint64)  # noqa: E731
+    own = np.concatenate([bits(nodes["t0"])[:, None], bits(nodes["x0"]).reshape(n, 3)], axis=1)
+    cross = np.concatenate([bits(nodes["tc"])[:, None], bits(nodes["xc"]).reshape(n, 3)], axis=1)
+    has, species = nodes["n_cross"] > 0, nodes["species"]
+
+    def factor(converted, sv, x):
+        e = np.exp(-(sv * x))
+        return 1.0 - e if converted else e
+
+    for t in range(n_trees):
+        a, b = int(start[t]), int(start[t + 1])
+        for j in range(a, b):
+            if j == a:
+                W[:, j] = 1.0
+                continue
+            cand = a + np.flatnonzero(has[a:j] & np.all(cross[a:j] == own[j], axis=1))
+            if len(cand) != 1:
+                unlinked += 1
+                continue
+            p = int(cand[0])
+            converted = species[j] != species[p]
+            f = factor(converted, s, x_nonad[p])
+            if p - a + 1 > mc_nodes:
+                f0 = factor(converted, 1.0, x_nonad[p])
+                W[:, j] = W[:, p] * (f / f0 if f0 > 0.0 else 0.0)
+            else:
+                W[:, j] = f * W[:, p]
+        cov[:, t] = W[:, a:b][:, ~has[a:b]].sum(axis=1)
+    return W, cov, unlinked
+
+
+def reweight_back(x_root, bweight, scales, x_single=None):
+    """The backtrace factor of art_event_reweight_device per event and scale, (K, n): (1 - exp(-s x_root))
+    bweight^s, with x_root the backtrace root's P_nonAD at the base coupling and bweight the backtrace node's
+    stored weight (0 stays 0, 1 stays 1, and s = 1 takes the stored value). x_single (n, optional): the
+    exponent of the backtrace's crossing where it has exactly one (its node stores it), NaN elsewhere:
+    there bweight^s is exp(-s x_single), free of the rounding of the stored 1 - P."""
+    s = np.asarray(scales, np.float64).reshape(-1, 1)
+    x, w = np.asarray(x_root, np.float64).reshape(1, -1), np.asarray(bweight, np.float64).reshape(1, -1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = np.exp(s * np.log(w))
+    if x_single is not None:
+        xs = np.asarray(x_single, np.float64).reshape(1, -1)
+        p = np.where(np.isnan(xs), p, np.exp(-(s * np.where(np.isnan(xs), 0.0, xs))))
+    keep = (w == 0.0) | (w == 1.0) | (s == 1.0)
+    return (1.0 - np.exp(-(s * x))) * np.where(keep, w + 0.0 * s, p)
+
+
+SCAN_KEYS = ("flux", "sky", "totals", "flux_sq", "flux_xa", "sky_sq", "sky_xa", "moment_totals")
+
+
+def scan_raw(scan) -> dict:
+    """Engine.event_reweight's dict with its tables on the host (numpy): what adds over chunks and ranks"""
+    out = {k: (None if scan[k] is None else (scan[k].cpu().numpy() if hasattr(scan[k], "cpu") else np.asarray(scan[k])))
+           for k in SCAN_KEYS if k in scan}
+    out.update(g=[float(v) for v in scan["g"]], n_events=int(scan["n_events"]))
+    return out
+
+
+def scan_pack(raw) -> np.ndarray:
+    """A rank's coupling-scan tables (scan_raw) as one vector for the run's all-reduce: the tables there
+    are, in SCAN_KEYS' order, then the number of events."""
+    parts = [np.asarray(raw[k], np.float64).reshape(-1) for k in SCAN_KEYS if raw.get(k) is not None]
+    return np.concatenate(parts + [np.array([float(raw["n_events"])])])
+
+
+def scan_unpack(vec, like) -> dict:
+    """scan_pack's vector back into a dict shaped like `like` (the rank's own scan_raw)"""
+    out, at = {"g": list(like["g"])}, 0
+    for k in SCAN_KEYS:
+        if k not in like:
+            continue
+        if like[k] is None:
+            out[k] = None
+            continue
+        out[k] = np.asarray(vec[at:at + like[k].size]).reshape(like[k].shape)
+        at += like[k].size
+    out["n_events"] = int(round(vec[at]))
+    return out
+
+
+def scan_result(raw, g0, f_inx) -> dict:
+    """The coupling scan of a run from its raw tables (scan_raw, summed over the ranks) and the run's
+    f_inx: g, scale = (g / g0)² (K), flux (K, 2, nbins) and sky_map (K, the map's shape; with a map), both
+    divided by f_inx, sum_weight_sln_prob (K, 2), coverage (K: the mean over the events of Σ W_k over the
+    records that closed their tree's probability; 1 where the g0 run's stop rules cut nothing that
+    matters at g_k), saturated (events whose backtrace weight underflowed to 0 at g0), unlinked,
+    recomputed_differs, raw, and with moment tables flux_sigma, sky_map_sigma, sum_weight_sln_prob_sigma
+    per coupling (moments_sigma; the bins, a_e and f_inx are those of the g0 run for every coupling)."""
+    g = np.array(raw["g"], np.float64)
+    K, f = len(g), float(f_inx) if f_inx > 0 else 1.0
+    q = g / float(g0)
+    tot = np.asarray(raw["totals"], np.float64).reshape(K, -1)
+    nbins = raw["flux"].shape[1] // 2
+    res = {"g": g, "scale": q * q, "flux": (raw["flux"] / f).reshape(K, 2, nbins), "sum_weight_sln_prob": tot[:, 0:2] / f,
+           "coverage": tot[:, 2] / max(int(raw["n_events"]), 1), "saturated": int(round(tot[0, 3])),
+           "unlinked": int(round(tot[0, 4])), "recomputed_differs": int(round(tot[0, 5])), "f_inx": int(f_inx), "raw": raw}
+    if raw.get("sky") is not None:
+        res["sky_map"] = raw["sky"] / f
+    if raw.get("moment_totals") is not None:
+        mt = np.asarray(raw["moment_totals"], np.float64).reshape(K, -1)
+        sig = lambda S, Q, Cx, k: moments_sigma(S, Q, Cx, f_inx, mt[k, 2], mt[k, 0])  # noqa: E731
+        res["flux_sigma"] = np.stack([sig(raw["flux"][k], raw["flux_sq"][k], raw["flux_xa"][k], k)
+                                      for k in range(K)]).reshape(K, 2, nbins)
+        res["sum_weight_sln_prob_sigma"] = np.stack([sig(tot[k, 0:2], mt[k, 3:5], mt[k, 5:7], k) for k in range(K)])
+        if raw.get("sky") is not None:
+            res["sky_map_sigma"] = np.stack([sig(raw["sky"][k], raw["sky_sq"][k], raw["sky_xa"][k], k) for k in range(K)])
+    return res
+
+
+def coupling_curve(scan, species=PHOTON):
+    """(g, power, sigma or None) of a coupling scan (run_events' or run_info's "coupling_scan") for
+    plotting: the radiated power Σ weight sln_prob / f_inx of `species` at every coupling, and its
+    Monte-Carlo standard error when the scan was made with errors."""
+    sp = 0 if species == AXION else 1
+    sigma = scan.get("sum_weight_sln_prob_sigma")
+    return scan["g"], scan["sum_weight_sln_prob"][:, sp], None if sigma is None else sigma[:, sp]
 
 
 def hist_bins(x, nbins, lo=-np.pi, hi=np.pi) -> np.ndarray:

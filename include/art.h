@@ -651,6 +651,61 @@ typedef struct art_event_moments_out {
 int art_event_moments_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
                              const art_event_moments_out* out, void* stream);
 
+/* ---- coupling scan: one forest grown at the base coupling g0 = p->g_agg reweighted to many ----
+ * No ray depends on g_agg; it enters only as the factor (g 1e-9 |B|)² of P_nonAD, so at coupling g_k
+ * every crossing's exponent is s_k = (g_k / g0)² times the one at g0, and the tree weights follow
+ * through P = 1 - exp(-P_nonAD). Per forward tree (node_start's ranges, records in the order the tree
+ * processed them): the parent of a record is the one earlier record with n_cross > 0 whose (tc, xc)
+ * equal its (t0, x0) bit for bit; a child of the other species is the converted branch. With x0 the
+ * P_nonAD of the parent's stored first crossing, recomputed at g0, f_k = 1 - exp(-s_k x0) (converted)
+ * or exp(-s_k x0) (unconverted); a record with n_cross > 1 took pc from the group of its segment's
+ * crossings, so there x0 = -log(1 - pc), which is also ∝ g², and pc == 1 keeps the probabilities 1 and 0
+ * (art_grow_trees and art_grow_trees_device store one crossing per forward segment: n_cross <= 1).
+ * W_k(root) = 1, W_k = f_k W_k(parent) for a child pushed while the tree
+ * split fully (the parent was pop number <= opts->mc_nodes), W_k = W_k(parent) (f_k / f_0) for a
+ * Monte-Carlo child (f_0 at s = 1: the likelihood ratio of the drawn branch). The event's backtrace
+ * factor is B_k = (1 - exp(-s_k x_root)) bweight^s_k, x_root the backtrace root's P_nonAD (parameters
+ * with B0 negated, the sampled x, -k_init), bweight the backtrace node's stored weight (0 stays 0, 1
+ * stays 1; a backtrace with exactly one crossing stores it, and bweight^s_k is then exp(-s_k x_c) from
+ * its recomputed exponent). The power of a final row at g_k is W_k B_k [exp(-τ)] sln_prob, in art_event_rows_device's
+ * bins. Every table is ACCUMULATED into (zero it first), ordinary device memory, coupling k's part at
+ * k times the usual size. totals, 6 per coupling: [0], [1] Σ power of the axion and of the photon
+ * rows; [2] the coverage, Σ_trees Σ W_k over the records that added to tot_prob (n_cross == 0): 1 per
+ * tree explored to its end, less where the g0 run's stop rules cut what matters at g_k; [3] events
+ * with bweight == 0 plus grouped forward records with pc == 1 (`saturated`: their exponents were lost
+ * to underflow at g0); [4] records without
+ * exactly one parent (`unlinked`; their weights are 0; must stay 0); [5] recomputed probabilities,
+ * 1 - exp(-x0) against pc, the root's against back.prob and a single backtrace crossing's against its pc,
+ * that are not bit-equal. [3]-[5] do not
+ * depend on k and are repeated for each. */
+typedef struct art_event_reweight_out {
+  const double* erg;           /* n   INPUT: the forests' erg (the sampler's; art_event_rows_in has none) */
+  int32_t nbins;               /* flux bins over [-π, π], 0 .. 4096 (0: no flux table)               */
+  int32_t reserved;            /* 0                                                                   */
+  double* flux;                /* K * 2 nbins                                                         */
+  const art_sky_spec* sky;     /* NULL: no sky map; mode is ignored                                   */
+  double* sky_hist;            /* K * 2 n_theta n_phi n_dw                                            */
+  double* totals;              /* K * 6                                                               */
+  double* weights;             /* may be NULL: K * n_nodes, W_k of every record (written, not added)  */
+  double* back;                /* may be NULL: K * n_events, B_k of every event (written)             */
+  double* back_prob;           /* may be NULL: K * n_events, its first factor 1 - exp(-s_k x_root)    */
+  /* the second moments per coupling (art_event_moments_device's tables, a_e and bins those of the g0
+   * forest); moment_totals NULL: none */
+  double* flux_sq; double* flux_xa;   /* K * 2 nbins each                                            */
+  double* sky_sq;  double* sky_xa;    /* K * 2 n_theta n_phi n_dw each                               */
+  double* moment_totals;       /* K * 8 (slot 7, misplaced records, in the first coupling's only)     */
+} art_event_reweight_out;
+/* Asynchronous on `stream`, no host read; scratch (8 B per record, and per coupling 8 B per record
+ * and per event for the weights and back factors not handed out, 8 B per record more with moments)
+ * comes from the stream-ordered allocator. couplings: n_couplings values on the HOST. ART_E_INVALID
+ * before any device is touched: a NULL p, in, out, opts or couplings; n_couplings < 1 or > 32; a
+ * coupling or p->g_agg that is not finite and positive; reserved != 0; a NULL node_start or erg with
+ * nodes present; art_event_moments_device's faults on the sky spec and nbins; a NULL table that the
+ * call needs. n_events == 0: ART_OK, nothing touched. */
+int art_event_reweight_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                              const art_tree_opts* opts, int32_t n_couplings, const double* couplings,
+                              const art_event_reweight_out* out, void* stream);
+
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the
  * other ranks (a file, MPI, the launcher); every rank then calls art_comm_init on its device.

@@ -136,6 +136,42 @@ int main() {
     CHECK(art_event_moments_device(&p, &ei, nullptr, &mo, nullptr) == ART_E_INVALID);
     ei.n_events = ei.n_nodes = 0;
     CHECK(art_event_moments_device(&p, &ei, nullptr, &mo, nullptr) == ART_OK);
+    // the coupling scan: the couplings (host memory, read before the device), the base coupling, node_start,
+    // the sky spec and the tables, all before the device
+    art_event_reweight_out ro{};
+    art_tree_opts to{5, 5, 50, -1, 64, 0, 1e-10, 1769};
+    ro.erg = d; ro.nbins = 50; ro.flux = ro.totals = d;
+    double g[33];
+    for (double& v : g) v = 1e-12;
+    int64_t ns[5] = {0, 1, 2, 3, 4};
+    ei.n_events = ei.n_nodes = 4;
+    CHECK(art_event_reweight_device(nullptr, &ei, ns, &to, 2, g, &ro, nullptr) == ART_E_INVALID);
+    CHECK(art_event_reweight_device(&p, nullptr, ns, &to, 2, g, &ro, nullptr) == ART_E_INVALID);
+    CHECK(art_event_reweight_device(&p, &ei, ns, nullptr, 2, g, &ro, nullptr) == ART_E_INVALID);
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 2, g, nullptr, nullptr) == ART_E_INVALID);
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 2, nullptr, &ro, nullptr) == ART_E_INVALID);
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 0, g, &ro, nullptr) == ART_E_INVALID);
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 33, g, &ro, nullptr) == ART_E_INVALID);
+    g[31] = 0.0;  // the last of 32 is read too
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 32, g, &ro, nullptr) == ART_E_INVALID);
+    g[31] = std::nan("");
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 32, g, &ro, nullptr) == ART_E_INVALID);
+    g[31] = 1e-12;
+    art_params p0 = p;
+    p0.g_agg = 0.0;
+    CHECK(art_event_reweight_device(&p0, &ei, ns, &to, 2, g, &ro, nullptr) == ART_E_INVALID);
+    CHECK(art_event_reweight_device(&p, &ei, nullptr, &to, 2, g, &ro, nullptr) == ART_E_INVALID);  // node_start
+    ro.reserved = 1;
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 2, g, &ro, nullptr) == ART_E_INVALID);
+    ro.reserved = 0; ro.sky = &sk;  // n_dw = 4 without a range
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 2, g, &ro, nullptr) == ART_E_INVALID);
+    ro.sky = &full;  // a good spec without its table
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 2, g, &ro, nullptr) == ART_E_INVALID);
+    ro.sky = nullptr; ro.moment_totals = d;  // moments without their tables
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 2, g, &ro, nullptr) == ART_E_INVALID);
+    ro.moment_totals = nullptr;
+    ei.n_events = ei.n_nodes = 0;
+    CHECK(art_event_reweight_device(&p, &ei, nullptr, &to, 32, g, &ro, nullptr) == ART_OK);
   }
   // the device forest: every argument check comes before the device; with roots it reaches the HIP runtime
   {
