@@ -69,12 +69,22 @@ class ArtHalo(C.Structure):  # include/art.h art_halo
     _fields_ = [("v0", C.c_double), ("v_ns", C.c_double * 3), ("v_prop", C.c_double)]
 
 
+class EventHaloScanOut(C.Structure):  # include/art.h art_event_halo_scan_out
+    _fields_ = [("vifty", C.c_void_p), ("nbins", C.c_int32), ("reserved", C.c_int32), ("flux", C.c_void_p),
+                ("sky", C.POINTER(SkySpec)), ("sky_hist", C.c_void_p), ("totals", C.c_void_p), ("ratio", C.c_void_p),
+                ("flux_sq", C.c_void_p), ("flux_xa", C.c_void_p), ("sky_sq", C.c_void_p), ("sky_xa", C.c_void_p),
+                ("moment_totals", C.c_void_p)]
+
+
 EVENT_TOTALS = ("rows", "photon_rows", "sum_axion", "sum_photon", "attempts_minus_1", "cyclotron_mismatches")
 # art_event_moments_out::totals
 MOMENT_TOTALS = ("events", "A1", "A2", "Q_axion", "Q_photon", "C_axion", "C_photon", "bad_nodes")
 # art_event_reweight_out::totals, per coupling
 REWEIGHT_TOTALS = ("sum_axion", "sum_photon", "coverage", "saturated", "unlinked", "recomputed_differs")
 REWEIGHT_MAX_COUPLINGS = 32
+# art_event_halo_scan_out::totals, per model
+HALO_SCAN_TOTALS = ("sum_axion", "sum_photon", "ratio_sum", "ratio_sq", "misplaced")
+HALO_SCAN_MAX_MODELS = 32
 
 
 # name -> (restype, argtypes); the test suite checks this table against include/art.h
@@ -150,6 +160,7 @@ SIGNATURES = {
     "art_event_moments_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventMomentsOut), _v]),
     "art_event_reweight_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(TreeOpts), _i32, C.POINTER(_d),
                                             C.POINTER(EventReweightOut), _v]),
+    "art_event_halo_scan_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, _H, _i32, _H, C.POINTER(EventHaloScanOut), _v]),
     "art_comm_unique_id": (C.c_int, [_v]),
     "art_comm_init": (C.c_int, [_i32, _i32, _v]),
     "art_flux_allreduce": (C.c_int, [_v, _i64, _v]),

@@ -186,6 +186,59 @@ __global__ __launch_bounds__(256) void event_moments_kernel(const EventRowsArgs 
   }
 }
 
+// Pass B of a scan (the coupling scan's and the halo scan's moments kernels), one lane per node
+// record and per event: event_moments_kernel's group-by over pass A's entries -- the bins and a_e are
+// the run's own for every k -- with the powers of set k, r.Pw[k n_nodes + record], in the place of the
+// entries' own. Scan: r.n_k sets, r.Pw, r.sky_size and the tables r.flux_sq, r.flux_xa, r.sky_sq,
+// r.sky_xa and r.mtotals, set k's part at k times the usual size.
+template <class Scan>
+__device__ inline void moment_scan_tables(const EventRowsArgs& a, const EventMomentsArgs& m, const Scan& r) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  double ev[3] = {0.0, 0.0, 0.0};  // events, a_e, a_e²
+  if (i < a.n_events) {
+    int64_t c, first;
+    const MomentEntry* t = moment_tree(m, a.n_nodes, i, &c, &first);
+    const double ae = (double)((a.attempts ? (int64_t)a.attempts[i] - 1 : 0) + moment_photon_rows(t, c, m.nbins));
+    ev[0] = 1.0, ev[1] = ae, ev[2] = ae * ae;
+  }
+  const MomentEntry* t = nullptr;
+  int64_t c = 0, first = 0, j = -1;
+  double ae = 0.0;
+  if (i < a.n_nodes && moment_final(m.entries[i])) {
+    const int64_t e = a.nodes[i].tree;  // (an entry is final only in its own tree's range)
+    t = moment_tree(m, a.n_nodes, e, &c, &first);
+    j = i - first;
+    if (j < 0 || j >= c) j = -1;
+    else ae = (double)((a.attempts ? (int64_t)a.attempts[e] - 1 : 0) + moment_photon_rows(t, c, m.nbins));
+  }
+  for (int k = 0; k < r.n_k; ++k) {
+    double tot[EM_TOT_BAD] = {ev[0], ev[1], ev[2], 0.0, 0.0, 0.0, 0.0};
+    if (j >= 0) {
+      const double* pw = r.Pw + k * a.n_nodes + first;
+      double X;
+      for (int which = MOMENT_KEY_FLUX; which <= MOMENT_KEY_SPECIES; ++which) {
+        const int key = moment_group_scaled(t, pw, c, j, which, m.nbins, &X);
+        if (key < 0) continue;
+        if (which == MOMENT_KEY_FLUX) {
+          unsafeAtomicAdd(&r.flux_sq[(int64_t)k * 2 * m.nbins + key], X * X);
+          unsafeAtomicAdd(&r.flux_xa[(int64_t)k * 2 * m.nbins + key], X * ae);
+        } else if (which == MOMENT_KEY_SKY) {
+          unsafeAtomicAdd(&r.sky_sq[k * r.sky_size + key], X * X);
+          unsafeAtomicAdd(&r.sky_xa[k * r.sky_size + key], X * ae);
+        } else {
+          tot[EM_TOT_Q_AXION + key] = X * X;
+          tot[EM_TOT_C_AXION + key] = X * ae;
+        }
+      }
+    }
+    for (int q = 0; q < EM_TOT_BAD; ++q) {
+      double v = tot[q];
+      for (int off = warpSize / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
+      if ((threadIdx.x & (warpSize - 1)) == 0 && v != 0.0) unsafeAtomicAdd(&r.mtotals[k * EM_TOT_COUNT + q], v);
+    }
+  }
+}
+
 hipError_t launch_event_moments(const EventRowsArgs& a, const EventMomentsArgs& m, const SkyAxes& A, int cos_axis,
                                 hipStream_t s) {
   const int64_t n = a.n_nodes > a.n_events ? a.n_nodes : a.n_events;

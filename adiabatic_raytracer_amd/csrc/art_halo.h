@@ -56,4 +56,32 @@ ART_HALO_HD inline double halo_factor(const double u[3], double s, double v0, co
   return (220.0 / v0) * ((vp / v0) * (vp / v0)) * exp(e);
 }
 
+// q = |u + v_NS|²/v0², the model's exponent, summed and rounded in one fixed order
+ART_HALO_HD inline double halo_q(const double u[3], const HaloK& h) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double w0 = u[0] + h.v_ns[0], w1 = u[1] + h.v_ns[1], w2 = u[2] + h.v_ns[2];
+  return ((w0 * w0 + w1 * w1) + w2 * w2) / (h.v0 * h.v0);
+}
+
+// R = F_target / F_base = (v0_b/v0_h)³ exp(q_b - q_h): what an event drawn and weighted under `base`
+// is worth under `target` (the halo scan, art_event_haloscan.h). The s²/vp² term of halo_factor
+// cancels, so neither model's vp enters. Every operation is rounded on its own and the exponent is
+// the difference of the two q, so target == base gives exp(0) * 1 = 1.0 exactly. On the device the
+// exponential is art_core.h's fexp (a hipcc unit includes art_core.h before this header).
+ART_HALO_HD inline double halo_ratio(const double u[3], const HaloK& base, const HaloK& target) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double x = halo_q(u, base) - halo_q(u, target);
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double e = fexp(x);
+#else
+  const double e = exp(x);
+#endif
+  const double r = base.v0 / target.v0;
+  return ((r * r) * r) * e;
+}
+
 }  // namespace art

@@ -368,4 +368,23 @@ struct EventReweightArgs {
 // P: the forward forest's parameters (g0), Pb: the backtrace's (B0 negated)
 hipError_t launch_event_reweight(const KParams& P, const KParams& Pb, const EventRowsArgs& a, const EventReweightArgs& r,
                                  const SkyAxes& A, int cos_axis, hipStream_t s);
+// The halo scan (art_event_halo_scan_device; the kernels of art_event_haloscan.h): the inputs are an
+// EventRowsArgs (its outputs unused), the sampler's vifty (3 n_events, SoA) and the forest's node_start;
+// base and models[0, n_k) travel in the kernel arguments (33 x 5 doubles). R (n_k n_events) is caller
+// memory or scratch; flux, sky (sky_size per model; null: none) and totals are art_event_halo_scan_out's.
+// mtotals null: no second moments; else Pw (n_k n_nodes) and entries (n_nodes) of scratch and the moment tables.
+constexpr int HALO_SCAN_MAX_MODELS = 32;
+struct EventHaloScanArgs {
+  const int64_t* node_start;
+  const double* vifty;
+  int32_t n_k, nbins;
+  int64_t sky_size;
+  HaloK base, models[HALO_SCAN_MAX_MODELS];
+  double* R;
+  double *flux, *sky, *totals;
+  double *Pw, *flux_sq, *flux_xa, *sky_sq, *sky_xa, *mtotals;
+  MomentEntry* entries;
+};
+hipError_t launch_event_halo_scan(const EventRowsArgs& a, const EventHaloScanArgs& h, const SkyAxes& A, int cos_axis,
+                                  hipStream_t s);
 }  // namespace art

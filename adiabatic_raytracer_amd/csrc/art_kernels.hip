@@ -1146,3 +1146,8 @@ hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_a
 // and group as the event moments do
 #define ART_EVENT_REWEIGHT_KERNELS
 #include "art_event_reweight.h"
+
+// The halo scan (art_event_halo_scan_device): the header's kernels, which bin as the event rows do
+// and group as the event moments do
+#define ART_EVENT_HALOSCAN_KERNELS
+#include "art_event_haloscan.h"

@@ -1,6 +1,6 @@
 // art_post.cpp -- the entry points around the propagate calls (declared in include/art.h): the
 // non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows, event moments, the coupling
-// scan and the eval entry points the tests compare against the oracle. Each checks its arguments, then
+// scan, the halo scan and the eval entry points the tests compare against the oracle. Each checks its arguments, then
 // launches on the caller's stream (or stages through the context's pool, the *_host ones).
 #include <algorithm>
 #include <cmath>
@@ -631,6 +631,102 @@ int art_event_reweight_device(const art_params* p, const art_event_rows_in* in, 
   art_params pb = *p;
   pb.B0 = -p->B0;  // the backtrace's field (main_runner_tree: the backtrace runs with B0 negated)
   const hipError_t e = art::launch_event_reweight(art::make_kparams(*p), art::make_kparams(pb), a, r, A, cos_axis, s);
+  (void)hipFreeAsync(block, s);
+  HIP_OK(e);
+  return ART_OK;
+}
+
+// The halo scan of a chunk (include/art.h): the ratios per event and model, then the bins and, when
+// asked for, the second moments per model (art_event_haloscan.h), all on `stream`.
+int art_event_halo_scan_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                               const art_halo* base, int32_t n_models, const art_halo* models,
+                               const art_event_halo_scan_out* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
+  if (!base || !models) return fail(ART_E_INVALID, "NULL base or models");
+  if (n_models < 1 || n_models > art::HALO_SCAN_MAX_MODELS) return fail(ART_E_INVALID, "n_models must be in [1, 32]");
+  art::EventHaloScanArgs h{};
+  if ((rc = halo_of(base, &h.base))) return rc;
+  for (int k = 0; k < n_models; ++k) {
+    const art_halo& m = models[k];
+    if (!std::isfinite(m.v0) || !(m.v0 > 0.0)) return fail(ART_E_INVALID, "halo scan: every model's v0 must be finite and > 0");
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(m.v_ns[i])) return fail(ART_E_INVALID, "halo scan: every model's v_ns must be finite");
+    if (m.v0 > h.base.vp)
+      return fail(ART_E_INVALID, "halo scan: a model's v0 must be <= the base's v_prop (the weights are unbounded above it)");
+    h.models[k].v0 = m.v0;
+    for (int i = 0; i < 3; ++i) h.models[k].v_ns[i] = m.v_ns[i];
+    h.models[k].vp = h.base.vp;  // (the run's proposal; a model's own v_prop is ignored)
+  }
+  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
+  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
+  if (out->reserved != 0) return fail(ART_E_INVALID, "reserved must be 0");
+  if (out->nbins < 0 || out->nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
+  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
+  int cos_axis = 1;
+  int64_t sky_size = 0;
+  if (out->sky) {
+    const art_sky_spec* spec = out->sky;
+    if (spec->theta_axis != 0 && spec->theta_axis != 1)
+      return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
+    const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
+    const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
+    const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
+    if ((rc = sky_axes(nb, lo, hi, spec->n_dw == 1, 0, &A))) return rc;  // (the tables are added to in HBM: no mode)
+    cos_axis = spec->theta_axis;
+    sky_size = 2 * (int64_t)nb[0] * nb[1] * nb[2];
+  }
+  if (in->n_events > 0 && !out->vifty) return fail(ART_E_INVALID, "vifty is NULL");
+  if (in->n_nodes > 0 && !node_start) return fail(ART_E_INVALID, "node_start is NULL");
+  if (in->n_events == 0) return ART_OK;
+  if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
+  if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
+  if (out->sky && !out->sky_hist) return fail(ART_E_INVALID, "sky_hist is NULL");
+  const bool moments = out->moment_totals != nullptr;
+  if (moments && out->nbins > 0 && (!out->flux_sq || !out->flux_xa)) return fail(ART_E_INVALID, "flux_sq or flux_xa is NULL");
+  if (moments && out->sky && (!out->sky_sq || !out->sky_xa)) return fail(ART_E_INVALID, "sky_sq or sky_xa is NULL");
+  if (in->n_nodes > 0 && (!in->x || !in->k_init || !in->weight5 || !in->back || !in->back_counts || !in->nodes ||
+                          !in->counts || !in->infos))
+    return fail(ART_E_INVALID, "NULL input buffer");
+  if (in->cyc_slot && (in->cyc_n < 0 || (in->cyc_n > 0 && !in->cyc_tau)))
+    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0 and cyc_tau");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  art::EventRowsArgs a{};
+  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
+  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
+  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
+  if (in->cyc_slot) {
+    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
+  }
+  a.mass_a = p->mass_a;
+  a.ncols = art::EVENT_COLS_SHORT;
+  h.node_start = node_start; h.vifty = out->vifty;
+  h.n_k = n_models; h.nbins = out->nbins; h.sky_size = sky_size;
+  h.flux = out->flux; h.sky = out->sky ? out->sky_hist : nullptr; h.totals = out->totals;
+  if (moments) {
+    h.flux_sq = out->flux_sq; h.flux_xa = out->flux_xa; h.mtotals = out->moment_totals;
+    if (out->sky) {
+      h.sky_sq = out->sky_sq; h.sky_xa = out->sky_xa;
+    }
+  }
+  // one block of scratch: [R | Pw | entries], each part a multiple of 256 bytes
+  const size_t K = (size_t)n_models, nn = (size_t)in->n_nodes, ne = (size_t)in->n_events;
+  auto part = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+  const size_t b_r = out->ratio ? 0 : part(K * ne * 8), b_pw = moments ? part(K * nn * 8) : 0,
+               b_en = moments ? part(nn * sizeof(art::MomentEntry)) : 0;
+  void* block = nullptr;
+  if ((rc = scratch_alloc(s, b_r + b_pw + b_en + 256, &block))) return rc;
+  char* at = (char*)block;
+  h.R = out->ratio ? out->ratio : (double*)at; at += b_r;
+  if (moments) {
+    h.Pw = (double*)at; at += b_pw;
+    h.entries = (art::MomentEntry*)at;
+  }
+  const hipError_t e = art::launch_event_halo_scan(a, h, A, cos_axis, s);
   (void)hipFreeAsync(block, s);
   HIP_OK(e);
   return ART_OK;

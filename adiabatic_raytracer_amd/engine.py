@@ -404,6 +404,63 @@ class Engine:
             scan["weights"], scan["back"], scan["back_prob"] = W[:, :nn], B[:, :n], Bp[:, :n]
         return scan
 
+    @staticmethod
+    def _halo_key(base):
+        """(v0, v_ns, the resolved proposal scale) of the base of a halo scan"""
+        return float(base.v0), tuple(float(c) for c in base.v_ns), base.vp()
+
+    def _zero_halo_scan(self, base, models, nbins, shape, errors):
+        z = lambda *d: torch.zeros(*d, dtype=F64, device=self.device)  # noqa: E731
+        K = len(models)
+        scan = {"base": self._halo_key(base), "models": list(models),
+                "flux": z(K, 2 * nbins), "sky": z(K, *shape) if shape else None,
+                "totals": z(K, len(_lib.HALO_SCAN_TOTALS)), "n_events": 0}
+        if errors:
+            scan.update(flux_sq=z(K, 2 * nbins), flux_xa=z(K, 2 * nbins), sky_sq=z(K, *shape) if shape else None,
+                        sky_xa=z(K, *shape) if shape else None, moment_totals=z(K, len(_lib.MOMENT_TOTALS)))
+        return scan
+
+    def event_halo_scan(self, sample, weight5, back, forward, base, halos, *, event_offset=0, nbins=50, sky=None,
+                        scan=None, errors=False, return_ratio=False, cyclotron_rerun=None) -> dict:
+        """The halo scan of one chunk (art_event_halo_scan_device; DESIGN.md §3, "Halo scan"), on the current
+        stream and without a synchronisation: the arguments of event_rows for the same chunk, which was
+        sampled and weighted under the raytracer.Halo `base`, reweighted to every model of `halos` (1 to 32
+        Halo objects or (v0, v_ns) pairs; v0 at most base.vp(); a model's own v_prop is ignored). Per event
+        and model R = F_model / F_base (trees.halo_ratio) multiplies the run's own column 8 * column 7, in the
+        run's own bins. Returns a dict of device tensors, float64, each with a leading axis over the models:
+        flux (K, 2 nbins), sky (K, the map's shape; None without sky), totals (K, 5: Σ power of axions and of
+        photons, Σ_e R, Σ_e R², misplaced records -- _lib.HALO_SCAN_TOTALS), models, base, n_events (a number,
+        summed over the chunks), and with errors flux_sq, flux_xa, sky_sq, sky_xa and moment_totals (K, 8),
+        art_event_moments_device's tables per model. scan: such a dict of an earlier chunk, ACCUMULATED into
+        and returned. cyclotron_rerun: event_rows' "cyclotron_rerun" of this chunk, so exp(-τ) is in the
+        powers (τ does not depend on the halo). return_ratio: also ratio (K, n_events), R of THIS chunk."""
+        from .trees import halo_scan_models
+        models = halo_scan_models(base, halos)
+        K, nbins = len(models), int(nbins)
+        n = sample["erg"].numel()
+        spec = shape = None
+        if sky is not None:
+            spec, shape, _ = self._sky_spec(sky)
+        if scan is None:
+            scan = self._zero_halo_scan(base, models, nbins, shape, errors)
+        if (scan["models"] != models or scan["base"] != self._halo_key(base) or
+                scan["flux"].shape[1] != 2 * nbins or errors != ("moment_totals" in scan) or
+                (None if scan["sky"] is None else tuple(scan["sky"].shape[1:])) != shape):
+            raise ValueError("event_halo_scan: `scan` was made for another base, other models or other tables")
+        R = self.empty(K, max(n, 1)) if return_ratio else None
+        ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
+        mo = [_p(scan.get(k)) for k in ("flux_sq", "flux_xa", "sky_sq", "sky_xa", "moment_totals")]
+        ho = _lib.EventHaloScanOut(_p(sample["vifty"]), nbins, 0, _p(scan["flux"]),
+                                   C.pointer(spec) if spec is not None else None, _p(scan["sky"]) if shape else None,
+                                   _p(scan["totals"]), _p(R), *mo)
+        arr = (_lib.ArtHalo * K)(*[_lib.ArtHalo(v0, (C.c_double * 3)(*v), -1.0) for v0, v in models])
+        check(self.lib.art_event_halo_scan_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]),
+                                                  C.byref(base.to_c()), K, arr, C.byref(ho), _stream()))
+        scan["n_events"] += n
+        if return_ratio:
+            scan["ratio"] = R[:, :n]
+        return scan
+
     def _cyclotron_rerun(self, sample, forward, nn, n):
         """The final photon segments of a forward forest, packed (art_event_gather_photons_device) and run
         again with the cyclotron observation: slot per node, the batch size m, its tau and end states."""
@@ -427,7 +484,7 @@ class Engine:
 
     def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
                    max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
-                   cyclotron=False, rows=True, halo=None, errors=False, couplings=None) -> dict:
+                   cyclotron=False, rows=True, halo=None, errors=False, couplings=None, halos=None) -> dict:
         """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
         n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
         event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
@@ -468,6 +525,16 @@ class Engine:
         sum_weight_sln_prob_sigma per coupling. A record without exactly one parent (unlinked != 0) is an
         ArtError. None (the default): exactly the keys below.
 
+        halos (a list of 1 to 32 raytracer.Halo; needs halo=, the base; DESIGN.md §3, "Halo scan"): the run, sampled
+        and weighted under `halo`, is also reweighted to every model of the list (event_halo_scan per chunk: one
+        ratio R = F_model / F_halo per event), and the result gets "halo_scan", trees.halo_scan_result's dict of
+        host arrays: models, flux (K, 2, nbins) and sky_map (K, the map's shape), both divided by f_inx,
+        sum_weight_sln_prob (K, 2), ratio_sum and ratio_sq (K), misplaced, raw (the undivided tables) and, with
+        errors, flux_sigma, sky_map_sigma, sum_weight_sln_prob_sigma and n_eff (K) per model. A model's v0 may
+        not exceed halo.vp(): choose the base as the widest model, with a v_prop that covers the targets.
+        couplings= in the same run scans the couplings at the base halo and the halos at the base coupling.
+        None (the default): exactly the keys below.
+
         Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
         or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
         f_inx, sum_weight_sln_prob, n_rows, n_photon_rows, and the raw, undivided parts for a caller that
@@ -475,7 +542,9 @@ class Engine:
         Σ (attempts - 1), cyclotron mismatches), flux_raw, sky_raw, rows_raw (column 7 undivided; the
         tensor `rows` is a divided copy of)."""
         from dataclasses import replace
-        from .trees import AXION, PHOTON, sky_map_edges
+        from .trees import AXION, PHOTON, halo_scan_models, sky_map_edges
+        if halos is not None:
+            halos = halo_scan_models(halo, halos)  # (before any work is done)
         n_events = int(n_events)
         if n_events < 0:
             raise ValueError("run_events: n_events must be >= 0")
@@ -496,7 +565,7 @@ class Engine:
         flux = torch.zeros(2 * int(nbins), dtype=F64, device=self.device)
         totals = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
         parts = []
-        moments = scan = None
+        moments = scan = hscan = None
         for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
             c = min(chunk, int(event_offset) + n_events - lo)
             s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r, halo=halo)
@@ -513,6 +582,9 @@ class Engine:
             if couplings is not None:
                 scan = self.event_reweight(s, w5, back, fwd, couplings, mc_nodes=MC_nodes, event_offset=lo, nbins=nbins,
                                            sky=sky_map, errors=errors, cyclotron_rerun=r["cyclotron_rerun"], scan=scan)
+            if halos is not None:
+                hscan = self.event_halo_scan(s, w5, back, fwd, halo, halos, event_offset=lo, nbins=nbins, sky=sky_map,
+                                             errors=errors, cyclotron_rerun=r["cyclotron_rerun"], scan=hscan)
             if rows:
                 parts.append(r["rows"] if len(r["rows"]) * 2 >= fwd["n_nodes"] else r["rows"].clone())
         tot = totals.cpu().numpy()
@@ -563,6 +635,15 @@ class Engine:
             if res["coupling_scan"]["unlinked"] != 0:
                 raise _lib.ArtError(f"run_events: {res['coupling_scan']['unlinked']} node records of the forward "
                                     "forest have no parent, or more than one")
+        if halos is not None:
+            from .trees import halo_scan_raw, halo_scan_result
+            if hscan is None:  # (no events)
+                hscan = self._zero_halo_scan(halo, halos, int(nbins),
+                                             None if sky_hist is None else tuple(sky_hist.shape), errors)
+            res["halo_scan"] = halo_scan_result(halo_scan_raw(hscan), f_inx)
+            if res["halo_scan"]["misplaced"] != 0:
+                raise _lib.ArtError(f"run_events: {res['halo_scan']['misplaced']} node records lie in the range of "
+                                    "another tree")
         return res
 
     # ---- pointwise physics (parity tests)

@@ -180,7 +180,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
                      sky_map=None, device_trees=False, device_events=False, halo=None, errors=False,
-                     couplings=None):
+                     couplings=None, halos=None):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -250,9 +250,20 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     at params.g_agg, are reweighted in HBM (Engine.run_events(couplings=); DESIGN.md §3, "Coupling scan").
     run_info["coupling_scan"] is scan_result's dict from the tables summed over the ranks, which follow
     everything else in the same all-reduce; the rows and files are those of params.g_agg. With the default
-    None every row, file, run_info key and the reduced vector are unchanged."""
+    None every row, file, run_info key and the reduced vector are unchanged.
+
+    halos (beyond the reference; device_events only, ValueError on the other two paths; needs halo=, the base): a
+    list of 1 to 32 raytracer.Halo to which the run, sampled and weighted under `halo`, is reweighted in HBM
+    (Engine.run_events(halos=); DESIGN.md §3, "Halo scan"). run_info["halo_scan"] is halo_scan_result's dict from
+    the tables summed over the ranks, which follow everything else in the same all-reduce; the rows and files
+    are those of `halo`. With the default None every row, file, run_info key and the reduced vector are
+    unchanged."""
     if couplings is not None and not device_events:
         raise ValueError("couplings: the coupling scan reweights forests held in HBM and needs device_events=True")
+    if halos is not None:
+        if not device_events:
+            raise ValueError("halos: the halo scan reweights a run held in HBM and needs device_events=True")
+        halos = halo_scan_models(halo, halos)
     if device_events:
         if saveMode > 1 and dir_tag is not None:
             raise ValueError("device_events: the text files and tree dumps of saveMode > 1 with a dir_tag need the "
@@ -262,7 +273,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                                         prob_cutoff=prob_cutoff, saveMode=saveMode, dir_tag=dir_tag, file_tag=file_tag,
                                         backtrace_cap=backtrace_cap, rank=rank, world=world, nbins=nbins, run_info=run_info,
                                         cyclotron=cyclotron, sky_map=sky_map, halo=halo, errors=errors,
-                                        couplings=couplings)
+                                        couplings=couplings, halos=halos)
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -386,7 +397,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
 
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
                              saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map,
-                             halo=None, errors=False, couplings=None):
+                             halo=None, errors=False, couplings=None, halos=None):
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
@@ -408,7 +419,8 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                                   MC_nodes=MC_nodes, max_nodes=max_nodes, prob_cutoff=prob_cutoff,
                                   backtrace_cap=backtrace_cap, rho_DM=rho_DM, n_maxSample=n_maxSample, nbins=nbins,
                                   sky_map=sky_kw, cyclotron=cyclotron, rows=True, halo=halo, errors=errors,
-                                  **({} if couplings is None else {"couplings": couplings}))
+                                  **({} if couplings is None else {"couplings": couplings}),
+                                  **({} if halos is None else {"halos": halos}))
     rows = r["rows_raw"].cpu().numpy()
     t6 = r["totals"].cpu().numpy()
     sky_shape = None if sky_kw is None else (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
@@ -418,6 +430,9 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
     n_tot = len(tot)
     if couplings is not None:  # the scan's raw tables follow, and only when asked for
         tot = np.concatenate([tot, scan_pack(r["coupling_scan"]["raw"])])
+    n_cs = len(tot)
+    if halos is not None:  # then the halo scan's, likewise
+        tot = np.concatenate([tot, halo_scan_pack(r["halo_scan"]["raw"])])
     if world > 1:
         tot = allreduce_sum(tot)
     tt = unpack_totals(tot[:n_tot], nbins, sky_shape, moments=errors)
@@ -433,8 +448,11 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
             run_info.update(sky_map=tt["sky"] / f_glob, sky_map_edges=sky_map_edges(**sky_kw))
         run_info.update(sigma)
         if couplings is not None:
-            raw = scan_unpack(tot[n_tot:], r["coupling_scan"]["raw"])
+            raw = scan_unpack(tot[n_tot:n_cs], r["coupling_scan"]["raw"])
             run_info["coupling_scan"] = scan_result(raw, params.g_agg, int(round(f_glob)))
+        if halos is not None:
+            raw = halo_scan_unpack(tot[n_cs:], r["halo_scan"]["raw"])
+            run_info["halo_scan"] = halo_scan_result(raw, int(round(f_glob)))
     if dir_tag is not None:
         path = tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul, params.B0, Ntajs,
                               ntimes, num_cutoff, MC_nodes, max_nodes, tag)
@@ -812,6 +830,137 @@ def coupling_curve(scan, species=PHOTON):
     sp = 0 if species == AXION else 1
     sigma = scan.get("sum_weight_sln_prob_sigma")
     return scan["g"], scan["sum_weight_sln_prob"][:, sp], None if sigma is None else sigma[:, sp]
+
+
+C_KM = 2.99792e5  # art_core.h's: vifty is u / c
+
+
+def _halo_of(h):
+    """(v0, (vx, vy, vz)) of a raytracer.Halo or of such a pair"""
+    v0, v = (h.v0, h.v_ns) if hasattr(h, "v0") else h
+    v = tuple(float(c) for c in v)
+    if len(v) != 3:
+        raise ValueError("halos: v_ns has three components")
+    return float(v0), v
+
+
+def halo_scan_models(base, halos) -> list:
+    """The model list of a halo scan as [(v0, (vx, vy, vz)), ...], checked as art_event_halo_scan_device
+    checks it (ValueError "halos: ..."): base, the raytracer.Halo the run is sampled and weighted with (None:
+    there is nothing to reweight), 1 to 32 models, each v0 finite and positive and not above the base's
+    proposal scale base.vp() -- beyond it a model's weights are unbounded in the drawn speed -- and each
+    v_ns finite. A model's own v_prop plays no part."""
+    if base is None:
+        raise ValueError("halos: a halo scan reweights a run made with a halo model and needs halo=")
+    models = [_halo_of(h) for h in halos]
+    if not 1 <= len(models) <= _lib.HALO_SCAN_MAX_MODELS:
+        raise ValueError(f"halos: 1 to {_lib.HALO_SCAN_MAX_MODELS} models, not {len(models)}")
+    vp = base.vp()
+    for v0, v in models:
+        if not (math.isfinite(v0) and v0 > 0.0 and all(math.isfinite(c) for c in v)):
+            raise ValueError("halos: every model needs a finite v0 > 0 and a finite v_ns")
+        if v0 > vp:
+            raise ValueError(f"halos: a model's v0 = {v0} exceeds the base's proposal scale {vp} (its weights are "
+                             "unbounded under that proposal: give the base a larger v_prop)")
+    return models
+
+
+def halo_ratio(vifty, base, halos) -> np.ndarray:
+    """The numpy statement of art_halo.h's halo_ratio, in its order of operations: R (K, n) of the n events
+    whose sampler output vifty (3n, SoA: u / c) was drawn and weighted under `base`, for each model of
+    `halos` (raytracer.Halo objects or (v0, v_ns) pairs):
+        R = ((r r) r) exp(q_b - q_h),  r = v0_b / v0_h,  q = ((w0² + w1²) + w2²) / (v0 v0),  w = u + v_ns,
+    with u = vifty C_KM. The proposal scale cancels. A model equal to the base gives exactly 1.0."""
+    u = np.asarray(vifty, np.float64).reshape(3, -1) * C_KM
+
+    def q(h):
+        v0, v = h
+        w0, w1, w2 = u[0] + v[0], u[1] + v[1], u[2] + v[2]
+        return ((w0 * w0 + w1 * w1) + w2 * w2) / (v0 * v0)
+
+    b = _halo_of(base)
+    qb = q(b)
+    out = np.empty((len(halos), u.shape[1]))
+    for k, h in enumerate(halos):
+        h = _halo_of(h)
+        r = b[0] / h[0]
+        out[k] = ((r * r) * r) * np.exp(qb - q(h))
+    return out
+
+
+def halo_scan_tables(rows_raw, ratio, nbins, sky_kw=None, event_lo=0) -> dict:
+    """art_event_halo_scan_device's first-moment tables in numpy from the run's own rows (column 7 raw) and
+    the ratios R (K, n_events) of the events event_lo .. event_lo + n_events: the power of a row under model
+    k is column 8 * column 7 times R[k, its event], binned as the run's own tables are (hist_bins of column
+    3, sky_bins). Returns flux (K, 2 nbins), sky (K, 2 n_theta n_phi n_dw; None without sky_kw) and totals
+    (K, 2: Σ power of the axion and of the photon rows)."""
+    rows, R = np.asarray(rows_raw, np.float64), np.atleast_2d(np.asarray(ratio, np.float64))
+    K, nbins = R.shape[0], int(nbins)
+    ev = np.rint(rows[:, 0]).astype(np.int64) - 1 - int(event_lo)
+    sp = (rows[:, 1] != 0).astype(np.int64)
+    p = rows[:, 8] * rows[:, 7]
+    fb = hist_bins(rows[:, 3], nbins) if nbins > 0 else np.full(len(rows), -1)
+    labels = [("flux", np.where(fb >= 0, sp * nbins + fb, -1), 2 * nbins), ("totals", sp, 2)]
+    out = {"sky": None}
+    if sky_kw is not None:
+        kw = {k: sky_kw[k] for k in ("n_theta", "n_phi", "n_dw", "theta_axis", "dw_range") if k in sky_kw}
+        size = 2 * kw.get("n_theta", 32) * kw.get("n_phi", 64) * kw.get("n_dw", 1)
+        labels.append(("sky", sky_bins(rows[:, 2], rows[:, 3], rows[:, 12], rows[:, 1], **kw), size))
+    for name, lab, size in labels:
+        keep = lab >= 0
+        out[name] = np.stack([np.bincount(lab[keep], weights=(p * R[k, ev])[keep], minlength=size) for k in range(K)])
+    return out
+
+
+def halo_scan_raw(scan) -> dict:
+    """Engine.event_halo_scan's dict with its tables on the host (numpy): what adds over chunks and ranks"""
+    out = {k: (None if scan[k] is None else (scan[k].cpu().numpy() if hasattr(scan[k], "cpu") else np.asarray(scan[k])))
+           for k in SCAN_KEYS if k in scan}
+    out.update(models=[_halo_of(h) for h in scan["models"]], n_events=int(scan["n_events"]))
+    return out
+
+
+def halo_scan_pack(raw) -> np.ndarray:
+    """A rank's halo-scan tables (halo_scan_raw) as one vector for the run's all-reduce: scan_pack's layout"""
+    return scan_pack(raw)
+
+
+def halo_scan_unpack(vec, like) -> dict:
+    """halo_scan_pack's vector back into a dict shaped like `like` (the rank's own halo_scan_raw)"""
+    out = scan_unpack(vec, dict(like, g=()))
+    del out["g"]
+    out["models"] = list(like["models"])
+    return out
+
+
+def halo_scan_result(raw, f_inx) -> dict:
+    """The halo scan of a run from its raw tables (halo_scan_raw, summed over the ranks) and the run's f_inx:
+    models, flux (K, 2, nbins) and sky_map (K, the map's shape; with a map; pulse_profile and line_profile
+    take sky_map[k]), both divided by f_inx, sum_weight_sln_prob (K, 2), ratio_sum and ratio_sq (K: Σ_e R and
+    Σ_e R² over the events), misplaced (records outside their tree's range, which must be 0), f_inx, raw, and
+    with moment tables flux_sigma, sky_map_sigma and sum_weight_sln_prob_sigma per model (moments_sigma; the
+    bins, a_e and f_inx are the run's own for every model) and n_eff (K) = S_photon² / Q_photon, the Kish
+    effective number of events behind the photon total: a small n_eff says the model lies far from the base."""
+    models = list(raw["models"])
+    K, f = len(models), float(f_inx) if f_inx > 0 else 1.0
+    tot = np.asarray(raw["totals"], np.float64).reshape(K, -1)
+    nbins = raw["flux"].shape[1] // 2
+    res = {"models": models, "flux": (raw["flux"] / f).reshape(K, 2, nbins), "sum_weight_sln_prob": tot[:, 0:2] / f,
+           "ratio_sum": tot[:, 2].copy(), "ratio_sq": tot[:, 3].copy(), "misplaced": int(round(tot[0, 4])),
+           "f_inx": int(f_inx), "raw": raw}
+    if raw.get("sky") is not None:
+        res["sky_map"] = raw["sky"] / f
+    if raw.get("moment_totals") is not None:
+        mt = np.asarray(raw["moment_totals"], np.float64).reshape(K, -1)
+        sig = lambda S, Q, Cx, k: moments_sigma(S, Q, Cx, f_inx, mt[k, 2], mt[k, 0])  # noqa: E731
+        res["flux_sigma"] = np.stack([sig(raw["flux"][k], raw["flux_sq"][k], raw["flux_xa"][k], k)
+                                      for k in range(K)]).reshape(K, 2, nbins)
+        res["sum_weight_sln_prob_sigma"] = np.stack([sig(tot[k, 0:2], mt[k, 3:5], mt[k, 5:7], k) for k in range(K)])
+        if raw.get("sky") is not None:
+            res["sky_map_sigma"] = np.stack([sig(raw["sky"][k], raw["sky_sq"][k], raw["sky_xa"][k], k) for k in range(K)])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res["n_eff"] = tot[:, 1] * tot[:, 1] / mt[:, 4]
+    return res
 
 
 def hist_bins(x, nbins, lo=-np.pi, hi=np.pi) -> np.ndarray:

@@ -706,6 +706,46 @@ int art_event_reweight_device(const art_params* p, const art_event_rows_in* in, 
                               const art_tree_opts* opts, int32_t n_couplings, const double* couplings,
                               const art_event_reweight_out* out, void* stream);
 
+/* ---- halo scan: one run drawn and weighted under a base halo model reweighted to many ----
+ * With a halo model the sampler takes only the proposal scale v_prop and the integrator sees the drawn
+ * speed through erg; v0 and v_ns enter only in the factor F of sln_prob. Two runs with the same seed and
+ * the same v_prop draw the same events, grow the same forests and write the same rows but for column 7,
+ * so a target model h seen from the run of the base model b is one scalar per event,
+ *   R_h = F_h / F_b = (v0_b/v0_h)^3 exp(|u + v_b|^2/v0_b^2 - |u + v_h|^2/v0_h^2),   u = c vifty,
+ * and the power of a final row under h is the run's own column 8 * column 7 (exp(-tau) included with the
+ * cyclotron fields of `in`) times R_h of its event, in art_event_rows_device's bins. Column 12, the line
+ * position, does not depend on the model. `base` must be the halo the run was sampled and weighted
+ * with (its v_prop resolved as there); a model's own v_prop is ignored. Every table is ACCUMULATED into
+ * (zero it first), ordinary device memory, model k's part at k times the usual size. */
+typedef struct art_event_halo_scan_out {
+  const double* vifty;         /* 3n INPUT: the sampler's vifty (SoA), the one the base run was weighted with */
+  int32_t nbins;               /* flux bins over [-π, π], 0 .. 4096 (0: no flux table)               */
+  int32_t reserved;            /* 0                                                                   */
+  double* flux;                /* K * 2 nbins                                                         */
+  const art_sky_spec* sky;     /* NULL: no sky map; mode is ignored                                   */
+  double* sky_hist;            /* K * 2 n_theta n_phi n_dw                                            */
+  double* totals;              /* K * 5: Σ power of the axion rows, of the photon rows, Σ_e R, Σ_e R²,
+                                  records outside their tree's range (must stay 0; repeated for each k) */
+  double* ratio;               /* may be NULL: K * n_events, R of every event (written, not added)    */
+  /* the second moments per model (art_event_moments_device's tables, a_e and bins the run's own);
+   * moment_totals NULL: none */
+  double* flux_sq; double* flux_xa;   /* K * 2 nbins each                                            */
+  double* sky_sq;  double* sky_xa;    /* K * 2 n_theta n_phi n_dw each                               */
+  double* moment_totals;       /* K * 8 (slot 7, misplaced records, in the first model's only)        */
+} art_event_halo_scan_out;
+/* Asynchronous on `stream`, no host read; the base and the models (HOST memory) travel in the kernel
+ * arguments; scratch (per model 8 B per event for the ratios not handed out, and with moments 8 B per
+ * record per model and 16 B per record) comes from the stream-ordered allocator. ART_E_INVALID before
+ * any device is touched: a NULL p, in, out, base or models; n_models < 1 or > 32; a base that the
+ * sampler would refuse; a model whose v0 is not finite and positive or whose v_ns is not finite; a
+ * model with v0 above the base's resolved v_prop (its weights are unbounded in the drawn speed under that
+ * proposal); reserved != 0; art_event_moments_device's faults on nbins and the sky spec; a NULL vifty
+ * with events or a NULL node_start with nodes present; a NULL table that the call needs.
+ * n_events == 0: ART_OK, nothing touched. */
+int art_event_halo_scan_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                               const art_halo* base, int32_t n_models, const art_halo* models,
+                               const art_event_halo_scan_out* out, void* stream);
+
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the
  * other ranks (a file, MPI, the launcher); every rank then calls art_comm_init on its device.

@@ -172,6 +172,42 @@ int main() {
     ro.moment_totals = nullptr;
     ei.n_events = ei.n_nodes = 0;
     CHECK(art_event_reweight_device(&p, &ei, nullptr, &to, 32, g, &ro, nullptr) == ART_OK);
+    // the halo scan: the base and the models (host memory, every one of n_models read before the device),
+    // node_start, vifty, the sky spec and the tables, all before the device
+    art_event_halo_scan_out ho{};
+    ho.vifty = d; ho.nbins = 50; ho.flux = ho.totals = d;
+    const art_halo hb{260.0, {0.0, 230.0, 0.0}, -1.0};
+    art_halo hm[33];
+    for (art_halo& v : hm) v = art_halo{220.0, {0.0, 230.0, 0.0}, -1.0};
+    ei.n_events = ei.n_nodes = 4;
+    CHECK(art_event_halo_scan_device(nullptr, &ei, ns, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID);
+    CHECK(art_event_halo_scan_device(&p, nullptr, ns, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID);
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, nullptr, 2, hm, &ho, nullptr) == ART_E_INVALID);
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, nullptr, &ho, nullptr) == ART_E_INVALID);
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, hm, nullptr, nullptr) == ART_E_INVALID);
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 0, hm, &ho, nullptr) == ART_E_INVALID);
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 33, hm, &ho, nullptr) == ART_E_INVALID);
+    hm[31].v0 = 400.0;  // the last of 32 is read too: above the base's resolved v_prop
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 32, hm, &ho, nullptr) == ART_E_INVALID);
+    hm[31].v0 = 220.0; hm[31].v_ns[2] = std::nan("");
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 32, hm, &ho, nullptr) == ART_E_INVALID);
+    hm[31].v_ns[2] = 0.0;
+    const art_halo bad_base{260.0, {0.0, 230.0, 0.0}, 100.0};  // v_prop below v0
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &bad_base, 2, hm, &ho, nullptr) == ART_E_INVALID);
+    CHECK(art_event_halo_scan_device(&p, &ei, nullptr, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID);  // node_start
+    ho.vifty = nullptr;
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID);
+    ho.vifty = d; ho.reserved = 1;
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID);
+    ho.reserved = 0; ho.sky = &sk;  // n_dw = 4 without a range
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID);
+    ho.sky = &full;  // a good spec without its table
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID);
+    ho.sky = nullptr; ho.moment_totals = d;  // moments without their tables
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID);
+    ho.moment_totals = nullptr;
+    ei.n_events = ei.n_nodes = 0;
+    CHECK(art_event_halo_scan_device(&p, &ei, nullptr, &hb, 32, hm, &ho, nullptr) == ART_OK);
   }
   // the device forest: every argument check comes before the device; with roots it reaches the HIP runtime
   {
