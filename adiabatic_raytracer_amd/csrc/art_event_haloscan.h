@@ -130,18 +130,7 @@ hipError_t launch_event_halo_scan(const EventRowsArgs& a, const EventHaloScanArg
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (!h.mtotals) return hipSuccess;
-  EventMomentsArgs m{};
-  m.node_start = h.node_start; m.nbins = h.nbins; m.entries = h.entries;
-  m.sky_sq = h.sky_sq;   // (pass A reads it as "there is a sky table" only)
-  m.totals = h.mtotals;  // (pass A's misplaced records: slot 7 of the first model)
-  if (a.n_nodes > 0) {
-    hipLaunchKernelGGL(event_moments_entries_kernel, dim3((unsigned)((a.n_nodes + 255) / 256)), dim3(256), 0, s, a, m, A,
-                       cos_axis);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  const int64_t n = a.n_nodes > a.n_events ? a.n_nodes : a.n_events;
-  hipLaunchKernelGGL(event_halo_moments_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, m, h);
-  return hipGetLastError();
+  return launch_scan_moments(event_halo_moments_kernel, a, h, A, cos_axis, s);
 }
 
 }  // namespace art

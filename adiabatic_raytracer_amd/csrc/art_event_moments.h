@@ -239,6 +239,26 @@ __device__ inline void moment_scan_tables(const EventRowsArgs& a, const EventMom
   }
 }
 
+// The moments tail of a scan's launch (host code; launch_event_reweight's and launch_event_halo_scan's): pass A
+// over the run's own records, then `kernel`, the scan's __global__ wrapper of moment_scan_tables.
+template <class Scan>
+hipError_t launch_scan_moments(void (*kernel)(EventRowsArgs, EventMomentsArgs, Scan), const EventRowsArgs& a, const Scan& r,
+                               const SkyAxes& A, int cos_axis, hipStream_t s) {
+  EventMomentsArgs m{};
+  m.node_start = r.node_start; m.nbins = r.nbins; m.entries = r.entries;
+  m.sky_sq = r.sky_sq;   // (pass A reads it as "there is a sky table" only)
+  m.totals = r.mtotals;  // (pass A's misplaced records: slot 7 of the first set)
+  if (a.n_nodes > 0) {
+    hipLaunchKernelGGL(event_moments_entries_kernel, dim3((unsigned)((a.n_nodes + 255) / 256)), dim3(256), 0, s, a, m, A,
+                       cos_axis);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const int64_t n = a.n_nodes > a.n_events ? a.n_nodes : a.n_events;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, m, r);
+  return hipGetLastError();
+}
+
 hipError_t launch_event_moments(const EventRowsArgs& a, const EventMomentsArgs& m, const SkyAxes& A, int cos_axis,
                                 hipStream_t s) {
   const int64_t n = a.n_nodes > a.n_events ? a.n_nodes : a.n_events;

@@ -286,18 +286,7 @@ hipError_t launch_event_reweight(const KParams& P, const KParams& Pb, const Even
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   if (!r.mtotals) return hipSuccess;
-  EventMomentsArgs m{};
-  m.node_start = r.node_start; m.nbins = r.nbins; m.entries = r.entries;
-  m.sky_sq = r.sky_sq;  // (pass A reads it as "there is a sky table" only)
-  m.totals = r.mtotals;  // (pass A's misplaced records: slot 7 of the first coupling)
-  if (a.n_nodes > 0) {
-    hipLaunchKernelGGL(event_moments_entries_kernel, dim3((unsigned)((a.n_nodes + 255) / 256)), dim3(256), 0, s, a, m, A,
-                       cos_axis);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  const int64_t n = a.n_nodes > a.n_events ? a.n_nodes : a.n_events;
-  hipLaunchKernelGGL(event_reweight_moments_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, m, r);
-  return hipGetLastError();
+  return launch_scan_moments(event_reweight_moments_kernel, a, r, A, cos_axis, s);
 }
 
 }  // namespace art

@@ -83,6 +83,152 @@ static int event_weight_device_impl(const art_params* p, const art_halo* halo, d
   return ART_OK;
 }
 
+// The argument checks the two sky-map entry points share (no device is touched): the axes of a
+// table of at most SKY_MAX_DOUBLES doubles, and a mode the table allows.
+static int sky_axes(const int32_t nbins[3], const double lo[3], const double hi[3], bool c_all, int32_t mode,
+                    art::SkyAxes* A) {
+  if (mode < 0 || mode > 2) return fail(ART_E_INVALID, "sky map mode must be 0 (auto), 1 (LDS table) or 2 (global adds)");
+  int64_t table = 2;
+  for (int d = 0; d < 3; ++d) {
+    if (nbins[d] < 1) return fail(ART_E_INVALID, "sky map bin counts must be >= 1");
+    if (nbins[d] > art::SKY_MAX_DOUBLES / table) return fail(ART_E_INVALID, "sky map table exceeds 2^26 doubles");
+    table *= nbins[d];
+    A->n[d] = nbins[d];
+    if (d == 2 && c_all) {
+      A->lo[d] = A->hi[d] = 0.0;
+      continue;
+    }
+    if (!std::isfinite(lo[d]) || !std::isfinite(hi[d]) || !(lo[d] < hi[d]))
+      return fail(ART_E_INVALID, "sky map ranges need finite lo < hi");
+    A->lo[d] = lo[d];
+    A->hi[d] = hi[d];
+  }
+  A->c_all = c_all;
+  if (mode == 1 && table > art::SKY_LDS_DOUBLES)
+    return fail(ART_E_INVALID, "sky map mode 1: the table exceeds the LDS budget of 8192 doubles");
+  return ART_OK;
+}
+
+// An art_sky_spec as the kernels take it. Without one (the event calls' optional map): a single bin, added to in
+// HBM (mode 2).
+struct EventSky {
+  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
+  int cos_axis = 1, mode = 2;
+  int64_t size = 0;  // the doubles of one table, 0 without a map
+};
+// honour_mode: the spec's mode is checked and kept, and with mode 1 the map must fit the LDS budget beside a flux
+// table of nbins bins; else the tables are added to in HBM and the mode is not looked at.
+static int event_sky(const art_sky_spec* spec, bool honour_mode, int32_t nbins, EventSky* S) {
+  if (!spec) return ART_OK;
+  if (spec->theta_axis != 0 && spec->theta_axis != 1)
+    return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
+  const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
+  const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
+  const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
+  const int rc = sky_axes(nb, lo, hi, spec->n_dw == 1, honour_mode ? spec->mode : 0, &S->A);
+  if (rc) return rc;
+  S->size = 2 * (int64_t)nb[0] * nb[1] * nb[2];
+  if (honour_mode && spec->mode == 1 && S->size + 2 * nbins > art::SKY_LDS_DOUBLES)
+    return fail(ART_E_INVALID, "sky map mode 1: the sky and flux tables exceed the LDS budget of 8192 doubles");
+  S->cos_axis = spec->theta_axis;
+  if (honour_mode) S->mode = spec->mode;
+  return ART_OK;
+}
+
+// ---- The front end of the four event calls (rows, moments, coupling scan, halo scan): with event_sky above, the
+// checks of an art_event_rows_in, the fill of EventRowsArgs, the scans' tables and the scratch carver. Each call
+// keeps its own order of checks; where the calls differ on purpose the difference is a flag at the call site.
+
+static int event_in_ranges(const art_event_rows_in* in) {
+  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
+  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
+  return ART_OK;
+}
+
+static int event_out_ranges(int32_t reserved, int32_t nbins) {
+  if (reserved != 0) return fail(ART_E_INVALID, "reserved must be 0");
+  if (nbins < 0 || nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
+  return ART_OK;
+}
+
+static int need_node_start(const art_event_rows_in* in, const int64_t* node_start) {
+  if (in->n_nodes > 0 && !node_start) return fail(ART_E_INVALID, "node_start is NULL");
+  return ART_OK;
+}
+
+// What event_in_buffers asks beyond the buffers of a chunk that has nodes
+enum : unsigned {
+  IN_CYC_END_STATES = 1u,       // cyc_slot needs the re-run's end states too, not cyc_tau alone
+  IN_EVENT_INPUTS_ALWAYS = 2u,  // x, k_init, weight5 and back are needed with n_nodes == 0 too
+  IN_NODE_START_LATE = 4u,      // node_start is checked here, after the call's n_events == 0 return
+};
+
+// The buffers of an art_event_rows_in and its cyc_* rule: the last checks before the device
+static int event_in_buffers(const art_event_rows_in* in, const int64_t* node_start, unsigned flags) {
+  int rc;
+  if ((flags & IN_NODE_START_LATE) && (rc = need_node_start(in, node_start))) return rc;
+  const bool per_event = in->x && in->k_init && in->weight5 && in->back;
+  const bool per_node = in->back_counts && in->nodes && in->counts && in->infos;
+  if (((flags & IN_EVENT_INPUTS_ALWAYS) && !per_event) || (in->n_nodes > 0 && !(per_event && per_node)))
+    return fail(ART_E_INVALID, "NULL input buffer");
+  if (!in->cyc_slot) return ART_OK;
+  const art_segment_out* ce = in->cyc_end;
+  const bool tau = in->cyc_n == 0 || (in->cyc_n > 0 && in->cyc_tau);
+  if (!(flags & IN_CYC_END_STATES)) return tau ? ART_OK : fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0 and cyc_tau");
+  if (!tau || (in->cyc_n > 0 && (!ce || !ce->x_end || !ce->k_end || !ce->u7_end || !ce->tau_end || !ce->status)))
+    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0, cyc_tau and the re-run's end states");
+  return ART_OK;
+}
+
+// EventRowsArgs' inputs from p and in (13 columns, no outputs). end_states: also the cyclotron re-run's end states
+static art::EventRowsArgs event_args(const art_params* p, const art_event_rows_in* in, bool end_states) {
+  art::EventRowsArgs a{};
+  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
+  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
+  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
+  if (in->cyc_slot) {
+    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
+    if (const art_segment_out* ce = end_states ? in->cyc_end : nullptr) {
+      a.cyc_x_end = ce->x_end; a.cyc_k_end = ce->k_end; a.cyc_u7_end = ce->u7_end; a.cyc_tau_end = ce->tau_end;
+      a.cyc_status = ce->status;
+    }
+  }
+  a.mass_a = p->mass_a;
+  a.ncols = art::EVENT_COLS_SHORT;
+  return a;
+}
+
+// The part of a scan's out struct the two scans share (art_event_reweight_out, art_event_halo_scan_out): the checks
+// of its tables after `totals`, then the tables, node_start and the sizes into the kernels' args.
+template <class Out, class Args>
+static int scan_tables(const Out* out, const int64_t* node_start, int32_t n_k, const EventSky& S, Args* r) {
+  if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
+  if (out->sky && !out->sky_hist) return fail(ART_E_INVALID, "sky_hist is NULL");
+  const bool moments = out->moment_totals != nullptr;
+  if (moments && out->nbins > 0 && (!out->flux_sq || !out->flux_xa)) return fail(ART_E_INVALID, "flux_sq or flux_xa is NULL");
+  if (moments && out->sky && (!out->sky_sq || !out->sky_xa)) return fail(ART_E_INVALID, "sky_sq or sky_xa is NULL");
+  r->node_start = node_start; r->n_k = n_k; r->nbins = out->nbins; r->sky_size = S.size;
+  r->flux = out->flux; r->sky = out->sky ? out->sky_hist : nullptr; r->totals = out->totals;
+  if (moments) {
+    r->flux_sq = out->flux_sq; r->flux_xa = out->flux_xa; r->mtotals = out->moment_totals;
+    if (out->sky) {
+      r->sky_sq = out->sky_sq; r->sky_xa = out->sky_xa;
+    }
+  }
+  return ART_OK;
+}
+
+// One block of scratch cut into parts that each begin at a multiple of 256 bytes: add() every part, allocate
+// `bytes`, then part i lies at block + its add().
+struct Carve {
+  size_t bytes = 0;
+  size_t add(size_t part) {
+    const size_t at = (bytes + 255) & ~(size_t)255;
+    bytes = at + part;
+    return at;
+  }
+};
+
 }  // namespace host
 }  // namespace art
 
@@ -288,32 +434,6 @@ int art_flux_histogram_phi_range_device(int64_t n, const double* phi, const int8
   return ART_OK;
 }
 
-// The argument checks the two sky-map entry points share (no device is touched): the axes of a
-// table of at most SKY_MAX_DOUBLES doubles, and a mode the table allows.
-static int sky_axes(const int32_t nbins[3], const double lo[3], const double hi[3], bool c_all, int32_t mode,
-                    art::SkyAxes* A) {
-  if (mode < 0 || mode > 2) return fail(ART_E_INVALID, "sky map mode must be 0 (auto), 1 (LDS table) or 2 (global adds)");
-  int64_t table = 2;
-  for (int d = 0; d < 3; ++d) {
-    if (nbins[d] < 1) return fail(ART_E_INVALID, "sky map bin counts must be >= 1");
-    if (nbins[d] > art::SKY_MAX_DOUBLES / table) return fail(ART_E_INVALID, "sky map table exceeds 2^26 doubles");
-    table *= nbins[d];
-    A->n[d] = nbins[d];
-    if (d == 2 && c_all) {
-      A->lo[d] = A->hi[d] = 0.0;
-      continue;
-    }
-    if (!std::isfinite(lo[d]) || !std::isfinite(hi[d]) || !(lo[d] < hi[d]))
-      return fail(ART_E_INVALID, "sky map ranges need finite lo < hi");
-    A->lo[d] = lo[d];
-    A->hi[d] = hi[d];
-  }
-  A->c_all = c_all;
-  if (mode == 1 && table > art::SKY_LDS_DOUBLES)
-    return fail(ART_E_INVALID, "sky map mode 1: the table exceeds the LDS budget of 8192 doubles");
-  return ART_OK;
-}
-
 int art_histogram3_device(int64_t n, const double* a, const double* b, const double* c, const int8_t* species,
                           const double* w, const int32_t nbins[3], const double lo[3], const double hi[3], int32_t mode,
                           double* hist, void* stream) {
@@ -339,19 +459,14 @@ int art_sky_map_segments_device(const art_params* p, const art_sky_spec* spec, i
   if (rc) return rc;
   if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
   if (!spec) return fail(ART_E_INVALID, "NULL spec");
-  if (spec->theta_axis != 0 && spec->theta_axis != 1)
-    return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
-  const int32_t nbins[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
-  const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
-  const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
-  art::SkyAxes A;
-  if ((rc = sky_axes(nbins, lo, hi, spec->n_dw == 1, spec->mode, &A))) return rc;
+  EventSky S;
+  if ((rc = event_sky(spec, /*honour_mode=*/true, 0, &S))) return rc;  // (no flux table beside the map)
   if (n == 0) return ART_OK;
   if (!x_end || !k_end || !u7_end || !status || !hist) return fail(ART_E_INVALID, "NULL buffer");
   DeviceCtx* ctx;
   if ((rc = current_ctx(&ctx))) return rc;
-  HIP_OK(art::launch_sky_map_segments(art::make_kparams(*p), n, x_end, k_end, u7_end, status, species, w, dw_offset, A,
-                                      spec->theta_axis, spec->mode, hist, bin_out, (hipStream_t)stream));
+  HIP_OK(art::launch_sky_map_segments(art::make_kparams(*p), n, x_end, k_end, u7_end, status, species, w, dw_offset, S.A,
+                                      S.cos_axis, S.mode, hist, bin_out, (hipStream_t)stream));
   return ART_OK;
 }
 
@@ -363,71 +478,44 @@ int art_event_rows_device(const art_params* p, const art_event_rows_in* in, cons
   int rc = validate(p);
   if (rc) return rc;
   if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
-  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
-  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
+  if ((rc = event_in_ranges(in))) return rc;
   if (out->ncols != art::EVENT_COLS_SHORT && out->ncols != art::EVENT_COLS_FULL)
     return fail(ART_E_INVALID, "ncols must be 13 or 29");
   if ((out->rows || out->bin_out) && out->row_capacity < in->n_nodes)
     return fail(ART_E_INVALID, "row_capacity must be >= n_nodes");
-  if (out->nbins < 0 || out->nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
-  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
-  int cos_axis = 1, mode = 2;
-  if (out->sky) {
-    const art_sky_spec* spec = out->sky;
-    if (spec->theta_axis != 0 && spec->theta_axis != 1)
-      return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
-    const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
-    const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
-    const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
-    if ((rc = sky_axes(nb, lo, hi, spec->n_dw == 1, spec->mode, &A))) return rc;
-    if (spec->mode == 1 && 2 * (int64_t)nb[0] * nb[1] * nb[2] + 2 * out->nbins > art::SKY_LDS_DOUBLES)
-      return fail(ART_E_INVALID, "sky map mode 1: the sky and flux tables exceed the LDS budget of 8192 doubles");
-    cos_axis = spec->theta_axis;
-    mode = spec->mode;
-  }
-  if (in->n_events == 0 || (in->n_nodes == 0 && !in->attempts)) return ART_OK;
+  if ((rc = event_out_ranges(0, out->nbins))) return rc;  // (this out struct has no reserved field)
+  EventSky S;
+  // honour_mode: event_rows_kernel alone can keep its tables in LDS; the other three calls add to theirs in HBM
+  if ((rc = event_sky(out->sky, /*honour_mode=*/true, out->nbins, &S))) return rc;
+  if (in->n_events == 0 || (in->n_nodes == 0 && !in->attempts)) return ART_OK;  // (attempts alone still add to totals)
   if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
   if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
   if (out->sky && !out->sky_hist) return fail(ART_E_INVALID, "sky_hist is NULL");
-  if (in->n_nodes > 0 && (!in->x || !in->k_init || !in->weight5 || !in->back || !in->back_counts || !in->nodes ||
-                          !in->counts || !in->infos))
-    return fail(ART_E_INVALID, "NULL input buffer");
-  const art_segment_out* ce = in->cyc_end;
-  if (in->cyc_slot && (in->cyc_n < 0 || (in->cyc_n > 0 && (!in->cyc_tau || !ce || !ce->x_end || !ce->k_end ||
-                                                           !ce->u7_end || !ce->tau_end || !ce->status))))
-    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0, cyc_tau and the re-run's end states");
+  // IN_CYC_END_STATES: the kernel compares each re-run's end state with its node's (totals[5])
+  if ((rc = event_in_buffers(in, nullptr, IN_CYC_END_STATES))) return rc;
   DeviceCtx* ctx;
   if ((rc = current_ctx(&ctx))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  art::EventRowsArgs a{};
-  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
+  art::EventRowsArgs a = event_args(p, in, /*end_states=*/true);
   a.row_capacity = out->row_capacity;
-  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
-  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
-  if (in->cyc_slot) {
-    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
-    if (ce) {
-      a.cyc_x_end = ce->x_end; a.cyc_k_end = ce->k_end; a.cyc_u7_end = ce->u7_end; a.cyc_tau_end = ce->tau_end;
-      a.cyc_status = ce->status;
-    }
-  }
-  a.mass_a = p->mass_a;
   a.ncols = out->ncols; a.nbins = out->nbins;
   a.rows = out->rows; a.flux = out->flux; a.sky_hist = out->sky ? out->sky_hist : nullptr; a.totals = out->totals;
   a.bin_out = out->sky ? out->bin_out : nullptr;
-  void* block = nullptr;
-  if (in->n_nodes > 0) {
-    const size_t pos_bytes = ((size_t)in->n_nodes * 4 + 255) & ~(size_t)255, tmp_bytes = art::event_scan_bytes(in->n_nodes);
-    if ((rc = scratch_alloc(s, pos_bytes + tmp_bytes, &block))) return rc;
-    a.pos = (const int32_t*)block;
-    hipError_t e = art::launch_event_scan(in->n_nodes, in->nodes, false, (int32_t*)block, (char*)block + pos_bytes,
-                                          tmp_bytes, s);
-    if (e == hipSuccess) e = art::launch_event_rows(a, A, cos_axis, mode, s);
-    (void)hipFreeAsync(block, s);
-    HIP_OK(e);
-  } else {
-    HIP_OK(art::launch_event_rows(a, A, cos_axis, mode, s));
+  if (in->n_nodes == 0) {
+    HIP_OK(art::launch_event_rows(a, S.A, S.cos_axis, S.mode, s));
+    return ART_OK;
   }
+  Carve cv;  // [pos | tmp]
+  const size_t tmp_bytes = art::event_scan_bytes(in->n_nodes), o_pos = cv.add((size_t)in->n_nodes * 4),
+               o_tmp = cv.add(tmp_bytes);
+  void* block = nullptr;
+  if ((rc = scratch_alloc(s, cv.bytes, &block))) return rc;
+  a.pos = (const int32_t*)((char*)block + o_pos);
+  hipError_t e = art::launch_event_scan(in->n_nodes, in->nodes, false, (int32_t*)((char*)block + o_pos),
+                                        (char*)block + o_tmp, tmp_bytes, s);
+  if (e == hipSuccess) e = art::launch_event_rows(a, S.A, S.cos_axis, S.mode, s);
+  (void)hipFreeAsync(block, s);
+  HIP_OK(e);
   return ART_OK;
 }
 
@@ -451,12 +539,13 @@ int art_event_gather_photons_device(const art_params* p, int64_t n_events, const
   hipStream_t s = (hipStream_t)stream;
   TreeScratch ts;  // (its block and its pinned word, released when the call returns)
   ts.s = s;
-  const size_t pos_bytes = ((size_t)(n_nodes + 1) * 4 + 255) & ~(size_t)255, tmp_bytes = art::event_scan_bytes(n_nodes + 1);
-  if ((rc = scratch_alloc(s, pos_bytes + tmp_bytes, &ts.block))) return rc;
+  Carve cv;  // [pos | tmp]
+  const size_t tmp_bytes = art::event_scan_bytes(n_nodes + 1), o_pos = cv.add((size_t)(n_nodes + 1) * 4), o_tmp = cv.add(tmp_bytes);
+  if ((rc = scratch_alloc(s, cv.bytes, &ts.block))) return rc;
   if (hipHostMalloc((void**)&ts.host, 64, hipHostMallocDefault) != hipSuccess) return fail(ART_E_NOMEM, "hipHostMalloc failed");
-  int32_t* pos = (int32_t*)ts.block;
+  int32_t* pos = (int32_t*)((char*)ts.block + o_pos);
   // the count is the sum of the last prefix and the last node's own flag: both come to the host
-  HIP_OK(art::launch_event_scan(n_nodes, nodes, true, pos, (char*)ts.block + pos_bytes, tmp_bytes, s));
+  HIP_OK(art::launch_event_scan(n_nodes, nodes, true, pos, (char*)ts.block + o_tmp, tmp_bytes, s));
   HIP_OK(hipMemcpyAsync(ts.host, pos + (n_nodes - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(ts.host + 2, &nodes[n_nodes - 1], 2 * sizeof(int32_t) + sizeof(int32_t), hipMemcpyDeviceToHost, s));
   lk.unlock();
@@ -483,46 +572,21 @@ int art_event_moments_device(const art_params* p, const art_event_rows_in* in, c
   int rc = validate(p);
   if (rc) return rc;
   if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
-  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
-  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
-  if (out->reserved != 0) return fail(ART_E_INVALID, "reserved must be 0");
-  if (out->nbins < 0 || out->nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
-  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
-  int cos_axis = 1;
-  if (out->sky) {
-    const art_sky_spec* spec = out->sky;
-    if (spec->theta_axis != 0 && spec->theta_axis != 1)
-      return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
-    const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
-    const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
-    const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
-    if ((rc = sky_axes(nb, lo, hi, spec->n_dw == 1, 0, &A))) return rc;  // (the tables are added to in HBM: no mode)
-    cos_axis = spec->theta_axis;
-  }
+  if ((rc = event_in_ranges(in)) || (rc = event_out_ranges(out->reserved, out->nbins))) return rc;
+  EventSky S;
+  if ((rc = event_sky(out->sky, /*honour_mode=*/false, out->nbins, &S))) return rc;  // (tables in HBM: no mode)
   if (in->n_events == 0) return ART_OK;
   if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
   if (out->nbins > 0 && (!out->flux_sq || !out->flux_xa)) return fail(ART_E_INVALID, "flux_sq or flux_xa is NULL");
   if (out->sky && (!out->sky_sq || !out->sky_xa)) return fail(ART_E_INVALID, "sky_sq or sky_xa is NULL");
-  if (in->n_nodes > 0 && !node_start) return fail(ART_E_INVALID, "node_start is NULL");
-  if (in->n_nodes > 0 && (!in->x || !in->k_init || !in->weight5 || !in->back || !in->back_counts || !in->nodes ||
-                          !in->counts || !in->infos))
-    return fail(ART_E_INVALID, "NULL input buffer");
-  const art_segment_out* ce = in->cyc_end;
-  if (in->cyc_slot && (in->cyc_n < 0 || (in->cyc_n > 0 && (!in->cyc_tau || !ce || !ce->x_end || !ce->k_end ||
-                                                           !ce->u7_end || !ce->tau_end || !ce->status))))
-    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0, cyc_tau and the re-run's end states");
+  // IN_NODE_START_LATE: an empty chunk has returned above without a look at node_start (the scans look first).
+  // IN_CYC_END_STATES: asked for as art_event_rows_device asks, whose chunk and re-run this call is handed; the
+  // kernels read cyc_tau alone.
+  if ((rc = event_in_buffers(in, node_start, IN_NODE_START_LATE | IN_CYC_END_STATES))) return rc;
   DeviceCtx* ctx;
   if ((rc = current_ctx(&ctx))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  art::EventRowsArgs a{};
-  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
-  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
-  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
-  if (in->cyc_slot) {
-    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
-  }
-  a.mass_a = p->mass_a;
-  a.ncols = art::EVENT_COLS_SHORT;
+  const art::EventRowsArgs a = event_args(p, in, /*end_states=*/false);
   art::EventMomentsArgs m{};
   m.node_start = node_start; m.nbins = out->nbins;
   m.flux_sq = out->flux_sq; m.flux_xa = out->flux_xa; m.totals = out->totals;
@@ -532,7 +596,7 @@ int art_event_moments_device(const art_params* p, const art_event_rows_in* in, c
   void* block = nullptr;
   if (in->n_nodes > 0 && (rc = scratch_alloc(s, (size_t)in->n_nodes * sizeof(art::MomentEntry), &block))) return rc;
   m.entries = (art::MomentEntry*)block;
-  const hipError_t e = art::launch_event_moments(a, m, A, cos_axis, s);
+  const hipError_t e = art::launch_event_moments(a, m, S.A, S.cos_axis, s);
   if (block) (void)hipFreeAsync(block, s);
   HIP_OK(e);
   return ART_OK;
@@ -554,83 +618,47 @@ int art_event_reweight_device(const art_params* p, const art_event_rows_in* in, 
   for (int k = 0; k < n_couplings; ++k)
     if (!(couplings[k] > 0.0) || !std::isfinite(couplings[k]))
       return fail(ART_E_INVALID, "every coupling must be finite and > 0");
-  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
-  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
-  if (out->reserved != 0) return fail(ART_E_INVALID, "reserved must be 0");
-  if (out->nbins < 0 || out->nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
-  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
-  int cos_axis = 1;
-  int64_t sky_size = 0;
-  if (out->sky) {
-    const art_sky_spec* spec = out->sky;
-    if (spec->theta_axis != 0 && spec->theta_axis != 1)
-      return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
-    const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
-    const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
-    const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
-    if ((rc = sky_axes(nb, lo, hi, spec->n_dw == 1, 0, &A))) return rc;  // (the tables are added to in HBM: no mode)
-    cos_axis = spec->theta_axis;
-    sky_size = 2 * (int64_t)nb[0] * nb[1] * nb[2];
-  }
-  if (in->n_nodes > 0 && !node_start) return fail(ART_E_INVALID, "node_start is NULL");
+  if ((rc = event_in_ranges(in)) || (rc = event_out_ranges(out->reserved, out->nbins))) return rc;
+  EventSky S;
+  if ((rc = event_sky(out->sky, /*honour_mode=*/false, out->nbins, &S))) return rc;  // (tables in HBM: no mode)
+  if ((rc = need_node_start(in, node_start))) return rc;  // (before the empty return, unlike the moments call)
   if (in->n_events == 0) return ART_OK;
   if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
   if (!out->erg) return fail(ART_E_INVALID, "erg is NULL");
-  if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
-  if (out->sky && !out->sky_hist) return fail(ART_E_INVALID, "sky_hist is NULL");
-  const bool moments = out->moment_totals != nullptr;
-  if (moments && out->nbins > 0 && (!out->flux_sq || !out->flux_xa)) return fail(ART_E_INVALID, "flux_sq or flux_xa is NULL");
-  if (moments && out->sky && (!out->sky_sq || !out->sky_xa)) return fail(ART_E_INVALID, "sky_sq or sky_xa is NULL");
-  if (!in->x || !in->k_init || !in->weight5 || !in->back) return fail(ART_E_INVALID, "NULL input buffer");
-  if (in->n_nodes > 0 && (!in->back_counts || !in->nodes || !in->counts || !in->infos))
-    return fail(ART_E_INVALID, "NULL input buffer");
-  if (in->cyc_slot && (in->cyc_n < 0 || (in->cyc_n > 0 && !in->cyc_tau)))
-    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0 and cyc_tau");
+  art::EventReweightArgs r{};
+  if ((rc = scan_tables(out, node_start, n_couplings, S, &r))) return rc;
+  // IN_EVENT_INPUTS_ALWAYS: event_reweight_kernel reads x, k_init and back of every event, nodes or not.
+  // No IN_CYC_END_STATES: the scan reads cyc_tau alone.
+  if ((rc = event_in_buffers(in, node_start, IN_EVENT_INPUTS_ALWAYS))) return rc;
   DeviceCtx* ctx;
   if ((rc = current_ctx(&ctx))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  art::EventRowsArgs a{};
-  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
-  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
-  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
-  if (in->cyc_slot) {
-    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
-  }
-  a.mass_a = p->mass_a;
-  a.ncols = art::EVENT_COLS_SHORT;
-  art::EventReweightArgs r{};
-  r.node_start = node_start; r.erg = out->erg;
-  r.mc_nodes = opts->mc_nodes; r.n_k = n_couplings; r.nbins = out->nbins; r.sky_size = sky_size;
+  const art::EventRowsArgs a = event_args(p, in, /*end_states=*/false);
+  r.erg = out->erg; r.mc_nodes = opts->mc_nodes;
   for (int k = 0; k < n_couplings; ++k) {
     const double q = couplings[k] / p->g_agg;
     r.s[k] = q * q;
   }
-  r.flux = out->flux; r.sky = out->sky ? out->sky_hist : nullptr; r.totals = out->totals;
-  if (moments) {
-    r.flux_sq = out->flux_sq; r.flux_xa = out->flux_xa; r.mtotals = out->moment_totals;
-    if (out->sky) {
-      r.sky_sq = out->sky_sq; r.sky_xa = out->sky_xa;
-    }
-  }
-  // one block of scratch: [X0 | W | B | Pw | entries], each part a multiple of 256 bytes
+  const bool moments = r.mtotals != nullptr;
   const size_t K = (size_t)n_couplings, nn = (size_t)in->n_nodes, ne = (size_t)in->n_events;
-  auto part = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-  const size_t b_x0 = part(nn * 8), b_w = out->weights ? 0 : part(K * nn * 8), b_b = out->back ? 0 : part(K * ne * 8),
-               b_pw = moments ? part(K * nn * 8) : 0, b_en = moments ? part(nn * sizeof(art::MomentEntry)) : 0;
+  Carve cv;  // [X0 | W | B | Pw | entries | 256 bytes, so the block is never empty]
+  const size_t o_x0 = cv.add(nn * 8), o_w = cv.add(out->weights ? 0 : K * nn * 8), o_b = cv.add(out->back ? 0 : K * ne * 8),
+               o_pw = cv.add(moments ? K * nn * 8 : 0), o_en = cv.add(moments ? nn * sizeof(art::MomentEntry) : 0);
+  cv.add(256);
   void* block = nullptr;
-  if ((rc = scratch_alloc(s, b_x0 + b_w + b_b + b_pw + b_en + 256, &block))) return rc;
+  if ((rc = scratch_alloc(s, cv.bytes, &block))) return rc;
   char* at = (char*)block;
-  r.X0 = (double*)at; at += b_x0;
-  r.W = out->weights ? out->weights : (double*)at; at += b_w;
-  r.B = out->back ? out->back : (double*)at; at += b_b;
+  r.X0 = (double*)(at + o_x0);
+  r.W = out->weights ? out->weights : (double*)(at + o_w);
+  r.B = out->back ? out->back : (double*)(at + o_b);
   r.Bp = out->back_prob;
   if (moments) {
-    r.Pw = (double*)at; at += b_pw;
-    r.entries = (art::MomentEntry*)at;
+    r.Pw = (double*)(at + o_pw);
+    r.entries = (art::MomentEntry*)(at + o_en);
   }
   art_params pb = *p;
   pb.B0 = -p->B0;  // the backtrace's field (main_runner_tree: the backtrace runs with B0 negated)
-  const hipError_t e = art::launch_event_reweight(art::make_kparams(*p), art::make_kparams(pb), a, r, A, cos_axis, s);
+  const hipError_t e = art::launch_event_reweight(art::make_kparams(*p), art::make_kparams(pb), a, r, S.A, S.cos_axis, s);
   (void)hipFreeAsync(block, s);
   HIP_OK(e);
   return ART_OK;
@@ -660,73 +688,36 @@ int art_event_halo_scan_device(const art_params* p, const art_event_rows_in* in,
     for (int i = 0; i < 3; ++i) h.models[k].v_ns[i] = m.v_ns[i];
     h.models[k].vp = h.base.vp;  // (the run's proposal; a model's own v_prop is ignored)
   }
-  if (in->n_events < 0) return fail(ART_E_INVALID, "n_events must be >= 0");
-  if (in->n_nodes < 0 || in->n_nodes > 2147483647LL) return fail(ART_E_INVALID, "n_nodes must be in [0, 2^31)");
-  if (out->reserved != 0) return fail(ART_E_INVALID, "reserved must be 0");
-  if (out->nbins < 0 || out->nbins > 4096) return fail(ART_E_INVALID, "nbins must be in [0, 4096]");
-  art::SkyAxes A{{1, 1, 1}, 1, {0.0, 0.0, 0.0}, {1.0, 1.0, 1.0}};
-  int cos_axis = 1;
-  int64_t sky_size = 0;
-  if (out->sky) {
-    const art_sky_spec* spec = out->sky;
-    if (spec->theta_axis != 0 && spec->theta_axis != 1)
-      return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
-    const int32_t nb[3] = {spec->n_theta, spec->n_phi, spec->n_dw};
-    const double lo[3] = {spec->theta_axis ? -1.0 : 0.0, -art::PI, spec->dw_lo};
-    const double hi[3] = {spec->theta_axis ? 1.0 : art::PI, art::PI, spec->dw_hi};
-    if ((rc = sky_axes(nb, lo, hi, spec->n_dw == 1, 0, &A))) return rc;  // (the tables are added to in HBM: no mode)
-    cos_axis = spec->theta_axis;
-    sky_size = 2 * (int64_t)nb[0] * nb[1] * nb[2];
-  }
+  if ((rc = event_in_ranges(in)) || (rc = event_out_ranges(out->reserved, out->nbins))) return rc;
+  EventSky S;
+  if ((rc = event_sky(out->sky, /*honour_mode=*/false, out->nbins, &S))) return rc;  // (tables in HBM: no mode)
   if (in->n_events > 0 && !out->vifty) return fail(ART_E_INVALID, "vifty is NULL");
-  if (in->n_nodes > 0 && !node_start) return fail(ART_E_INVALID, "node_start is NULL");
+  if ((rc = need_node_start(in, node_start))) return rc;  // (before the empty return, unlike the moments call)
   if (in->n_events == 0) return ART_OK;
   if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
-  if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
-  if (out->sky && !out->sky_hist) return fail(ART_E_INVALID, "sky_hist is NULL");
-  const bool moments = out->moment_totals != nullptr;
-  if (moments && out->nbins > 0 && (!out->flux_sq || !out->flux_xa)) return fail(ART_E_INVALID, "flux_sq or flux_xa is NULL");
-  if (moments && out->sky && (!out->sky_sq || !out->sky_xa)) return fail(ART_E_INVALID, "sky_sq or sky_xa is NULL");
-  if (in->n_nodes > 0 && (!in->x || !in->k_init || !in->weight5 || !in->back || !in->back_counts || !in->nodes ||
-                          !in->counts || !in->infos))
-    return fail(ART_E_INVALID, "NULL input buffer");
-  if (in->cyc_slot && (in->cyc_n < 0 || (in->cyc_n > 0 && !in->cyc_tau)))
-    return fail(ART_E_INVALID, "cyc_slot needs cyc_n >= 0 and cyc_tau");
+  if ((rc = scan_tables(out, node_start, n_models, S, &h))) return rc;
+  // No IN_EVENT_INPUTS_ALWAYS: the ratio kernel reads vifty alone per event. No IN_CYC_END_STATES: cyc_tau alone.
+  if ((rc = event_in_buffers(in, node_start, 0))) return rc;
   DeviceCtx* ctx;
   if ((rc = current_ctx(&ctx))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  art::EventRowsArgs a{};
-  a.n_events = in->n_events; a.event_offset = in->event_offset; a.n_nodes = in->n_nodes;
-  a.x = in->x; a.k_init = in->k_init; a.weight5 = in->weight5; a.attempts = in->attempts;
-  a.back = in->back; a.nodes = in->nodes; a.back_counts = in->back_counts; a.counts = in->counts; a.infos = in->infos;
-  if (in->cyc_slot) {
-    a.cyc_slot = in->cyc_slot; a.cyc_n = in->cyc_n; a.cyc_tau = in->cyc_tau;
-  }
-  a.mass_a = p->mass_a;
-  a.ncols = art::EVENT_COLS_SHORT;
-  h.node_start = node_start; h.vifty = out->vifty;
-  h.n_k = n_models; h.nbins = out->nbins; h.sky_size = sky_size;
-  h.flux = out->flux; h.sky = out->sky ? out->sky_hist : nullptr; h.totals = out->totals;
-  if (moments) {
-    h.flux_sq = out->flux_sq; h.flux_xa = out->flux_xa; h.mtotals = out->moment_totals;
-    if (out->sky) {
-      h.sky_sq = out->sky_sq; h.sky_xa = out->sky_xa;
-    }
-  }
-  // one block of scratch: [R | Pw | entries], each part a multiple of 256 bytes
+  const art::EventRowsArgs a = event_args(p, in, /*end_states=*/false);
+  h.vifty = out->vifty;
+  const bool moments = h.mtotals != nullptr;
   const size_t K = (size_t)n_models, nn = (size_t)in->n_nodes, ne = (size_t)in->n_events;
-  auto part = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-  const size_t b_r = out->ratio ? 0 : part(K * ne * 8), b_pw = moments ? part(K * nn * 8) : 0,
-               b_en = moments ? part(nn * sizeof(art::MomentEntry)) : 0;
+  Carve cv;  // [R | Pw | entries | 256 bytes, so the block is never empty]
+  const size_t o_r = cv.add(out->ratio ? 0 : K * ne * 8), o_pw = cv.add(moments ? K * nn * 8 : 0),
+               o_en = cv.add(moments ? nn * sizeof(art::MomentEntry) : 0);
+  cv.add(256);
   void* block = nullptr;
-  if ((rc = scratch_alloc(s, b_r + b_pw + b_en + 256, &block))) return rc;
+  if ((rc = scratch_alloc(s, cv.bytes, &block))) return rc;
   char* at = (char*)block;
-  h.R = out->ratio ? out->ratio : (double*)at; at += b_r;
+  h.R = out->ratio ? out->ratio : (double*)(at + o_r);
   if (moments) {
-    h.Pw = (double*)at; at += b_pw;
-    h.entries = (art::MomentEntry*)at;
+    h.Pw = (double*)(at + o_pw);
+    h.entries = (art::MomentEntry*)(at + o_en);
   }
-  const hipError_t e = art::launch_event_halo_scan(a, h, A, cos_axis, s);
+  const hipError_t e = art::launch_event_halo_scan(a, h, S.A, S.cos_axis, s);
   (void)hipFreeAsync(block, s);
   HIP_OK(e);
   return ART_OK;

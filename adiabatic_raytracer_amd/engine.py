@@ -229,8 +229,10 @@ class Engine:
     # ---- main_runner_tree's rows, flux and sky map from forests in HBM (art_event_rows_device)
     def _sky_spec(self, sky):
         """(SkySpec, shape, the keywords completed) of a sky-map dict: sky_map()'s keywords n_theta, n_phi,
-        n_dw, theta_axis, dw_range, and mode."""
-        kw = {"n_theta": 32, "n_phi": 64, "n_dw": 1, "theta_axis": "cos", "dw_range": None, "mode": 0}
+        n_dw, theta_axis, dw_range, and mode. None (no map): three None."""
+        if sky is None:
+            return None, None, None
+        kw ={"n_theta": 32, "n_phi": 64, "n_dw": 1, "theta_axis": "cos", "dw_range": None, "mode": 0}
         if set(sky) - set(kw):
             raise ValueError(f"sky_map: unknown keys {sorted(set(sky) - set(kw))}")
         kw.update(sky)
@@ -267,11 +269,9 @@ class Engine:
         nbins = int(nbins)
         if flux is None:
             flux = torch.zeros(2 * nbins, dtype=F64, device=self.device)
-        spec = shape = None
-        if sky is not None:
-            spec, shape, _ = self._sky_spec(sky)
-            if sky_hist is None:
-                sky_hist = torch.zeros(*shape, dtype=F64, device=self.device)
+        spec, shape, _ = self._sky_spec(sky)
+        if spec is not None and sky_hist is None:
+            sky_hist = torch.zeros(*shape, dtype=F64, device=self.device)
         if return_bins and spec is None:
             raise ValueError("event_rows: return_bins needs a sky map")
         part = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
@@ -324,9 +324,7 @@ class Engine:
         cyclotron_rerun: event_rows' "cyclotron_rerun" of this chunk, so exp(-τ) is in the powers as it is
         in column 8; nothing is propagated here. trees.moments_sigma turns the tables into errors."""
         nbins = int(nbins)
-        spec = shape = None
-        if sky is not None:
-            spec, shape, _ = self._sky_spec(sky)
+        spec, shape, _ = self._sky_spec(sky)
         if moments is None:
             moments = self._zero_moments(nbins, shape)
         if moments["flux_sq"].numel() != 2 * nbins or (shape and tuple(moments["sky_sq"].shape) != shape):
@@ -351,15 +349,40 @@ class Engine:
             raise ValueError("couplings: the base coupling params.g_agg must be finite and > 0")
         return g
 
-    def _zero_scan(self, g, nbins, shape, errors):
+    def _zero_scan(self, K, n_totals, nbins, shape, errors, ident):
+        """The zero tables of a scan over K sets (couplings or halo models), its totals n_totals wide. ident: what
+        the scan was made for, its first keys ({"g": [...]}, or {"base": ..., "models": [...]})."""
         z = lambda *d: torch.zeros(*d, dtype=F64, device=self.device)  # noqa: E731
-        K = len(g)
-        scan = {"g": list(g), "flux": z(K, 2 * nbins), "sky": z(K, *shape) if shape else None,
-                "totals": z(K, len(_lib.REWEIGHT_TOTALS)), "n_events": 0}
+        scan = {**ident, "flux": z(K, 2 * nbins), "sky": z(K, *shape) if shape else None, "totals": z(K, n_totals),
+                "n_events": 0}
         if errors:
             scan.update(flux_sq=z(K, 2 * nbins), flux_xa=z(K, 2 * nbins), sky_sq=z(K, *shape) if shape else None,
                         sky_xa=z(K, *shape) if shape else None, moment_totals=z(K, len(_lib.MOMENT_TOTALS)))
         return scan
+
+    @staticmethod
+    def _scan_fits(scan, ident, nbins, shape, errors):
+        """Was `scan` (a _zero_scan, maybe added to since) made for this ident and these tables?"""
+        return (all(scan[k] == v for k, v in ident.items()) and scan["flux"].shape[1] == 2 * nbins and
+                errors == ("moment_totals" in scan) and
+                (None if scan["sky"] is None else tuple(scan["sky"].shape[1:])) == shape)
+
+    @staticmethod
+    def _finish_scan(scan, zero, result, counter, what):
+        """run_events' last step for a scan: zero tables (zero()) when there were no events, the tables as `result`
+        makes them the scan's dict of host arrays, and its integrity counter, which must be 0"""
+        out = result(zero() if scan is None else scan)
+        if out[counter] != 0:
+            raise _lib.ArtError(f"run_events: {out[counter]} node records {what}")
+        return out
+
+    @staticmethod
+    def _scan_out(scan, nbins, spec, shape):
+        """What art_event_reweight_out and art_event_halo_scan_out share: (nbins, reserved, flux, sky, sky_hist,
+        totals), the fields after the first, and the five moment tables, the last ones"""
+        mo = [_p(scan.get(k)) for k in ("flux_sq", "flux_xa", "sky_sq", "sky_xa", "moment_totals")]
+        return (nbins, 0, _p(scan["flux"]), C.pointer(spec) if spec is not None else None,
+                _p(scan["sky"]) if shape else None, _p(scan["totals"])), mo
 
     def event_reweight(self, sample, weight5, back, forward, couplings, *, mc_nodes, event_offset=0, nbins=50, sky=None,
                        errors=False, cyclotron_rerun=None, scan=None, return_weights=False) -> dict:
@@ -379,23 +402,18 @@ class Engine:
         g = self._couplings(couplings)
         K, nbins = len(g), int(nbins)
         n, nn = sample["erg"].numel(), int(forward["n_nodes"])
-        spec = shape = None
-        if sky is not None:
-            spec, shape, _ = self._sky_spec(sky)
+        spec, shape, _ = self._sky_spec(sky)
         if scan is None:
-            scan = self._zero_scan(g, nbins, shape, errors)
-        if (scan["g"] != g or scan["flux"].shape[1] != 2 * nbins or errors != ("moment_totals" in scan) or
-                (None if scan["sky"] is None else tuple(scan["sky"].shape[1:])) != shape):
+            scan = self._zero_scan(K, len(_lib.REWEIGHT_TOTALS), nbins, shape, errors, {"g": list(g)})
+        if not self._scan_fits(scan, {"g": g}, nbins, shape, errors):
             raise ValueError("event_reweight: `scan` was made for other couplings or tables")
         # (zeros: a record outside its own tree's range is written by no lane)
         W = torch.zeros(K, max(nn, 1), dtype=F64, device=self.device) if return_weights else None
         B = self.empty(K, max(n, 1)) if return_weights else None
         Bp = self.empty(K, max(n, 1)) if return_weights else None
         ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
-        mo = [_p(scan.get(k)) for k in ("flux_sq", "flux_xa", "sky_sq", "sky_xa", "moment_totals")]
-        ro = _lib.EventReweightOut(_p(sample["erg"]), nbins, 0, _p(scan["flux"]),
-                                   C.pointer(spec) if spec is not None else None, _p(scan["sky"]) if shape else None,
-                                   _p(scan["totals"]), _p(W), _p(B), _p(Bp), *mo)
+        tables, mo = self._scan_out(scan, nbins, spec, shape)
+        ro = _lib.EventReweightOut(_p(sample["erg"]), *tables, _p(W), _p(B), _p(Bp), *mo)
         opts = _lib.TreeOpts(0, int(mc_nodes), 0, -1, 0, 0, 0.0, 0)  # (only mc_nodes is read)
         check(self.lib.art_event_reweight_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]), C.byref(opts),
                                                  K, (C.c_double * K)(*g), C.byref(ro), _stream()))
@@ -408,17 +426,6 @@ class Engine:
     def _halo_key(base):
         """(v0, v_ns, the resolved proposal scale) of the base of a halo scan"""
         return float(base.v0), tuple(float(c) for c in base.v_ns), base.vp()
-
-    def _zero_halo_scan(self, base, models, nbins, shape, errors):
-        z = lambda *d: torch.zeros(*d, dtype=F64, device=self.device)  # noqa: E731
-        K = len(models)
-        scan = {"base": self._halo_key(base), "models": list(models),
-                "flux": z(K, 2 * nbins), "sky": z(K, *shape) if shape else None,
-                "totals": z(K, len(_lib.HALO_SCAN_TOTALS)), "n_events": 0}
-        if errors:
-            scan.update(flux_sq=z(K, 2 * nbins), flux_xa=z(K, 2 * nbins), sky_sq=z(K, *shape) if shape else None,
-                        sky_xa=z(K, *shape) if shape else None, moment_totals=z(K, len(_lib.MOMENT_TOTALS)))
-        return scan
 
     def event_halo_scan(self, sample, weight5, back, forward, base, halos, *, event_offset=0, nbins=50, sky=None,
                         scan=None, errors=False, return_ratio=False, cyclotron_rerun=None) -> dict:
@@ -438,21 +445,16 @@ class Engine:
         models = halo_scan_models(base, halos)
         K, nbins = len(models), int(nbins)
         n = sample["erg"].numel()
-        spec = shape = None
-        if sky is not None:
-            spec, shape, _ = self._sky_spec(sky)
+        spec, shape, _ = self._sky_spec(sky)
+        ident = {"base": self._halo_key(base), "models": list(models)}
         if scan is None:
-            scan = self._zero_halo_scan(base, models, nbins, shape, errors)
-        if (scan["models"] != models or scan["base"] != self._halo_key(base) or
-                scan["flux"].shape[1] != 2 * nbins or errors != ("moment_totals" in scan) or
-                (None if scan["sky"] is None else tuple(scan["sky"].shape[1:])) != shape):
+            scan = self._zero_scan(K, len(_lib.HALO_SCAN_TOTALS), nbins, shape, errors, ident)
+        if not self._scan_fits(scan, ident, nbins, shape, errors):
             raise ValueError("event_halo_scan: `scan` was made for another base, other models or other tables")
         R = self.empty(K, max(n, 1)) if return_ratio else None
         ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
-        mo = [_p(scan.get(k)) for k in ("flux_sq", "flux_xa", "sky_sq", "sky_xa", "moment_totals")]
-        ho = _lib.EventHaloScanOut(_p(sample["vifty"]), nbins, 0, _p(scan["flux"]),
-                                   C.pointer(spec) if spec is not None else None, _p(scan["sky"]) if shape else None,
-                                   _p(scan["totals"]), _p(R), *mo)
+        tables, mo = self._scan_out(scan, nbins, spec, shape)
+        ho = _lib.EventHaloScanOut(_p(sample["vifty"]), *tables, _p(R), *mo)
         arr = (_lib.ArtHalo * K)(*[_lib.ArtHalo(v0, (C.c_double * 3)(*v), -1.0) for v0, v in models])
         check(self.lib.art_event_halo_scan_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]),
                                                   C.byref(base.to_c()), K, arr, C.byref(ho), _stream()))
@@ -554,10 +556,8 @@ class Engine:
         if chunk < 1:
             raise ValueError("run_events: chunk must be >= 1")
         ncols = 29 if saveMode > 0 else 13
-        sky_hist = sky_kw = None
-        if sky_map is not None:
-            _, shape, sky_kw = self._sky_spec(sky_map)
-            sky_hist = torch.zeros(*shape, dtype=F64, device=self.device)
+        _, shape, sky_kw = self._sky_spec(sky_map)
+        sky_hist = torch.zeros(*shape, dtype=F64, device=self.device) if shape else None
         max_r = self.params.max_r()
         if max_r < self.params.rNS:
             raise ValueError("maxR < rNS: this neutron star has no conversion surface (MainRunner.jl:387-396)")
@@ -608,42 +608,34 @@ class Engine:
             ekw = {k: sky_kw[k] for k in ("n_theta", "n_phi", "n_dw", "theta_axis", "dw_range")}
             res.update(sky_map=sky_hist / div, sky_raw=sky_hist, sky_map_edges=sky_map_edges(**ekw))
         if errors:
-            from .trees import moments_sigma
+            from .trees import _sigma_info
             if moments is None:  # (no events)
-                moments = self._zero_moments(int(nbins), None if sky_hist is None else tuple(sky_hist.shape))
-            mt = moments["totals"].cpu().numpy()
-            if mt[7] != 0:
-                raise _lib.ArtError(f"run_events: {int(mt[7])} node records lie in the range of another tree")
-
-            def sigma(S, key, like):
-                """σ of the table S / f_inx, on the device in the shape of `like` (the tables are small: on the host)"""
-                Q, Cx = (moments[key + k].cpu().numpy().reshape(-1) for k in ("_sq", "_xa"))
-                s = moments_sigma(S.cpu().numpy().reshape(-1), Q, Cx, f_inx, mt[2], mt[0])
-                return torch.from_numpy(s).to(self.device).view(like.shape)
-
-            tot_sigma = moments_sigma(tot[2:4], mt[3:5], mt[5:7], f_inx, mt[2], mt[0])
-            res.update(flux_sigma=sigma(flux, "flux", res["flux"]), moments=moments,
-                       sum_weight_sln_prob_sigma=(float(tot_sigma[0]), float(tot_sigma[1])))
-            if sky_map is not None:
-                res["sky_map_sigma"] = sigma(sky_hist, "sky", sky_hist)
+                moments = self._zero_moments(int(nbins), shape)
+            host = {k: None if v is None else v.cpu().numpy() for k, v in moments.items()}
+            if host["totals"][7] != 0:
+                raise _lib.ArtError(f"run_events: {int(host['totals'][7])} node records lie in the range of another tree")
+            # (the tables are small: σ is formed on the host, as main_runner_tree forms it from the reduced ones)
+            tt = {"flux": flux.cpu().numpy(), "f_inx": f_inx, "sum_axion": tot[2], "sum_photon": tot[3], "moments": host}
+            if shape:
+                tt["sky"] = sky_hist.cpu().numpy()
+            sig = _sigma_info(tt, int(nbins))
+            res.update(flux_sigma=torch.from_numpy(sig["flux_sigma"]).to(self.device), moments=moments,
+                       sum_weight_sln_prob_sigma=sig["sum_weight_sln_prob_sigma"])
+            if shape:
+                res["sky_map_sigma"] = torch.from_numpy(sig["sky_map_sigma"]).to(self.device)
         if couplings is not None:
             from .trees import scan_raw, scan_result
-            if scan is None:  # (no events)
-                scan = self._zero_scan(couplings, int(nbins),
-                                       None if sky_hist is None else tuple(sky_hist.shape), errors)
-            res["coupling_scan"] = scan_result(scan_raw(scan), self.params.g_agg, f_inx)
-            if res["coupling_scan"]["unlinked"] != 0:
-                raise _lib.ArtError(f"run_events: {res['coupling_scan']['unlinked']} node records of the forward "
-                                    "forest have no parent, or more than one")
+            res["coupling_scan"] = self._finish_scan(
+                scan, lambda: self._zero_scan(len(couplings), len(_lib.REWEIGHT_TOTALS), int(nbins), shape, errors,
+                                              {"g": list(couplings)}),
+                lambda s: scan_result(scan_raw(s), self.params.g_agg, f_inx), "unlinked",
+                "of the forward forest have no parent, or more than one")
         if halos is not None:
             from .trees import halo_scan_raw, halo_scan_result
-            if hscan is None:  # (no events)
-                hscan = self._zero_halo_scan(halo, halos, int(nbins),
-                                             None if sky_hist is None else tuple(sky_hist.shape), errors)
-            res["halo_scan"] = halo_scan_result(halo_scan_raw(hscan), f_inx)
-            if res["halo_scan"]["misplaced"] != 0:
-                raise _lib.ArtError(f"run_events: {res['halo_scan']['misplaced']} node records lie in the range of "
-                                    "another tree")
+            res["halo_scan"] = self._finish_scan(
+                hscan, lambda: self._zero_scan(len(halos), len(_lib.HALO_SCAN_TOTALS), int(nbins), shape, errors,
+                                               {"base": self._halo_key(halo), "models": list(halos)}),
+                lambda s: halo_scan_result(halo_scan_raw(s), f_inx), "misplaced", "lie in the range of another tree")
         return res
 
     # ---- pointwise physics (parity tests)

@@ -176,6 +176,24 @@ def save_node(fh, node, tr, q):
     fh.write("".join("  " + jl(tr["times"][q, k]) for k in range(cnt)) + "\n")
 
 
+def _sky_keywords(sky_map, device_events, world):
+    """main_runner_tree's sky_map keywords completed and checked (None: no map). Without a dw_range n_dw > 1 bins
+    over the rows' own (min, max), which device_events cannot do, nor more than one process."""
+    if sky_map is None:
+        return None
+    sky_kw = {"n_theta": 32, "n_phi": 64, "n_dw": 1, "theta_axis": "cos", "dw_range": None}
+    if set(sky_map) - set(sky_kw):
+        raise ValueError(f"sky_map: unknown keys {sorted(set(sky_map) - set(sky_kw))}")
+    sky_kw.update(sky_map)
+    _theta_range(sky_kw["theta_axis"])
+    if sky_kw["n_dw"] > 1 and sky_kw["dw_range"] is None:
+        if device_events:
+            raise ValueError("sky_map: device_events bins on the device as it goes: n_dw > 1 needs a dw_range")
+        if world > 1:
+            raise ValueError("sky_map: n_dw > 1 needs a dw_range when world > 1 (the ranks' rows span different Δω)")
+    return sky_kw
+
+
 def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_DM=0.45, n_maxSample=6,
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
@@ -278,16 +296,9 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
         ntimes = 3  # "Times to store in ODE" (MainRunner.jl:379-381): also names the npy file
-    if sky_map is not None:
-        sky_kw = {"n_theta": 32, "n_phi": 64, "n_dw": 1, "theta_axis": "cos", "dw_range": None}
-        if set(sky_map) - set(sky_kw):
-            raise ValueError(f"sky_map: unknown keys {sorted(set(sky_map) - set(sky_kw))}")
-        sky_kw.update(sky_map)
-        _theta_range(sky_kw["theta_axis"])
-        if sky_kw["n_dw"] > 1 and sky_kw["dw_range"] is None and world > 1:
-            raise ValueError("sky_map: n_dw > 1 needs a dw_range when world > 1 (the ranks' rows span different Δω)")
+    sky_kw = _sky_keywords(sky_map, False, world)
     import time
-    from .shard import allreduce_sum, shard_range
+    from .shard import shard_range
     t_start = time.perf_counter()
     n_glob = max(0, int(Ntajs) - 1)
     lo, hi = shard_range(n_glob, rank, world)
@@ -356,43 +367,20 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     want_flux = len(rows) and (world > 1 or run_info is not None)
     flux = radiated_flux(rows[:, 3], rows[:, 1], rows[:, 8] * rows[:, 7], nbins) if want_flux else np.zeros(2 * nbins)
     pps = rows[:, 8] * rows[:, 7] if len(rows) else np.zeros(0)
-    sky = sky_shape = None
-    if sky_map is not None:  # the rows' sky map, the flux's weights (every rank adds its part)
-        sky_shape = (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
+    sky = None
+    if sky_kw is not None:  # the rows' sky map, the flux's weights (every rank adds its part)
         if sky_kw["n_dw"] > 1 and sky_kw["dw_range"] is None:
             sky_kw["dw_range"] = flux_range(rows[:, 12])
-        sky = np.zeros(sky_shape)
+        sky = np.zeros((2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"]))
         if len(rows):
             sky = _sky_map_rows(rows[:, 2], rows[:, 3], rows[:, 12], rows[:, 1], pps, **sky_kw)
-    mom = rows_moments(rows, lo, s["attempts"], nbins, sky_kw if sky_map is not None else None) if errors else None
+    mom = rows_moments(rows, lo, s["attempts"], nbins, sky_kw) if errors else None
     tot = pack_totals(flux, f_inx, pps[rows[:, 1] == 0].sum() if len(rows) else 0.0,
                       pps[rows[:, 1] == 1].sum() if len(rows) else 0.0, len(rows), sky, mom)
-    if world > 1:
-        tot = allreduce_sum(tot)
-    tt = unpack_totals(tot, nbins, sky_shape, moments=errors)
-    sigma = _sigma_info(tt, nbins) if errors else {}
-    f_glob = tt["f_inx"]
-    if len(rows):
-        rows[:, 7] /= f_glob  # saveAll[:, 8] ./= f_inx (:747), the whole run's f_inx
-    if run_info is not None:
-        run_info.update(f_inx=int(round(f_glob)), flux=(tt["flux"] / f_glob).reshape(2, nbins),
-                        sum_weight_sln_prob=(tt["sum_axion"] / f_glob, tt["sum_photon"] / f_glob),
-                        rows=int(round(tt["rows"])), events=(lo, hi), n_events=n_glob)
-        if sky_map is not None:
-            run_info.update(sky_map=tt["sky"] / f_glob, sky_map_edges=sky_map_edges(**sky_kw))
-        run_info.update(sigma)
-    if dir_tag is not None:
-        path = tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul, params.B0, Ntajs,
-                              ntimes, num_cutoff, MC_nodes, max_nodes, tag)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        np.save(path, rows)
-        if sky_map is not None:
-            te, pe, de = sky_map_edges(**sky_kw)
-            stem = os.path.splitext(os.path.basename(path))[0]
-            np.savez(os.path.join(os.path.dirname(path), f"skymap_{stem}.npz"), sky_map=tt["sky"] / f_glob,
-                     theta_edges=te, phi_edges=pe, dw_edges=de, theta_axis=sky_kw["theta_axis"], f_inx=int(round(f_glob)),
-                     **({"sky_map_sigma": sigma["sky_map_sigma"]} if errors else {}))
-    return rows
+    path = None if dir_tag is None else tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul,
+                                                       params.B0, Ntajs, ntimes, num_cutoff, MC_nodes, max_nodes, tag)
+    return _finish_run(rows, tot, nbins=nbins, sky_kw=sky_kw, errors=errors, world=world, run_info=run_info,
+                       events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path)
 
 
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
@@ -401,16 +389,8 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
-    from .shard import allreduce_sum, shard_range
-    sky_kw = None
-    if sky_map is not None:
-        sky_kw = {"n_theta": 32, "n_phi": 64, "n_dw": 1, "theta_axis": "cos", "dw_range": None}
-        if set(sky_map) - set(sky_kw):
-            raise ValueError(f"sky_map: unknown keys {sorted(set(sky_map) - set(sky_kw))}")
-        sky_kw.update(sky_map)
-        _theta_range(sky_kw["theta_axis"])
-        if sky_kw["n_dw"] > 1 and sky_kw["dw_range"] is None:
-            raise ValueError("sky_map: device_events bins on the device as it goes: n_dw > 1 needs a dw_range")
+    from .shard import shard_range
+    sky_kw = _sky_keywords(sky_map, True, world)
     ntimes = 3 if saveMode < 3 else 1000  # names the npy file only (main_runner_tree's default beyond saveMode 2)
     n_glob = max(0, int(Ntajs) - 1)
     lo, hi = shard_range(n_glob, rank, world)
@@ -423,48 +403,14 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                                   **({} if halos is None else {"halos": halos}))
     rows = r["rows_raw"].cpu().numpy()
     t6 = r["totals"].cpu().numpy()
-    sky_shape = None if sky_kw is None else (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
     tot = pack_totals(r["flux_raw"].cpu().numpy(), t6[4] + t6[1], t6[2], t6[3], t6[0],
                       None if sky_kw is None else r["sky_raw"].cpu().numpy(),
                       {k: (None if v is None else v.cpu().numpy()) for k, v in r["moments"].items()} if errors else None)
-    n_tot = len(tot)
-    if couplings is not None:  # the scan's raw tables follow, and only when asked for
-        tot = np.concatenate([tot, scan_pack(r["coupling_scan"]["raw"])])
-    n_cs = len(tot)
-    if halos is not None:  # then the halo scan's, likewise
-        tot = np.concatenate([tot, halo_scan_pack(r["halo_scan"]["raw"])])
-    if world > 1:
-        tot = allreduce_sum(tot)
-    tt = unpack_totals(tot[:n_tot], nbins, sky_shape, moments=errors)
-    sigma = _sigma_info(tt, nbins) if errors else {}
-    f_glob = tt["f_inx"]
-    if len(rows):
-        rows[:, 7] /= f_glob  # saveAll[:, 8] ./= f_inx (:747), the whole run's f_inx
-    if run_info is not None:
-        run_info.update(f_inx=int(round(f_glob)), flux=(tt["flux"] / f_glob).reshape(2, nbins),
-                        sum_weight_sln_prob=(tt["sum_axion"] / f_glob, tt["sum_photon"] / f_glob),
-                        rows=int(round(tt["rows"])), events=(lo, hi), n_events=n_glob)
-        if sky_kw is not None:
-            run_info.update(sky_map=tt["sky"] / f_glob, sky_map_edges=sky_map_edges(**sky_kw))
-        run_info.update(sigma)
-        if couplings is not None:
-            raw = scan_unpack(tot[n_tot:n_cs], r["coupling_scan"]["raw"])
-            run_info["coupling_scan"] = scan_result(raw, params.g_agg, int(round(f_glob)))
-        if halos is not None:
-            raw = halo_scan_unpack(tot[n_cs:], r["halo_scan"]["raw"])
-            run_info["halo_scan"] = halo_scan_result(raw, int(round(f_glob)))
-    if dir_tag is not None:
-        path = tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul, params.B0, Ntajs,
-                              ntimes, num_cutoff, MC_nodes, max_nodes, tag)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        np.save(path, rows)
-        if sky_kw is not None:
-            te, pe, de = sky_map_edges(**sky_kw)
-            stem = os.path.splitext(os.path.basename(path))[0]
-            np.savez(os.path.join(os.path.dirname(path), f"skymap_{stem}.npz"), sky_map=tt["sky"] / f_glob,
-                     theta_edges=te, phi_edges=pe, dw_edges=de, theta_axis=sky_kw["theta_axis"], f_inx=int(round(f_glob)),
-                     **({"sky_map_sigma": sigma["sky_map_sigma"]} if errors else {}))
-    return rows
+    path = None if dir_tag is None else tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul,
+                                                       params.B0, Ntajs, ntimes, num_cutoff, MC_nodes, max_nodes, tag)
+    return _finish_run(rows, tot, None if couplings is None else r["coupling_scan"]["raw"],
+                       None if halos is None else r["halo_scan"]["raw"], nbins=nbins, sky_kw=sky_kw, errors=errors,
+                       world=world, run_info=run_info, events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path)
 
 
 def cyclotron_optical_depth(params: Params, fin, erg) -> np.ndarray:
@@ -764,24 +710,30 @@ def reweight_back(x_root, bweight, scales, x_single=None):
 SCAN_KEYS = ("flux", "sky", "totals", "flux_sq", "flux_xa", "sky_sq", "sky_xa", "moment_totals")
 
 
-def scan_raw(scan) -> dict:
-    """Engine.event_reweight's dict with its tables on the host (numpy): what adds over chunks and ranks"""
+def _scan_raw(scan, **ident) -> dict:
+    """A scan's dict (Engine.event_reweight's or event_halo_scan's) with its tables on the host (numpy): what adds
+    over chunks and ranks, then `ident`, what the scan was made for, and the number of events"""
     out = {k: (None if scan[k] is None else (scan[k].cpu().numpy() if hasattr(scan[k], "cpu") else np.asarray(scan[k])))
            for k in SCAN_KEYS if k in scan}
-    out.update(g=[float(v) for v in scan["g"]], n_events=int(scan["n_events"]))
+    out.update(**ident, n_events=int(scan["n_events"]))
     return out
 
 
+def scan_raw(scan) -> dict:
+    """Engine.event_reweight's dict with its tables on the host (numpy): what adds over chunks and ranks"""
+    return _scan_raw(scan, g=[float(v) for v in scan["g"]])
+
+
 def scan_pack(raw) -> np.ndarray:
-    """A rank's coupling-scan tables (scan_raw) as one vector for the run's all-reduce: the tables there
+    """A rank's scan tables (scan_raw, halo_scan_raw) as one vector for the run's all-reduce: the tables there
     are, in SCAN_KEYS' order, then the number of events."""
     parts = [np.asarray(raw[k], np.float64).reshape(-1) for k in SCAN_KEYS if raw.get(k) is not None]
     return np.concatenate(parts + [np.array([float(raw["n_events"])])])
 
 
-def scan_unpack(vec, like) -> dict:
-    """scan_pack's vector back into a dict shaped like `like` (the rank's own scan_raw)"""
-    out, at = {"g": list(like["g"])}, 0
+def _scan_unpack(vec, like) -> dict:
+    """scan_pack's vector back into tables shaped like those of `like` (the rank's own raw dict), and n_events"""
+    out, at = {}, 0
     for k in SCAN_KEYS:
         if k not in like:
             continue
@@ -794,6 +746,35 @@ def scan_unpack(vec, like) -> dict:
     return out
 
 
+def scan_unpack(vec, like) -> dict:
+    """scan_pack's vector back into a dict shaped like `like` (the rank's own scan_raw)"""
+    return {"g": list(like["g"]), **_scan_unpack(vec, like)}
+
+
+def _scan_result(raw, K, f_inx, first, own) -> dict:
+    """What scan_result and halo_scan_result share, from raw tables over K sets: flux (K, 2, nbins) and sky_map,
+    divided by f_inx, sum_weight_sln_prob (K, 2), f_inx, raw, and with moment tables the three σ per set
+    (moments_sigma; the bins, a_e and f_inx are the run's own for every set). first: the scan's keys before these;
+    own(tot): its keys from its totals (K, their width). Returns (the dict, tot, the moment totals or None)."""
+    f = float(f_inx) if f_inx > 0 else 1.0
+    tot = np.asarray(raw["totals"], np.float64).reshape(K, -1)
+    nbins = raw["flux"].shape[1] // 2
+    res = {**first, "flux": (raw["flux"] / f).reshape(K, 2, nbins), "sum_weight_sln_prob": tot[:, 0:2] / f, **own(tot),
+           "f_inx": int(f_inx), "raw": raw}
+    if raw.get("sky") is not None:
+        res["sky_map"] = raw["sky"] / f
+    if raw.get("moment_totals") is None:
+        return res, tot, None
+    mt = np.asarray(raw["moment_totals"], np.float64).reshape(K, -1)
+    sig = lambda S, Q, Cx, k: moments_sigma(S, Q, Cx, f_inx, mt[k, 2], mt[k, 0])  # noqa: E731
+    res["flux_sigma"] = np.stack([sig(raw["flux"][k], raw["flux_sq"][k], raw["flux_xa"][k], k)
+                                  for k in range(K)]).reshape(K, 2, nbins)
+    res["sum_weight_sln_prob_sigma"] = np.stack([sig(tot[k, 0:2], mt[k, 3:5], mt[k, 5:7], k) for k in range(K)])
+    if raw.get("sky") is not None:
+        res["sky_map_sigma"] = np.stack([sig(raw["sky"][k], raw["sky_sq"][k], raw["sky_xa"][k], k) for k in range(K)])
+    return res, tot, mt
+
+
 def scan_result(raw, g0, f_inx) -> dict:
     """The coupling scan of a run from its raw tables (scan_raw, summed over the ranks) and the run's
     f_inx: g, scale = (g / g0)² (K), flux (K, 2, nbins) and sky_map (K, the map's shape; with a map), both
@@ -803,24 +784,10 @@ def scan_result(raw, g0, f_inx) -> dict:
     recomputed_differs, raw, and with moment tables flux_sigma, sky_map_sigma, sum_weight_sln_prob_sigma
     per coupling (moments_sigma; the bins, a_e and f_inx are those of the g0 run for every coupling)."""
     g = np.array(raw["g"], np.float64)
-    K, f = len(g), float(f_inx) if f_inx > 0 else 1.0
     q = g / float(g0)
-    tot = np.asarray(raw["totals"], np.float64).reshape(K, -1)
-    nbins = raw["flux"].shape[1] // 2
-    res = {"g": g, "scale": q * q, "flux": (raw["flux"] / f).reshape(K, 2, nbins), "sum_weight_sln_prob": tot[:, 0:2] / f,
-           "coverage": tot[:, 2] / max(int(raw["n_events"]), 1), "saturated": int(round(tot[0, 3])),
-           "unlinked": int(round(tot[0, 4])), "recomputed_differs": int(round(tot[0, 5])), "f_inx": int(f_inx), "raw": raw}
-    if raw.get("sky") is not None:
-        res["sky_map"] = raw["sky"] / f
-    if raw.get("moment_totals") is not None:
-        mt = np.asarray(raw["moment_totals"], np.float64).reshape(K, -1)
-        sig = lambda S, Q, Cx, k: moments_sigma(S, Q, Cx, f_inx, mt[k, 2], mt[k, 0])  # noqa: E731
-        res["flux_sigma"] = np.stack([sig(raw["flux"][k], raw["flux_sq"][k], raw["flux_xa"][k], k)
-                                      for k in range(K)]).reshape(K, 2, nbins)
-        res["sum_weight_sln_prob_sigma"] = np.stack([sig(tot[k, 0:2], mt[k, 3:5], mt[k, 5:7], k) for k in range(K)])
-        if raw.get("sky") is not None:
-            res["sky_map_sigma"] = np.stack([sig(raw["sky"][k], raw["sky_sq"][k], raw["sky_xa"][k], k) for k in range(K)])
-    return res
+    return _scan_result(raw, len(g), f_inx, {"g": g, "scale": q * q}, lambda tot: {
+        "coverage": tot[:, 2] / max(int(raw["n_events"]), 1), "saturated": int(round(tot[0, 3])),
+        "unlinked": int(round(tot[0, 4])), "recomputed_differs": int(round(tot[0, 5]))})[0]
 
 
 def coupling_curve(scan, species=PHOTON):
@@ -914,10 +881,7 @@ def halo_scan_tables(rows_raw, ratio, nbins, sky_kw=None, event_lo=0) -> dict:
 
 def halo_scan_raw(scan) -> dict:
     """Engine.event_halo_scan's dict with its tables on the host (numpy): what adds over chunks and ranks"""
-    out = {k: (None if scan[k] is None else (scan[k].cpu().numpy() if hasattr(scan[k], "cpu") else np.asarray(scan[k])))
-           for k in SCAN_KEYS if k in scan}
-    out.update(models=[_halo_of(h) for h in scan["models"]], n_events=int(scan["n_events"]))
-    return out
+    return _scan_raw(scan, models=[_halo_of(h) for h in scan["models"]])
 
 
 def halo_scan_pack(raw) -> np.ndarray:
@@ -927,10 +891,7 @@ def halo_scan_pack(raw) -> np.ndarray:
 
 def halo_scan_unpack(vec, like) -> dict:
     """halo_scan_pack's vector back into a dict shaped like `like` (the rank's own halo_scan_raw)"""
-    out = scan_unpack(vec, dict(like, g=()))
-    del out["g"]
-    out["models"] = list(like["models"])
-    return out
+    return {**_scan_unpack(vec, like), "models": list(like["models"])}
 
 
 def halo_scan_result(raw, f_inx) -> dict:
@@ -942,22 +903,9 @@ def halo_scan_result(raw, f_inx) -> dict:
     bins, a_e and f_inx are the run's own for every model) and n_eff (K) = S_photon² / Q_photon, the Kish
     effective number of events behind the photon total: a small n_eff says the model lies far from the base."""
     models = list(raw["models"])
-    K, f = len(models), float(f_inx) if f_inx > 0 else 1.0
-    tot = np.asarray(raw["totals"], np.float64).reshape(K, -1)
-    nbins = raw["flux"].shape[1] // 2
-    res = {"models": models, "flux": (raw["flux"] / f).reshape(K, 2, nbins), "sum_weight_sln_prob": tot[:, 0:2] / f,
-           "ratio_sum": tot[:, 2].copy(), "ratio_sq": tot[:, 3].copy(), "misplaced": int(round(tot[0, 4])),
-           "f_inx": int(f_inx), "raw": raw}
-    if raw.get("sky") is not None:
-        res["sky_map"] = raw["sky"] / f
-    if raw.get("moment_totals") is not None:
-        mt = np.asarray(raw["moment_totals"], np.float64).reshape(K, -1)
-        sig = lambda S, Q, Cx, k: moments_sigma(S, Q, Cx, f_inx, mt[k, 2], mt[k, 0])  # noqa: E731
-        res["flux_sigma"] = np.stack([sig(raw["flux"][k], raw["flux_sq"][k], raw["flux_xa"][k], k)
-                                      for k in range(K)]).reshape(K, 2, nbins)
-        res["sum_weight_sln_prob_sigma"] = np.stack([sig(tot[k, 0:2], mt[k, 3:5], mt[k, 5:7], k) for k in range(K)])
-        if raw.get("sky") is not None:
-            res["sky_map_sigma"] = np.stack([sig(raw["sky"][k], raw["sky_sq"][k], raw["sky_xa"][k], k) for k in range(K)])
+    res, tot, mt = _scan_result(raw, len(models), f_inx, {"models": models}, lambda tot: {
+        "ratio_sum": tot[:, 2].copy(), "ratio_sq": tot[:, 3].copy(), "misplaced": int(round(tot[0, 4]))})
+    if mt is not None:
         with np.errstate(divide="ignore", invalid="ignore"):
             res["n_eff"] = tot[:, 1] * tot[:, 1] / mt[:, 4]
     return res
@@ -1060,6 +1008,56 @@ def _sigma_info(tt, nbins) -> dict:
     if "sky" in tt:
         out["sky_map_sigma"] = moments_sigma(tt["sky"], mo["sky_sq"], mo["sky_xa"], f, t8[2], t8[0])
     return out
+
+
+def rank_vector(totals, coupling_raw=None, halo_raw=None):
+    """A rank's vector for main_runner_tree's single all-reduce, [pack_totals | coupling scan | halo scan]: the
+    rank's pack_totals vector, then scan_pack of its coupling scan's raw tables and halo_scan_pack of its halo
+    scan's, each only when there is one. Returns (the vector, where each of its parts ends)."""
+    parts = [totals] + [pack(raw) for pack, raw in ((scan_pack, coupling_raw), (halo_scan_pack, halo_raw)) if raw is not None]
+    return (np.concatenate(parts) if len(parts) > 1 else totals), np.cumsum([len(v) for v in parts])
+
+
+def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw, errors, world, run_info, events, n_events,
+                g0, path):
+    """The end of main_runner_tree on every path: the rank's vector (rank_vector of its pack_totals vector and its
+    scans' raw tables) summed over the ranks in ONE all-reduce, σ from the reduced tables, column 8 of the rank's
+    rows divided by the global f_inx, run_info (a dict or None; events: the rank's (lo, hi), n_events: the run's),
+    and with `path` the npy file and, with a sky map, skymap_<its stem>.npz beside it. g0: the run's coupling, the
+    coupling scan's base. Returns the rows."""
+    from .shard import allreduce_sum
+    tot, ends = rank_vector(totals, coupling_raw, halo_raw)
+    if world > 1:
+        tot = allreduce_sum(tot)
+    sky_shape = None if sky_kw is None else (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
+    tt = unpack_totals(tot[:ends[0]], nbins, sky_shape, moments=errors)
+    sigma = _sigma_info(tt, nbins) if errors else {}
+    f_glob = tt["f_inx"]
+    if len(rows):
+        rows[:, 7] /= f_glob  # saveAll[:, 8] ./= f_inx (MainRunner.jl:747), the whole run's f_inx
+    if run_info is not None:
+        run_info.update(f_inx=int(round(f_glob)), flux=(tt["flux"] / f_glob).reshape(2, nbins),
+                        sum_weight_sln_prob=(tt["sum_axion"] / f_glob, tt["sum_photon"] / f_glob),
+                        rows=int(round(tt["rows"])), events=events, n_events=n_events)
+        if sky_kw is not None:
+            run_info.update(sky_map=tt["sky"] / f_glob, sky_map_edges=sky_map_edges(**sky_kw))
+        run_info.update(sigma)
+        if coupling_raw is not None:
+            raw = scan_unpack(tot[ends[0]:ends[1]], coupling_raw)
+            run_info["coupling_scan"] = scan_result(raw, g0, int(round(f_glob)))
+        if halo_raw is not None:
+            raw = halo_scan_unpack(tot[ends[-2]:], halo_raw)
+            run_info["halo_scan"] = halo_scan_result(raw, int(round(f_glob)))
+    if path is not None:
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        np.save(path, rows)
+        if sky_kw is not None:
+            te, pe, de = sky_map_edges(**sky_kw)
+            stem = os.path.splitext(os.path.basename(path))[0]
+            np.savez(os.path.join(os.path.dirname(path), f"skymap_{stem}.npz"), sky_map=tt["sky"] / f_glob,
+                     theta_edges=te, phi_edges=pe, dw_edges=de, theta_axis=sky_kw["theta_axis"], f_inx=int(round(f_glob)),
+                     **({"sky_map_sigma": sigma["sky_map_sigma"]} if errors else {}))
+    return rows
 
 
 def gather_rank_rows(dir_tag, params: Params, Ntajs, world, file_tag="", ntimes=3, num_cutoff=5, MC_nodes=5,

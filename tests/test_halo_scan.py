@@ -350,3 +350,68 @@ def test_pack_round_trip_and_result():
     # a misplaced record shows in the result
     tot[:, 4] = 2.0
     assert trees.halo_scan_result(raw, 20)["misplaced"] == 2
+
+
+def _same(a, b):
+    """deep equality of scan results: dicts by key order, arrays bit for bit (NaN equal to NaN)"""
+    if isinstance(a, dict):
+        return isinstance(b, dict) and list(a) == list(b) and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.shape == b.shape and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
+    if isinstance(a, (list, tuple)):
+        return type(a) is type(b) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    return a == b
+
+
+def test_rank_vector_layout_and_finish(monkeypatch):
+    """The reduced vector of a run with a sky map, errors, two couplings and two halo models is
+    [pack_totals | coupling scan | halo scan], and the finish both drivers share turns its sum over two ranks into
+    the run_info that scan_result and halo_scan_result give for the doubled tables."""
+    from adiabatic_raytracer_amd import shard, trees
+    K, nbins, shape = 2, 4, (2, 2, 3, 1)
+    rng = np.random.default_rng(11)
+    tab = lambda *s: rng.random(s) + 0.5  # noqa: E731
+    mom = {"flux_sq": tab(2 * nbins), "flux_xa": tab(2 * nbins), "sky_sq": tab(*shape), "sky_xa": tab(*shape),
+           "totals": np.array([6.0, 30.0, 170.0, 0.4, 0.8, 1.5, 2.5, 0.0])}
+    flux, sky, f_inx = tab(2 * nbins), tab(*shape), 30
+    tot = trees.pack_totals(flux, f_inx, 1.25, 2.5, 7, sky, mom)
+
+    def scan_tables(width):
+        t = {"flux": tab(K, 2 * nbins), "sky": tab(K, *shape), "totals": tab(K, width), "flux_sq": tab(K, 2 * nbins),
+             "flux_xa": tab(K, 2 * nbins), "sky_sq": tab(K, *shape), "sky_xa": tab(K, *shape),
+             "moment_totals": np.tile(mom["totals"], (K, 1)), "n_events": 6}
+        t["totals"][:, 3:] = 0.0  # (the counters: saturated, unlinked, ... and misplaced)
+        return t
+
+    craw = trees.scan_raw({"g": [1e-12, 3e-12], **scan_tables(6)})
+    hraw = trees.halo_scan_raw({"models": [BASE, TARGETS[0]], **scan_tables(5)})
+    vec, ends = trees.rank_vector(tot, craw, hraw)
+    want = np.concatenate([tot, trees.scan_pack(craw), trees.halo_scan_pack(hraw)])
+    assert vec.dtype == np.float64 and vec.tobytes() == want.tobytes()
+    assert list(ends) == [len(tot), len(tot) + len(trees.scan_pack(craw)), len(want)]
+    # without the scans the vector is the totals' own, and one scan alone follows them directly
+    assert trees.rank_vector(tot)[0] is tot
+    assert trees.rank_vector(tot, None, hraw)[0].tobytes() == np.concatenate([tot, trees.halo_scan_pack(hraw)]).tobytes()
+
+    monkeypatch.setattr(shard, "allreduce_sum", lambda v: 2.0 * v)  # two ranks with the same tables
+    sky_kw = {"n_theta": 2, "n_phi": 3, "n_dw": 1, "theta_axis": "cos", "dw_range": None}
+    rows0 = tab(3, 13)
+    info = {}
+    rows = trees._finish_run(rows0.copy(), tot, craw, hraw, nbins=nbins, sky_kw=sky_kw, errors=True, world=2, run_info=info,
+                             events=(0, 6), n_events=12, g0=1e-12, path=None)
+    assert np.array_equal(rows[:, 7], rows0[:, 7] / 60.0) and np.array_equal(np.delete(rows, 7, 1), np.delete(rows0, 7, 1))
+    assert list(info) == ["f_inx", "flux", "sum_weight_sln_prob", "rows", "events", "n_events", "sky_map", "sky_map_edges",
+                          "flux_sigma", "sum_weight_sln_prob_sigma", "sky_map_sigma", "coupling_scan", "halo_scan"]
+    assert info["f_inx"] == 60 and info["rows"] == 14 and info["events"] == (0, 6) and info["n_events"] == 12
+    assert np.array_equal(info["flux"], (2.0 * flux / 60.0).reshape(2, nbins)) and np.array_equal(info["sky_map"], 2.0 * sky / 60.0)
+    assert info["sum_weight_sln_prob"] == (2.5 / 60.0, 5.0 / 60.0)
+    assert np.array_equal(info["flux_sigma"].reshape(-1),
+                          trees.moments_sigma(2.0 * flux, 2.0 * mom["flux_sq"], 2.0 * mom["flux_xa"], 60, 340.0, 12.0))
+
+    def doubled(raw):
+        return {k: (2 * v if k == "n_events" else 2.0 * v if isinstance(v, np.ndarray) else v) for k, v in raw.items()}
+
+    assert _same(info["coupling_scan"], trees.scan_result(trees.scan_unpack(trees.scan_pack(doubled(craw)), craw), 1e-12, 60))
+    assert _same(info["halo_scan"], trees.halo_scan_result(trees.halo_scan_unpack(trees.halo_scan_pack(doubled(hraw)), hraw), 60))
+    assert _same(info["coupling_scan"]["raw"]["sky_xa"], 2.0 * craw["sky_xa"]) and info["halo_scan"]["raw"]["n_events"] == 12
+    assert info["halo_scan"]["n_eff"].shape == (K,) and info["coupling_scan"]["unlinked"] == 0

@@ -208,6 +208,44 @@ int main() {
     ho.moment_totals = nullptr;
     ei.n_events = ei.n_nodes = 0;
     CHECK(art_event_halo_scan_device(&p, &ei, nullptr, &hb, 32, hm, &ho, nullptr) == ART_OK);
+    // where the four event calls differ on purpose (art_post.cpp's front-end flags). A call that passes its
+    // argument checks goes on to the device, which this container does not have.
+    auto went_on = [](int r) { return r == ART_E_HIP || r == ART_E_NOMEM || r == ART_OK; };
+    auto said = [](const char* what) { return std::strstr(art_last_error(), what) != nullptr; };
+    // an empty chunk with nodes and no node_start: moments returns before it looks, the scans look first
+    mo.sky = nullptr;
+    ei.n_events = 0; ei.n_nodes = 4;
+    CHECK(art_event_moments_device(&p, &ei, nullptr, &mo, nullptr) == ART_OK);
+    CHECK(art_event_reweight_device(&p, &ei, nullptr, &to, 2, g, &ro, nullptr) == ART_E_INVALID && said("node_start is NULL"));
+    CHECK(art_event_halo_scan_device(&p, &ei, nullptr, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID && said("node_start is NULL"));
+    // only the rows call looks at the spec's mode
+    art_sky_spec odd{4, 8, 1, 1, 7, 0.0, 0.0};
+    ei.n_nodes = 0;
+    eo.sky = &odd; mo.sky = &odd; ro.sky = &odd; ho.sky = &odd;
+    CHECK(art_event_rows_device(&p, &ei, &eo, nullptr) == ART_E_INVALID && said("sky map mode"));
+    CHECK(art_event_moments_device(&p, &ei, nullptr, &mo, nullptr) == ART_OK);
+    CHECK(art_event_reweight_device(&p, &ei, nullptr, &to, 2, g, &ro, nullptr) == ART_OK);
+    CHECK(art_event_halo_scan_device(&p, &ei, nullptr, &hb, 2, hm, &ho, nullptr) == ART_OK);
+    eo.sky = mo.sky = ro.sky = ho.sky = nullptr;
+    // cyc_slot with a batch and its cyc_tau but no end states: rows and moments refuse, the scans need cyc_tau alone
+    std::vector<art_tree_node> nd(4);
+    ei.n_events = ei.n_nodes = 4;
+    ei.x = ei.k_init = ei.weight5 = d; ei.attempts = ai.data();
+    ei.back = ei.nodes = nd.data(); ei.back_counts = ei.counts = ei.infos = st.data();
+    ei.cyc_slot = st.data(); ei.cyc_n = 2; ei.cyc_tau = d; ei.cyc_end = nullptr;
+    eo.ncols = 13; eo.row_capacity = 4; eo.flux = eo.totals = d;
+    CHECK(art_event_rows_device(&p, &ei, &eo, nullptr) == ART_E_INVALID && said("the re-run's end states"));
+    CHECK(art_event_moments_device(&p, &ei, ns, &mo, nullptr) == ART_E_INVALID && said("the re-run's end states"));
+    CHECK(went_on(art_event_reweight_device(&p, &ei, ns, &to, 2, g, &ro, nullptr)));
+    CHECK(went_on(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, hm, &ho, nullptr)));
+    ei.cyc_tau = nullptr;  // (that much the scans do ask for, in their own words)
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 2, g, &ro, nullptr) == ART_E_INVALID && said("cyc_n >= 0 and cyc_tau"));
+    CHECK(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, hm, &ho, nullptr) == ART_E_INVALID && said("cyc_n >= 0 and cyc_tau"));
+    // events without nodes: the coupling scan still reads its per-event buffers, the halo scan only vifty
+    ei.cyc_slot = nullptr; ei.cyc_n = 0;
+    ei.n_nodes = 0; ei.weight5 = nullptr;
+    CHECK(art_event_reweight_device(&p, &ei, ns, &to, 2, g, &ro, nullptr) == ART_E_INVALID && said("NULL input buffer"));
+    CHECK(went_on(art_event_halo_scan_device(&p, &ei, ns, &hb, 2, hm, &ho, nullptr)));
   }
   // the device forest: every argument check comes before the device; with roots it reaches the HIP runtime
   {
