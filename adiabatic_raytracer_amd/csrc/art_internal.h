@@ -387,4 +387,18 @@ struct EventHaloScanArgs {
 };
 hipError_t launch_event_halo_scan(const EventRowsArgs& a, const EventHaloScanArgs& h, const SkyAxes& A, int cos_axis,
                                   hipStream_t s);
+// The jackknife replicates (art_event_replicates_device; the kernel of art_event_replicates.h): the inputs are an
+// EventRowsArgs (its outputs unused) and the forest's node_start; kind says whose powers the n_k sets take (0 the
+// run's own, 1 a coupling scan's from node_factor (n_k n_nodes) and event_factor (n_k n_events), 2 a halo scan's
+// from event_factor). flux, sky (sky_size per set and group; null: none) and totals hold set k's group g at
+// k n_groups + g times the usual size; groups is 3 per group.
+struct EventReplicatesArgs {
+  const int64_t* node_start;
+  int32_t n_groups, kind, n_k, nbins;
+  int64_t sky_size;
+  const double *node_factor, *event_factor;
+  double *flux, *sky, *totals, *groups;
+};
+hipError_t launch_event_replicates(const EventRowsArgs& a, const EventReplicatesArgs& r, const SkyAxes& A, int cos_axis,
+                                   hipStream_t s);
 }  // namespace art

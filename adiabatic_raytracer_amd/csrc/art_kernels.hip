@@ -1151,3 +1151,8 @@ hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_a
 // and group as the event moments do
 #define ART_EVENT_HALOSCAN_KERNELS
 #include "art_event_haloscan.h"
+
+// The jackknife replicates (art_event_replicates_device): the header's kernel, which bins as the event rows do and
+// takes the scans' powers as the scans do
+#define ART_EVENT_REPLICATES_KERNELS
+#include "art_event_replicates.h"

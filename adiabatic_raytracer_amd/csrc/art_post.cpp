@@ -1,6 +1,6 @@
 // art_post.cpp -- the entry points around the propagate calls (declared in include/art.h): the
 // non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows, event moments, the coupling
-// scan, the halo scan and the eval entry points the tests compare against the oracle. Each checks its arguments, then
+// scan, the halo scan, the jackknife replicates and the eval entry points the tests compare against the oracle. Each checks its arguments, then
 // launches on the caller's stream (or stages through the context's pool, the *_host ones).
 #include <algorithm>
 #include <cmath>
@@ -8,6 +8,7 @@
 #include <string>
 
 #include "art_event_moments.h"
+#include "art_event_replicates.h"
 #include "art_event_reweight.h"
 #include "art_event_rows.h"
 #include "art_host.h"
@@ -720,6 +721,45 @@ int art_event_halo_scan_device(const art_params* p, const art_event_rows_in* in,
   const hipError_t e = art::launch_event_halo_scan(a, h, S.A, S.cos_axis, s);
   (void)hipFreeAsync(block, s);
   HIP_OK(e);
+  return ART_OK;
+}
+
+// The jackknife replicates of a chunk (include/art.h): the run's, a coupling scan's or a halo scan's first-moment
+// tables per group of events (art_event_replicates.h), one kernel on `stream`.
+int art_event_replicates_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                                const art_event_replicates_out* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
+  if (out->n_groups < art::REPLICATES_MIN_GROUPS || out->n_groups > art::REPLICATES_MAX_GROUPS)
+    return fail(ART_E_INVALID, "n_groups must be in [2, 64]");
+  if (out->kind < 0 || out->kind >= art::REP_KIND_COUNT)
+    return fail(ART_E_INVALID, "kind must be 0 (the run), 1 (a coupling scan) or 2 (a halo scan)");
+  if (out->n_sets < 1 || out->n_sets > art::REPLICATES_MAX_SETS) return fail(ART_E_INVALID, "n_sets must be in [1, 32]");
+  if (out->kind == art::REP_KIND_RUN && out->n_sets != 1) return fail(ART_E_INVALID, "n_sets must be 1 with kind 0");
+  if (out->kind == art::REP_KIND_COUPLING && in->n_nodes > 0 && !out->node_factor)
+    return fail(ART_E_INVALID, "node_factor is NULL (kind 1: the coupling scan's weights)");
+  if (out->kind != art::REP_KIND_RUN && !out->event_factor)
+    return fail(ART_E_INVALID, "event_factor is NULL (kind 1: the coupling scan's back, kind 2: the halo scan's ratio)");
+  if ((rc = event_in_ranges(in)) || (rc = event_out_ranges(0, out->nbins))) return rc;  // (no reserved field)
+  EventSky S;
+  if ((rc = event_sky(out->sky, /*honour_mode=*/false, out->nbins, &S))) return rc;  // (tables in HBM: no mode)
+  if (in->n_events == 0) return ART_OK;
+  if (!out->totals || !out->groups) return fail(ART_E_INVALID, "totals or groups is NULL");
+  if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
+  if (out->sky && !out->sky_hist) return fail(ART_E_INVALID, "sky_hist is NULL");
+  // IN_NODE_START_LATE and IN_CYC_END_STATES: the moments call's checks, whose chunk and re-run this call is handed;
+  // the kernel reads cyc_tau alone.
+  if ((rc = event_in_buffers(in, node_start, IN_NODE_START_LATE | IN_CYC_END_STATES))) return rc;
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  const art::EventRowsArgs a = event_args(p, in, /*end_states=*/false);
+  art::EventReplicatesArgs r{};
+  r.node_start = node_start; r.n_groups = out->n_groups; r.kind = out->kind; r.n_k = out->n_sets; r.nbins = out->nbins;
+  r.sky_size = S.size; r.node_factor = out->node_factor; r.event_factor = out->event_factor;
+  r.flux = out->flux; r.sky = out->sky ? out->sky_hist : nullptr; r.totals = out->totals; r.groups = out->groups;
+  HIP_OK(art::launch_event_replicates(a, r, S.A, S.cos_axis, (hipStream_t)stream));
   return ART_OK;
 }
 

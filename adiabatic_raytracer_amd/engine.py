@@ -463,6 +463,71 @@ class Engine:
             scan["ratio"] = R[:, :n]
         return scan
 
+    # The most bytes the replicate tables of one set of tables (the run's, a coupling scan's or a halo scan's) may take
+    REPLICATES_MAX_BYTES = 1 << 30
+
+    @staticmethod
+    def _replicates_groups(R):
+        """The group count of replicates= as an int, checked as art_event_replicates_device checks it"""
+        if int(R) != R or not _lib.REPLICATES_MIN_GROUPS <= int(R) <= _lib.REPLICATES_MAX_GROUPS:
+            raise ValueError(f"replicates: {_lib.REPLICATES_MIN_GROUPS} to {_lib.REPLICATES_MAX_GROUPS} groups, not {R!r}")
+        return int(R)
+
+    @classmethod
+    def _replicates_fit(cls, what, K, R, nbins, shape):
+        """ValueError when the replicate tables of K sets and R groups exceed REPLICATES_MAX_BYTES"""
+        sky = 1
+        for d in shape or (0,):
+            sky *= d
+        size = 8 * K * R * (2 * nbins + sky + 2)
+        if size > cls.REPLICATES_MAX_BYTES:
+            raise ValueError(f"replicates: the replicate tables of {what} ({K} sets x {R} groups) would take {size} bytes, "
+                             f"more than {cls.REPLICATES_MAX_BYTES}: drop the sky map from the scan or lower R")
+
+    def _zero_replicates(self, kind, K, R, nbins, shape):
+        z = lambda *d: torch.zeros(*d, dtype=F64, device=self.device)  # noqa: E731
+        return {"kind": kind, "R": R, "flux": z(K, R, 2 * nbins), "sky": z(K, R, *shape) if shape else None,
+                "totals": z(K, R, 2), "groups": z(R, len(_lib.REPLICATE_GROUPS))}
+
+    def event_replicates(self, sample, weight5, back, forward, R, *, event_offset=0, nbins=50, sky=None,
+                         cyclotron_rerun=None, rep=None, kind="run", node_factor=None, event_factor=None) -> dict:
+        """The jackknife replicates of one chunk (art_event_replicates_device; DESIGN.md §3, "Jackknife
+        replicates"), on the current stream and without a synchronisation: the arguments of event_rows for the same
+        chunk, whose first-moment tables it keeps per group of events, g = (event_offset + tree) mod R (2 <= R <= 64).
+        kind "run": the run's own powers, one set. kind "coupling": the powers of a coupling scan, from
+        node_factor = event_reweight(return_weights=True)'s "weights" (K, n_nodes) and event_factor = its "back"
+        (K, n_events). kind "halo": those of a halo scan, from event_factor = event_halo_scan(return_ratio=True)'s
+        "ratio" (K, n_events). Returns a dict of device tensors, float64: flux (K, R, 2 nbins), sky (K, R, the map's
+        shape; None without sky), totals (K, R, 2: Σ power of all final axion and photon rows) and groups (R, 3:
+        events, a_g = Σ (attempts - 1) + final photon rows, misplaced records -- _lib.REPLICATE_GROUPS), with kind and
+        R. rep: such a dict of an earlier chunk, ACCUMULATED into and returned. cyclotron_rerun: event_rows'
+        "cyclotron_rerun" of this chunk, so exp(-τ) is in the powers. trees.jackknife turns the tables into errors."""
+        R, nbins = self._replicates_groups(R), int(nbins)
+        if kind not in _lib.REPLICATE_KINDS:
+            raise ValueError(f"event_replicates: kind must be one of {sorted(_lib.REPLICATE_KINDS)}, not {kind!r}")
+        if (kind == "coupling" and node_factor is None) or (kind != "run" and event_factor is None):
+            raise ValueError(f"event_replicates: kind {kind!r} needs its factor arrays")
+        K = 1 if kind == "run" else int(event_factor.shape[0])
+        spec, shape, _ = self._sky_spec(sky)
+        if rep is None:
+            rep = self._zero_replicates(kind, K, R, nbins, shape)
+        if (rep["kind"] != kind or tuple(rep["flux"].shape) != (K, R, 2 * nbins) or
+                (None if rep["sky"] is None else tuple(rep["sky"].shape[2:])) != shape):
+            raise ValueError("event_replicates: `rep` was made for another kind, other groups, sets or tables")
+        n, nn = sample["erg"].numel(), int(forward["n_nodes"])
+        if kind != "run" and (tuple(event_factor.shape) != (K, n) or not event_factor.is_contiguous()):
+            raise ValueError("event_replicates: event_factor must be a contiguous (K, n_events) tensor")
+        if kind == "coupling" and (tuple(node_factor.shape) != (K, nn) or (nn > 0 and not node_factor.is_contiguous())):
+            raise ValueError("event_replicates: node_factor must be a contiguous (K, n_nodes) tensor")
+        ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
+        ro = _lib.EventReplicatesOut(R, _lib.REPLICATE_KINDS[kind], K, nbins, _p(node_factor) if kind == "coupling" else None,
+                                     _p(event_factor) if kind != "run" else None, _p(rep["flux"]),
+                                     C.pointer(spec) if spec is not None else None, _p(rep["sky"]) if shape else None,
+                                     _p(rep["totals"]), _p(rep["groups"]))
+        check(self.lib.art_event_replicates_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]), C.byref(ro),
+                                                   _stream()))
+        return rep
+
     def _cyclotron_rerun(self, sample, forward, nn, n):
         """The final photon segments of a forward forest, packed (art_event_gather_photons_device) and run
         again with the cyclotron observation: slot per node, the batch size m, its tau and end states."""
@@ -486,7 +551,7 @@ class Engine:
 
     def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
                    max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
-                   cyclotron=False, rows=True, halo=None, errors=False, couplings=None, halos=None) -> dict:
+                   cyclotron=False, rows=True, halo=None, errors=False, couplings=None, halos=None, replicates=None) -> dict:
         """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
         n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
         event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
@@ -537,6 +602,15 @@ class Engine:
         couplings= in the same run scans the couplings at the base halo and the halos at the base coupling.
         None (the default): exactly the keys below.
 
+        replicates (a group count R, 2 to 64; DESIGN.md §3, "Jackknife replicates"): the run's first-moment tables are
+        also kept per group of events, g = global event id mod R (event_replicates per chunk), and the result gets
+        "replicates", trees.replicates_result's dict of host arrays, from which trees.jackknife gives the value, σ and
+        covariance of ANY function of the tables -- a pulse profile summed over Δω, a band power, a ratio. With
+        couplings= or halos= the scan's dict gets "replicates" too, with the scan's leading axis (the scans are then
+        called with return_weights / return_ratio), so correlated read-offs such as trees.coupling_crossing have an
+        error. It needs neither rows nor errors=True. Replicate tables of more than Engine.REPLICATES_MAX_BYTES (1 GiB)
+        per set of tables are a ValueError before any work is done. None (the default): exactly the keys below.
+
         Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
         or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
         f_inx, sum_weight_sln_prob, n_rows, n_photon_rows, and the raw, undivided parts for a caller that
@@ -545,6 +619,8 @@ class Engine:
         tensor `rows` is a divided copy of)."""
         from dataclasses import replace
         from .trees import AXION, PHOTON, halo_scan_models, sky_map_edges
+        if replicates is not None:
+            replicates = Engine._replicates_groups(replicates)  # (before any work is done)
         if halos is not None:
             halos = halo_scan_models(halo, halos)  # (before any work is done)
         n_events = int(n_events)
@@ -557,6 +633,11 @@ class Engine:
             raise ValueError("run_events: chunk must be >= 1")
         ncols = 29 if saveMode > 0 else 13
         _, shape, sky_kw = self._sky_spec(sky_map)
+        if replicates is not None:  # (before any work is done)
+            for what, K in (("the run", 1), ("the coupling scan", couplings and len(couplings)),
+                            ("the halo scan", halos and len(halos))):
+                if K:
+                    self._replicates_fit(what, K, replicates, int(nbins), shape)
         sky_hist = torch.zeros(*shape, dtype=F64, device=self.device) if shape else None
         max_r = self.params.max_r()
         if max_r < self.params.rNS:
@@ -565,7 +646,8 @@ class Engine:
         flux = torch.zeros(2 * int(nbins), dtype=F64, device=self.device)
         totals = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
         parts = []
-        moments = scan = hscan = None
+        moments = scan = hscan = rep = crep = hrep = None
+        want = replicates is not None
         for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
             c = min(chunk, int(event_offset) + n_events - lo)
             s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r, halo=halo)
@@ -581,10 +663,22 @@ class Engine:
                                              cyclotron_rerun=r["cyclotron_rerun"])
             if couplings is not None:
                 scan = self.event_reweight(s, w5, back, fwd, couplings, mc_nodes=MC_nodes, event_offset=lo, nbins=nbins,
-                                           sky=sky_map, errors=errors, cyclotron_rerun=r["cyclotron_rerun"], scan=scan)
+                                           sky=sky_map, errors=errors, cyclotron_rerun=r["cyclotron_rerun"], scan=scan,
+                                           **({"return_weights": True} if want else {}))
             if halos is not None:
                 hscan = self.event_halo_scan(s, w5, back, fwd, halo, halos, event_offset=lo, nbins=nbins, sky=sky_map,
-                                             errors=errors, cyclotron_rerun=r["cyclotron_rerun"], scan=hscan)
+                                             errors=errors, cyclotron_rerun=r["cyclotron_rerun"], scan=hscan,
+                                             **({"return_ratio": True} if want else {}))
+            if want:
+                kw = dict(event_offset=lo, nbins=nbins, sky=sky_map, cyclotron_rerun=r["cyclotron_rerun"])
+                rep = self.event_replicates(s, w5, back, fwd, replicates, rep=rep, **kw)
+                if couplings is not None:
+                    crep = self.event_replicates(s, w5, back, fwd, replicates, rep=crep, kind="coupling",
+                                                 node_factor=scan.pop("weights"), event_factor=scan.pop("back"), **kw)
+                    del scan["back_prob"]
+                if halos is not None:
+                    hrep = self.event_replicates(s, w5, back, fwd, replicates, rep=hrep, kind="halo",
+                                                 event_factor=hscan.pop("ratio"), **kw)
             if rows:
                 parts.append(r["rows"] if len(r["rows"]) * 2 >= fwd["n_nodes"] else r["rows"].clone())
         tot = totals.cpu().numpy()
@@ -636,6 +730,17 @@ class Engine:
                 hscan, lambda: self._zero_scan(len(halos), len(_lib.HALO_SCAN_TOTALS), int(nbins), shape, errors,
                                                {"base": self._halo_key(halo), "models": list(halos)}),
                 lambda s: halo_scan_result(halo_scan_raw(s), f_inx), "misplaced", "lie in the range of another tree")
+        if want:
+            from .trees import replicates_raw, replicates_result
+            for out, have, kind, K in ((res, rep, "run", 1), (res.get("coupling_scan"), crep, "coupling", len(couplings or ())),
+                                       (res.get("halo_scan"), hrep, "halo", len(halos or ()))):
+                if out is None:
+                    continue
+                have = self._zero_replicates(kind, K, replicates, int(nbins), shape) if have is None else have  # (no events)
+                out["replicates"] = replicates_result(replicates_raw(have), f_inx)
+                if out["replicates"]["misplaced"] != 0:
+                    raise _lib.ArtError(f"run_events: {out['replicates']['misplaced']} node records lie in the range of "
+                                        "another tree")
         return res
 
     # ---- pointwise physics (parity tests)

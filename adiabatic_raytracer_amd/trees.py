@@ -198,7 +198,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
                      sky_map=None, device_trees=False, device_events=False, halo=None, errors=False,
-                     couplings=None, halos=None):
+                     couplings=None, halos=None, replicates=None):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -275,7 +275,17 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     (Engine.run_events(halos=); DESIGN.md §3, "Halo scan"). run_info["halo_scan"] is halo_scan_result's dict from
     the tables summed over the ranks, which follow everything else in the same all-reduce; the rows and files
     are those of `halo`. With the default None every row, file, run_info key and the reduced vector are
-    unchanged."""
+    unchanged.
+
+    replicates (beyond the reference; a group count R, 2 to 64; DESIGN.md §3, "Jackknife replicates"): the run's
+    first-moment tables per group of events, g = global event id mod R, on all three paths: run_info["replicates"] is
+    replicates_result's dict from the tables summed over the ranks, which end the vector of the same all-reduce, and
+    jackknife(run_info["replicates"], fn) gives the value and error of any function of the flux, the sky map and the
+    totals. The host paths take the tables from the rows (rows_replicates with the sampler's attempts); device_events
+    takes them from art_event_replicates_device, and there the scans' dicts get "replicates" too. With the default
+    None every row, file, run_info key and the reduced vector are unchanged."""
+    if replicates is not None and not _lib.REPLICATES_MIN_GROUPS <= int(replicates) <= _lib.REPLICATES_MAX_GROUPS:
+        raise ValueError(f"replicates: {_lib.REPLICATES_MIN_GROUPS} to {_lib.REPLICATES_MAX_GROUPS} groups, not {replicates!r}")
     if couplings is not None and not device_events:
         raise ValueError("couplings: the coupling scan reweights forests held in HBM and needs device_events=True")
     if halos is not None:
@@ -291,7 +301,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                                         prob_cutoff=prob_cutoff, saveMode=saveMode, dir_tag=dir_tag, file_tag=file_tag,
                                         backtrace_cap=backtrace_cap, rank=rank, world=world, nbins=nbins, run_info=run_info,
                                         cyclotron=cyclotron, sky_map=sky_map, halo=halo, errors=errors,
-                                        couplings=couplings, halos=halos)
+                                        couplings=couplings, halos=halos, replicates=replicates)
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -379,13 +389,14 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                       pps[rows[:, 1] == 1].sum() if len(rows) else 0.0, len(rows), sky, mom)
     path = None if dir_tag is None else tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul,
                                                        params.B0, Ntajs, ntimes, num_cutoff, MC_nodes, max_nodes, tag)
+    rep = None if replicates is None else {"run": rows_replicates(rows, replicates, nbins, sky_kw, s["attempts"], lo)}
     return _finish_run(rows, tot, nbins=nbins, sky_kw=sky_kw, errors=errors, world=world, run_info=run_info,
-                       events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path)
+                       events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path, **({} if rep is None else {"replicates": rep}))
 
 
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
                              saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map,
-                             halo=None, errors=False, couplings=None, halos=None):
+                             halo=None, errors=False, couplings=None, halos=None, replicates=None):
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
@@ -400,7 +411,12 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                                   backtrace_cap=backtrace_cap, rho_DM=rho_DM, n_maxSample=n_maxSample, nbins=nbins,
                                   sky_map=sky_kw, cyclotron=cyclotron, rows=True, halo=halo, errors=errors,
                                   **({} if couplings is None else {"couplings": couplings}),
-                                  **({} if halos is None else {"halos": halos}))
+                                  **({} if halos is None else {"halos": halos}),
+                                  **({} if replicates is None else {"replicates": replicates}))
+    rep = None
+    if replicates is not None:
+        rep = {"run": r["replicates"]["raw"]}
+        rep.update({k: r[k + "_scan"]["replicates"]["raw"] for k in ("coupling", "halo") if k + "_scan" in r})
     rows = r["rows_raw"].cpu().numpy()
     t6 = r["totals"].cpu().numpy()
     tot = pack_totals(r["flux_raw"].cpu().numpy(), t6[4] + t6[1], t6[2], t6[3], t6[0],
@@ -410,7 +426,8 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                                                        params.B0, Ntajs, ntimes, num_cutoff, MC_nodes, max_nodes, tag)
     return _finish_run(rows, tot, None if couplings is None else r["coupling_scan"]["raw"],
                        None if halos is None else r["halo_scan"]["raw"], nbins=nbins, sky_kw=sky_kw, errors=errors,
-                       world=world, run_info=run_info, events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path)
+                       world=world, run_info=run_info, events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path,
+                       **({} if rep is None else {"replicates": rep}))
 
 
 def cyclotron_optical_depth(params: Params, fin, erg) -> np.ndarray:
@@ -962,6 +979,179 @@ def rows_moments(rows, event_lo, attempts, nbins, sky_kw=None) -> dict:
     return out
 
 
+REPLICATE_KEYS = ("flux", "sky", "totals", "groups")
+
+
+def rows_replicates(rows, R, nbins, sky_kw=None, attempts=None, event_lo=0, n_events=None) -> dict:
+    """art_event_replicates_device's tables in numpy from npy rows (column 7 raw or divided alike: the tables are in
+    the powers' own units): the oracle of the device tables, and the path for row files written earlier. The group
+    of a row is (column 0 - 1) mod R, its event's 0-based global id mod R (2 <= R <= 64). Returns the raw dict of
+    one set (kind "run"): flux (1, R, 2 nbins), sky (1, R, 2, n_theta, n_phi, n_dw; None without sky_kw), totals
+    (1, R, 2: Σ power of all axion and photon rows) and groups (R, 3: the events n_g, a_g, 0). attempts (the
+    sampler's, of the events event_lo .. event_lo + len(attempts)): a_g = Σ_e (attempts - 1 + the event's photon
+    rows), whose sum is the f_inx of these events. attempts=None, for row files, which do not store them: a_e is
+    taken constant, as moments_sigma(trials=None) takes it (a_g = n_g; jackknife scales it to f_inx), over the
+    events event_lo .. event_lo + n_events (n_events=None: up to the last event that has a row)."""
+    rows = np.asarray(rows, np.float64)
+    R, nbins, lo = int(R), int(nbins), int(event_lo)
+    if not _lib.REPLICATES_MIN_GROUPS <= R <= _lib.REPLICATES_MAX_GROUPS:
+        raise ValueError(f"replicates: {_lib.REPLICATES_MIN_GROUPS} to {_lib.REPLICATES_MAX_GROUPS} groups, not {R}")
+    gid = np.rint(rows[:, 0]).astype(np.int64) - 1  # the 0-based global id
+    if attempts is not None:
+        n = len(attempts)
+    elif n_events is not None:
+        n = int(n_events)
+    else:
+        n = int(gid.max()) + 1 - lo if len(rows) else 0
+    if len(rows) and (gid.min() < lo or gid.max() >= lo + n):
+        raise ValueError("rows_replicates: a row's event lies outside event_lo .. event_lo + n_events")
+    g = gid % R
+    sp = (rows[:, 1] != 0).astype(np.int64)
+    p = rows[:, 8] * rows[:, 7]
+    ev_g = np.arange(lo, lo + n, dtype=np.int64) % R
+    groups = np.zeros((R, len(_lib.REPLICATE_GROUPS)))
+    groups[:, 0] = np.bincount(ev_g, minlength=R)
+    if attempts is None:
+        groups[:, 1] = groups[:, 0]
+    else:
+        groups[:, 1] = (np.bincount(ev_g, weights=np.asarray(attempts, np.int64) - 1, minlength=R)
+                        + np.bincount(g[sp == 1], minlength=R))
+    fb = hist_bins(rows[:, 3], nbins) if nbins > 0 else np.full(len(rows), -1)
+    labels = [("flux", np.where(fb >= 0, sp * nbins + fb, -1), 2 * nbins, (2 * nbins,)), ("totals", sp, 2, (2,))]
+    out = {"kind": "run", "R": R, "sky": None, "groups": groups}
+    if sky_kw is not None:
+        kw = {k: sky_kw[k] for k in ("n_theta", "n_phi", "n_dw", "theta_axis", "dw_range") if k in sky_kw}
+        shape = (2, kw.get("n_theta", 32), kw.get("n_phi", 64), kw.get("n_dw", 1))
+        labels.append(("sky", sky_bins(rows[:, 2], rows[:, 3], rows[:, 12], rows[:, 1], **kw), int(np.prod(shape)), shape))
+    for name, lab, size, shape in labels:
+        keep = lab >= 0
+        out[name] = np.bincount(g[keep] * size + lab[keep], weights=p[keep], minlength=R * size).reshape(1, R, *shape)
+    return out
+
+
+def replicates_raw(rep) -> dict:
+    """Engine.event_replicates' dict with its tables on the host (numpy): what adds over chunks and ranks"""
+    out = {k: (None if rep[k] is None else (rep[k].cpu().numpy() if hasattr(rep[k], "cpu") else np.asarray(rep[k])))
+           for k in REPLICATE_KEYS}
+    out.update(kind=rep["kind"], R=int(rep["R"]))
+    return out
+
+
+def replicates_pack(raw) -> np.ndarray:
+    """A rank's replicate tables (replicates_raw, rows_replicates) as one vector for the run's all-reduce: the tables
+    there are, in REPLICATE_KEYS' order"""
+    return np.concatenate([np.asarray(raw[k], np.float64).reshape(-1) for k in REPLICATE_KEYS if raw.get(k) is not None])
+
+
+def replicates_unpack(vec, like) -> dict:
+    """replicates_pack's vector back into a dict shaped like `like` (the rank's own raw dict)"""
+    out, at = {"kind": like["kind"], "R": like["R"]}, 0
+    for k in REPLICATE_KEYS:
+        if like.get(k) is None:
+            out[k] = None
+            continue
+        out[k] = np.asarray(vec[at:at + like[k].size], np.float64).reshape(like[k].shape)
+        at += like[k].size
+    return out
+
+
+def _replicate_tables(flux, sky, totals, f, squeeze):
+    """The normalised tables jackknife hands to fn: flux (K, 2, nbins), sky_map, sum_weight_sln_prob (K, 2), each
+    divided by f (NaN where f is 0); squeeze: without the leading axis (the plain run's one set)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        div = (lambda t: t / f) if f != 0 else (lambda t: np.full(t.shape, np.nan))
+        t = {"flux": div(flux.reshape(flux.shape[0], 2, flux.shape[-1] // 2)), "sum_weight_sln_prob": div(totals)}
+        if sky is not None:
+            t["sky_map"] = div(sky)
+    return {k: v[0] for k, v in t.items()} if squeeze else t
+
+
+def replicates_result(raw, f_inx) -> dict:
+    """The jackknife replicates of a run from its raw tables (replicates_raw or rows_replicates, summed over the
+    ranks) and the run's f_inx: R, kind, n_g and a_g (R), misplaced (records outside their tree's range, which must
+    be 0), f_inx, raw, and the full estimates jackknife's fn is handed -- flux (2, nbins), sky_map (with a map) and
+    sum_weight_sln_prob (2), the tables summed over the groups and divided by f_inx, with a scan's leading K axis
+    where there is one. trees.jackknife(result, fn) gives the value and error of fn of these."""
+    groups = np.asarray(raw["groups"], np.float64)
+    S = {k: (None if raw.get(k) is None else np.asarray(raw[k], np.float64).sum(axis=1)) for k in ("flux", "sky", "totals")}
+    res = {"R": int(raw["R"]), "kind": raw["kind"], "n_g": groups[:, 0].copy(), "a_g": groups[:, 1].copy(),
+           "misplaced": int(round(groups[:, 2].sum())), "f_inx": int(f_inx), "raw": raw}
+    res.update(_replicate_tables(S["flux"], S["sky"], S["totals"], float(f_inx), raw["kind"] == "run"))
+    return res
+
+
+def jackknife(rep, fn, cov=False) -> dict:
+    """The delete-a-group jackknife of fn over a run's replicates (replicates_result's dict: run_events' or run_info's
+    "replicates", or a scan's). fn gets a dict of normalised tables -- flux (2, nbins), sky_map (2, n_theta, n_phi,
+    n_dw; with a map) and sum_weight_sln_prob (2), with a scan's leading K axis where there is one -- and returns a
+    number or an array: a pulse profile summed over Δω, a band power, a ratio of two bins or of two models, the g
+    where a curve crosses a threshold. With S a table summed over the groups, T_g its group g, f = f_inx and a_g the
+    group's part of it (scaled so that Σ_g a_g = f, which changes nothing when the attempts were counted):
+        value   = fn(S / f),      θ_g = fn((S - T_g) / (f - a_g)),
+        sigma   = sqrt((R' - 1) / R' Σ_g (θ_g - mean θ)²)    over the R' groups that hold events,
+    and with cov the covariance (R' - 1) / R' Σ_g (θ_g - mean)(θ_g - mean)ᵀ of the flattened result, whose diagonal
+    is sigma². groups_used is R'. sigma is NaN with R' < 2 and where a leave-out divisor is 0. The two estimates of
+    one scatter, this one and moments_sigma's, differ by a relative noise of order sqrt(2 / (R' - 1)); under
+    heavy-tailed weights both are biased low alike."""
+    raw, f = rep["raw"], float(rep["f_inx"])
+    groups = np.asarray(raw["groups"], np.float64)
+    n_g, a_g = groups[:, 0], groups[:, 1]
+    squeeze = raw["kind"] == "run"
+    T = {k: (None if raw.get(k) is None else np.asarray(raw[k], np.float64)) for k in ("flux", "sky", "totals")}
+    S = {k: (None if v is None else v.sum(axis=1)) for k, v in T.items()}
+    value = np.asarray(fn(_replicate_tables(S["flux"], S["sky"], S["totals"], f, squeeze)), np.float64)
+    used = np.flatnonzero(n_g > 0)
+    out = {"value": value, "groups_used": int(used.size)}
+    a_sum = a_g.sum()
+    scale = f / a_sum if a_sum > 0 else 0.0
+    theta = []
+    for g in used:
+        left = {k: (None if v is None else S[k] - v[:, g]) for k, v in T.items()}
+        theta.append(np.asarray(fn(_replicate_tables(left["flux"], left["sky"], left["totals"], f - a_g[g] * scale, squeeze)),
+                                np.float64).reshape(-1))
+    if used.size < 2:
+        out["sigma"] = np.full(value.shape, np.nan)
+        if cov:
+            out["cov"] = np.full((value.size, value.size), np.nan)
+        return out
+    theta = np.stack(theta)
+    d = theta - theta.mean(axis=0)
+    c = (used.size - 1.0) / used.size
+    out["sigma"] = np.sqrt(c * (d * d).sum(axis=0)).reshape(value.shape)
+    if cov:
+        out["cov"] = c * (d.T @ d)
+    return out
+
+
+def _loglog_crossing(g, P, power):
+    """The g at which the curve P(g), given at the points g (any order), first crosses `power` going up the sorted g,
+    by linear interpolation of log P in log g; NaN where it does not cross"""
+    g, P = np.asarray(g, np.float64), np.asarray(P, np.float64)
+    order = np.argsort(g)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x, y, y0 = np.log(g[order]), np.log(P[order]), math.log(power)
+    for i in range(len(x) - 1):
+        lo, hi = sorted((y[i], y[i + 1]))
+        if np.isfinite(lo) and np.isfinite(hi) and lo <= y0 <= hi and lo < hi:
+            return float(np.exp(x[i] + (y0 - y[i]) / (y[i + 1] - y[i]) * (x[i + 1] - x[i])))
+    return float("nan")
+
+
+def coupling_crossing(scan, power, species=PHOTON) -> dict:
+    """The coupling g at which the radiated power of `species` equals `power` (> 0), from a coupling scan made with
+    replicates (run_events' or run_info's "coupling_scan"): log-log interpolation of coupling_curve between the two
+    neighbouring couplings that bracket it, and its jackknife error. The K points of a scan are reweightings of the
+    same events and strongly correlated, so this error cannot be had from the per-point σ. Returns jackknife's dict:
+    value (NaN where the curve does not reach `power`), sigma, groups_used."""
+    if not (power > 0.0 and math.isfinite(power)):
+        raise ValueError("coupling_crossing: power must be finite and > 0")
+    if "replicates" not in scan:
+        raise ValueError("coupling_crossing: the scan has no replicates (run_events(couplings=, replicates=R))")
+    sp = 0 if species == AXION else 1
+    g = np.asarray(scan["g"], np.float64)
+    return jackknife(scan["replicates"], lambda t: _loglog_crossing(g, t["sum_weight_sln_prob"][:, sp], power))
+
+
 def pack_totals(flux, f_inx, sum_axion, sum_photon, n_rows, sky=None, moments=None) -> np.ndarray:
     """A rank's part of main_runner_tree's single all-reduce: [flux (2 nbins) | f_inx | Σ weight *
     sln_prob (axions, photons) | rows], then the sky map's table when there is one, then with moments
@@ -1010,23 +1200,31 @@ def _sigma_info(tt, nbins) -> dict:
     return out
 
 
-def rank_vector(totals, coupling_raw=None, halo_raw=None):
-    """A rank's vector for main_runner_tree's single all-reduce, [pack_totals | coupling scan | halo scan]: the
-    rank's pack_totals vector, then scan_pack of its coupling scan's raw tables and halo_scan_pack of its halo
-    scan's, each only when there is one. Returns (the vector, where each of its parts ends)."""
+REPLICATE_PARTS = ("run", "coupling", "halo")  # the order of the replicate parts of a rank's vector
+
+
+def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None):
+    """A rank's vector for main_runner_tree's single all-reduce, [pack_totals | coupling scan | halo scan |
+    replicates...]: the rank's pack_totals vector, then scan_pack of its coupling scan's raw tables and halo_scan_pack
+    of its halo scan's, each only when there is one, then replicates_pack of each raw dict of `replicates` (a dict
+    with the keys "run", "coupling", "halo" there are, in that order; None: none), so every earlier part keeps its
+    place. Returns (the vector, where each of its parts ends)."""
     parts = [totals] + [pack(raw) for pack, raw in ((scan_pack, coupling_raw), (halo_scan_pack, halo_raw)) if raw is not None]
+    parts += [replicates_pack(replicates[k]) for k in REPLICATE_PARTS if replicates and replicates.get(k) is not None]
     return (np.concatenate(parts) if len(parts) > 1 else totals), np.cumsum([len(v) for v in parts])
 
 
 def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw, errors, world, run_info, events, n_events,
-                g0, path):
+                g0, path, replicates=None):
     """The end of main_runner_tree on every path: the rank's vector (rank_vector of its pack_totals vector and its
     scans' raw tables) summed over the ranks in ONE all-reduce, σ from the reduced tables, column 8 of the rank's
     rows divided by the global f_inx, run_info (a dict or None; events: the rank's (lo, hi), n_events: the run's),
     and with `path` the npy file and, with a sky map, skymap_<its stem>.npz beside it. g0: the run's coupling, the
-    coupling scan's base. Returns the rows."""
+    coupling scan's base. replicates: the rank's raw replicate tables (rank_vector's keyword), which end the vector
+    and come back as run_info["replicates"] and as "replicates" in the scans' dicts. Returns the rows."""
     from .shard import allreduce_sum
-    tot, ends = rank_vector(totals, coupling_raw, halo_raw)
+    tot, ends = rank_vector(totals, coupling_raw, halo_raw, replicates=replicates)
+    n_scans = (coupling_raw is not None) + (halo_raw is not None)
     if world > 1:
         tot = allreduce_sum(tot)
     sky_shape = None if sky_kw is None else (2, sky_kw["n_theta"], sky_kw["n_phi"], sky_kw["n_dw"])
@@ -1046,8 +1244,13 @@ def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw
             raw = scan_unpack(tot[ends[0]:ends[1]], coupling_raw)
             run_info["coupling_scan"] = scan_result(raw, g0, int(round(f_glob)))
         if halo_raw is not None:
-            raw = halo_scan_unpack(tot[ends[-2]:], halo_raw)
+            raw = halo_scan_unpack(tot[ends[n_scans - 1]:ends[n_scans]], halo_raw)
             run_info["halo_scan"] = halo_scan_result(raw, int(round(f_glob)))
+        have = [k for k in REPLICATE_PARTS if replicates and replicates.get(k) is not None]
+        for j, k in enumerate(have):
+            raw = replicates_unpack(tot[ends[n_scans + j]:ends[n_scans + j + 1]], replicates[k])
+            where = run_info if k == "run" else run_info[k + "_scan"]
+            where["replicates"] = replicates_result(raw, int(round(f_glob)))
     if path is not None:
         os.makedirs(os.path.dirname(path), exist_ok=True)
         np.save(path, rows)

@@ -746,6 +746,43 @@ int art_event_halo_scan_device(const art_params* p, const art_event_rows_in* in,
                                const art_halo* base, int32_t n_models, const art_halo* models,
                                const art_event_halo_scan_out* out, void* stream);
 
+/* ---- jackknife replicates: the first-moment tables per group of events, for the error of ANY function of them ----
+ * The events of a run are split into n_groups groups by global id, g = (event_offset + tree) mod n_groups (in a
+ * row file (column 0 - 1) mod n_groups); the events are independent draws keyed by that id, so the groups are
+ * exchangeable and do not depend on the chunks or the ranks. Per set k and group g the call ADDS the powers of g's
+ * final rows to flux[k][g], sky_hist[k][g] and totals[k][g] (2: Σ power of all final axion rows and of all final
+ * photon rows, binned or not), in art_event_rows_device's bins, and per group alone to groups[g] (3): [0] the
+ * events n_g, [1] a_g = Σ_e a_e with art_event_moments_device's a_e = (attempts[e] - 1) + (final photon rows of
+ * e), so Σ_g a_g is the run's f_inx (attempts NULL: the photon rows only), [2] the records inside the forest's
+ * range that lie in the range of a tree other than their own (skipped; must stay 0). The powers by kind:
+ *   0  the run's own, column 8 * column 7 (exp(-τ) included with the cyclotron fields of `in`); n_sets = 1;
+ *   1  a coupling scan's, W_k B_k [exp(-τ)] sln_prob, from node_factor = art_event_reweight_out::weights and
+ *      event_factor = art_event_reweight_out::back of the same chunk;
+ *   2  a halo scan's, column 8 * column 7 times R_k, from event_factor = art_event_halo_scan_out::ratio.
+ * With S a table summed over the groups, T_g its group g and f = Σ_g a_g, the estimate of a function φ is
+ * φ(S / f), its leave-one-out g is φ((S - T_g) / (f - a_g)), and σ² = (R' - 1) / R' Σ_g (θ_g - mean θ)² over
+ * the R' groups with n_g > 0. Everything adds over chunks and ranks. */
+typedef struct art_event_replicates_out {
+  int32_t n_groups;            /* R, 2 .. 64                                                          */
+  int32_t kind;                /* 0 the run, 1 a coupling scan, 2 a halo scan                         */
+  int32_t n_sets;              /* K, 1 .. 32; 1 with kind 0                                           */
+  int32_t nbins;               /* flux bins over [-π, π], 0 .. 4096 (0: no flux table)               */
+  const double* node_factor;   /* K * n_nodes  INPUT, kind 1: W_k of every record                    */
+  const double* event_factor;  /* K * n_events INPUT, kind 1: B_k; kind 2: R_k of every event         */
+  double* flux;                /* K * R * 2 nbins                                                     */
+  const art_sky_spec* sky;     /* NULL: no sky map; mode is ignored                                   */
+  double* sky_hist;            /* K * R * 2 n_theta n_phi n_dw                                        */
+  double* totals;              /* K * R * 2                                                           */
+  double* groups;              /* R * 3: n_g, a_g, misplaced records                                  */
+} art_event_replicates_out;
+/* Asynchronous on `stream`, no host read and no scratch. Every table is ordinary device memory and takes float64
+ * hardware adds. ART_E_INVALID before any device is touched: a NULL p, in or out; n_groups outside 2 .. 64; an
+ * unknown kind; n_sets outside 1 .. 32, or not 1 with kind 0; a NULL event_factor with kind 1 or 2, a NULL
+ * node_factor with kind 1 and n_nodes > 0; art_event_moments_device's faults on nbins, the sky spec and
+ * node_start; a NULL table that the call needs. n_events == 0: ART_OK, nothing touched. */
+int art_event_replicates_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                                const art_event_replicates_out* out, void* stream);
+
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the
  * other ranks (a file, MPI, the launcher); every rank then calls art_comm_init on its device.

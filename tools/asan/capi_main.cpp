@@ -208,6 +208,38 @@ int main() {
     ho.moment_totals = nullptr;
     ei.n_events = ei.n_nodes = 0;
     CHECK(art_event_halo_scan_device(&p, &ei, nullptr, &hb, 32, hm, &ho, nullptr) == ART_OK);
+    // the jackknife replicates: the group count, the kind, the sets and its factor arrays, then the moments call's
+    // checks, all before the device
+    art_event_replicates_out po{};
+    po.n_groups = 8; po.kind = 0; po.n_sets = 1; po.nbins = 50; po.flux = po.totals = po.groups = d;
+    ei.n_events = ei.n_nodes = 4;
+    CHECK(art_event_replicates_device(nullptr, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    CHECK(art_event_replicates_device(&p, nullptr, ns, &po, nullptr) == ART_E_INVALID);
+    CHECK(art_event_replicates_device(&p, &ei, ns, nullptr, nullptr) == ART_E_INVALID);
+    for (int bad_groups : {-1, 0, 1, 65}) {
+      po.n_groups = bad_groups;
+      CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    }
+    po.n_groups = 64; po.kind = 3;
+    CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    po.kind = 0; po.n_sets = 2;  // the run has one set
+    CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    po.kind = 1; po.n_sets = 33; po.node_factor = po.event_factor = d;
+    CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    po.n_sets = 32; po.node_factor = nullptr;  // a coupling scan's weights
+    CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    po.kind = 2; po.event_factor = nullptr;  // a halo scan's ratios
+    CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    po.kind = 0; po.n_sets = 1;
+    CHECK(art_event_replicates_device(&p, &ei, nullptr, &po, nullptr) == ART_E_INVALID);  // node_start
+    po.sky = &sk;  // n_dw = 4 without a range
+    CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    po.sky = &full;  // a good spec without its table
+    CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    po.sky = nullptr; po.groups = nullptr;
+    CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
+    ei.n_events = ei.n_nodes = 0;
+    CHECK(art_event_replicates_device(&p, &ei, nullptr, &po, nullptr) == ART_OK);
     // where the four event calls differ on purpose (art_post.cpp's front-end flags). A call that passes its
     // argument checks goes on to the device, which this container does not have.
     auto went_on = [](int r) { return r == ART_E_HIP || r == ART_E_NOMEM || r == ART_OK; };

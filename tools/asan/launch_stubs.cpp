@@ -84,6 +84,9 @@ hipError_t launch_event_reweight(const KParams&, const KParams&, const EventRows
 hipError_t launch_event_halo_scan(const EventRowsArgs&, const EventHaloScanArgs&, const SkyAxes&, int, hipStream_t) {
   return hipErrorNoDevice;
 }
+hipError_t launch_event_replicates(const EventRowsArgs&, const EventReplicatesArgs&, const SkyAxes&, int, hipStream_t) {
+  return hipErrorNoDevice;
+}
 MFn nl_eval_math(int) { return nullptr; }
 hipError_t launch_eval_math(int, int, int64_t, const double*, const double*, double*, double*, hipStream_t) {
   return hipErrorNoDevice;
