@@ -87,6 +87,17 @@ REPLICATE_GROUPS = ("events", "a", "misplaced")
 REPLICATE_KINDS = {"run": 0, "coupling": 1, "halo": 2}
 REPLICATES_MIN_GROUPS, REPLICATES_MAX_GROUPS = 2, 64
 
+class EventGridOut(C.Structure):  # include/art.h art_event_grid_out
+    _fields_ = [("n_couplings", C.c_int32), ("n_models", C.c_int32), ("nbins", C.c_int32), ("n_groups", C.c_int32),
+                ("node_factor", C.c_void_p), ("back", C.c_void_p), ("ratio", C.c_void_p), ("flux", C.c_void_p),
+                ("totals", C.c_void_p), ("flux_rep", C.c_void_p), ("totals_rep", C.c_void_p), ("groups", C.c_void_p),
+                ("moment_totals", C.c_void_p)]
+
+
+# art_event_grid_out::totals, per cell; the limits of its two axes
+GRID_TOTALS = ("sum_axion", "sum_photon", "misplaced")
+GRID_MAX_COUPLINGS, GRID_MAX_MODELS = 32, 32
+
 EVENT_TOTALS = ("rows", "photon_rows", "sum_axion", "sum_photon", "attempts_minus_1", "cyclotron_mismatches")
 # art_event_moments_out::totals
 MOMENT_TOTALS = ("events", "A1", "A2", "Q_axion", "Q_photon", "C_axion", "C_photon", "bad_nodes")
@@ -173,6 +184,7 @@ SIGNATURES = {
                                             C.POINTER(EventReweightOut), _v]),
     "art_event_halo_scan_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, _H, _i32, _H, C.POINTER(EventHaloScanOut), _v]),
     "art_event_replicates_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventReplicatesOut), _v]),
+    "art_event_grid_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventGridOut), _v]),
     "art_comm_unique_id": (C.c_int, [_v]),
     "art_comm_init": (C.c_int, [_i32, _i32, _v]),
     "art_flux_allreduce": (C.c_int, [_v, _i64, _v]),

@@ -401,4 +401,16 @@ struct EventReplicatesArgs {
 };
 hipError_t launch_event_replicates(const EventRowsArgs& a, const EventReplicatesArgs& r, const SkyAxes& A, int cos_axis,
                                    hipStream_t s);
+// The coupling x halo grid (art_event_grid_device; the kernel of art_event_grid.h): the inputs are an EventRowsArgs
+// (its outputs unused), the forest's node_start and the factors of the two scans of the same chunk, W (n_g n_nodes),
+// B (n_g n_events) and R (n_h n_events). The tables are cell-minor (art_event_grid.h): flux (2 nbins x C), totals
+// (3 x C), and with n_groups > 0 flux_rep (n_groups x 2 nbins x C), totals_rep (n_groups x 2 x C) and groups (3 per
+// group); mtotals (8 x C) null: no moment sums.
+struct EventGridArgs {
+  const int64_t* node_start;
+  int32_t n_g, n_h, nbins, n_groups;
+  const double *W, *B, *R;
+  double *flux, *totals, *flux_rep, *totals_rep, *groups, *mtotals;
+};
+hipError_t launch_event_grid(const EventRowsArgs& a, const EventGridArgs& r, hipStream_t s);
 }  // namespace art

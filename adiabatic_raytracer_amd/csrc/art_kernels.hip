@@ -1156,3 +1156,8 @@ hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_a
 // takes the scans' powers as the scans do
 #define ART_EVENT_REPLICATES_KERNELS
 #include "art_event_replicates.h"
+
+// The coupling x halo grid (art_event_grid_device): the header's kernel, which bins as the event rows do and takes
+// the two scans' factors
+#define ART_EVENT_GRID_KERNELS
+#include "art_event_grid.h"

@@ -1,12 +1,13 @@
 // art_post.cpp -- the entry points around the propagate calls (declared in include/art.h): the
 // non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows, event moments, the coupling
-// scan, the halo scan, the jackknife replicates and the eval entry points the tests compare against the oracle. Each checks its arguments, then
+// scan, the halo scan, the jackknife replicates, the coupling x halo grid and the eval entry points the tests compare against the oracle. Each checks its arguments, then
 // launches on the caller's stream (or stages through the context's pool, the *_host ones).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <string>
 
+#include "art_event_grid.h"
 #include "art_event_moments.h"
 #include "art_event_replicates.h"
 #include "art_event_reweight.h"
@@ -760,6 +761,44 @@ int art_event_replicates_device(const art_params* p, const art_event_rows_in* in
   r.sky_size = S.size; r.node_factor = out->node_factor; r.event_factor = out->event_factor;
   r.flux = out->flux; r.sky = out->sky ? out->sky_hist : nullptr; r.totals = out->totals; r.groups = out->groups;
   HIP_OK(art::launch_event_replicates(a, r, S.A, S.cos_axis, (hipStream_t)stream));
+  return ART_OK;
+}
+
+// The coupling x halo grid of a chunk (include/art.h): the first-moment tables at every (coupling, halo model) cell
+// from the two scans' factors (art_event_grid.h), one kernel on `stream`.
+int art_event_grid_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                          const art_event_grid_out* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
+  if (out->n_couplings < 1 || out->n_couplings > art::GRID_MAX_COUPLINGS)
+    return fail(ART_E_INVALID, "n_couplings must be in [1, 32]");
+  if (out->n_models < 1 || out->n_models > art::GRID_MAX_MODELS) return fail(ART_E_INVALID, "n_models must be in [1, 32]");
+  if (out->n_groups != 0 && (out->n_groups < art::REPLICATES_MIN_GROUPS || out->n_groups > art::REPLICATES_MAX_GROUPS))
+    return fail(ART_E_INVALID, "n_groups must be 0 (no replicate tables) or in [2, 64]");
+  if ((rc = event_in_ranges(in)) || (rc = event_out_ranges(0, out->nbins))) return rc;  // (no reserved field)
+  if (in->n_events == 0) return ART_OK;
+  if (!out->back || !out->ratio) return fail(ART_E_INVALID, "back or ratio is NULL (the two scans' factors per event)");
+  if (in->n_nodes > 0 && !out->node_factor) return fail(ART_E_INVALID, "node_factor is NULL (the coupling scan's weights)");
+  if (!out->totals) return fail(ART_E_INVALID, "totals is NULL");
+  if (out->nbins > 0 && !out->flux) return fail(ART_E_INVALID, "flux is NULL");
+  if (out->n_groups > 0 && (!out->totals_rep || !out->groups)) return fail(ART_E_INVALID, "totals_rep or groups is NULL");
+  if (out->n_groups > 0 && out->nbins > 0 && !out->flux_rep) return fail(ART_E_INVALID, "flux_rep is NULL");
+  // IN_NODE_START_LATE and IN_CYC_END_STATES: the moments call's checks, whose chunk and re-run this call is handed;
+  // the kernel reads cyc_tau alone.
+  if ((rc = event_in_buffers(in, node_start, IN_NODE_START_LATE | IN_CYC_END_STATES))) return rc;
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  const art::EventRowsArgs a = event_args(p, in, /*end_states=*/false);
+  art::EventGridArgs r{};
+  r.node_start = node_start; r.n_g = out->n_couplings; r.n_h = out->n_models; r.nbins = out->nbins;
+  r.n_groups = out->n_groups; r.W = out->node_factor; r.B = out->back; r.R = out->ratio;
+  r.flux = out->flux; r.totals = out->totals; r.mtotals = out->moment_totals;
+  if (out->n_groups > 0) {
+    r.flux_rep = out->flux_rep; r.totals_rep = out->totals_rep; r.groups = out->groups;
+  }
+  HIP_OK(art::launch_event_grid(a, r, (hipStream_t)stream));
   return ART_OK;
 }
 

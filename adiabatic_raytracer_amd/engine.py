@@ -528,6 +528,69 @@ class Engine:
                                                    _stream()))
         return rep
 
+    @classmethod
+    def _grid_fit(cls, Kg, Kh, R, nbins, errors):
+        """ValueError when the grid's tables -- (1 + R) copies under replicates=R, plus the moment totals -- exceed
+        REPLICATES_MAX_BYTES"""
+        C_ = Kg * Kh
+        size = 8 * (C_ * ((2 * nbins + len(_lib.GRID_TOTALS)) + (R or 0) * (2 * nbins + 2)
+                          + (len(_lib.MOMENT_TOTALS) if errors else 0)) + (R or 0) * len(_lib.REPLICATE_GROUPS))
+        if size > cls.REPLICATES_MAX_BYTES:
+            raise ValueError(f"grid: the tables of {Kg} x {Kh} cells{f' and {R} groups' if R else ''} would take {size} "
+                             f"bytes, more than {cls.REPLICATES_MAX_BYTES}: lower nbins, R or the number of cells")
+
+    def _zero_grid(self, g, models, base, R, nbins, errors):
+        """The zero tables of a grid, cell-minor as art_event_grid_out takes them (C = K_g K_h cells last)"""
+        z = lambda *d: torch.zeros(*d, dtype=F64, device=self.device)  # noqa: E731
+        C_ = len(g) * len(models)
+        grid = {"g": list(g), "models": list(models), "base": base, "R": R, "flux": z(2 * nbins, C_),
+                "totals": z(len(_lib.GRID_TOTALS), C_), "n_events": 0}
+        if R is not None:
+            grid.update(flux_rep=z(R, 2 * nbins, C_), totals_rep=z(R, 2, C_), groups=z(R, len(_lib.REPLICATE_GROUPS)))
+        if errors:
+            grid["moment_totals"] = z(len(_lib.MOMENT_TOTALS), C_)
+        return grid
+
+    def event_grid(self, sample, weight5, back, forward, *, weights, back_factor, ratio, g, models, base, event_offset=0,
+                   nbins=50, replicates=None, errors=False, cyclotron_rerun=None, grid=None) -> dict:
+        """The coupling x halo grid of one chunk (art_event_grid_device; DESIGN.md §3, "Coupling x halo grid"), on the
+        current stream and without a synchronisation: the arguments of event_rows for the same chunk and the factors
+        the two scans hand out for it -- weights (K_g, n_nodes) and back_factor (K_g, n_events), event_reweight(
+        return_weights=True)'s "weights" and "back", and ratio (K_h, n_events), event_halo_scan(return_ratio=True)'s
+        "ratio" -- with what they were made for: g (the K_g couplings), models (the K_h halo models) and base (the
+        raytracer.Halo of the run). At cell (kg, kh) the power of a final row is the coupling scan's at g[kg] times
+        ratio[kh] of its event, in the run's own flux bins. Returns a dict of device tensors, float64, CELL-MINOR as
+        the kernel adds to them (C = K_g K_h, cell = kg K_h + kh last): flux (2 nbins, C), totals (3, C: Σ power of
+        axions and of photons, misplaced records -- _lib.GRID_TOTALS), with replicates=R flux_rep (R, 2 nbins, C),
+        totals_rep (R, 2, C) and groups (R, 3, event_replicates'), with errors moment_totals (8, C,
+        _lib.MOMENT_TOTALS per cell), and g, models, base, R, n_events. trees.grid_raw brings them to the host with
+        (K_g, K_h) leading. grid: such a dict of an earlier chunk, ACCUMULATED into and returned. cyclotron_rerun:
+        event_rows' "cyclotron_rerun" of this chunk, so exp(-τ) is in the powers."""
+        from .trees import halo_scan_models
+        g = self._couplings(g)
+        models = halo_scan_models(base, models)
+        R = None if replicates is None else self._replicates_groups(replicates)
+        Kg, Kh, nbins = len(g), len(models), int(nbins)
+        n, nn = sample["erg"].numel(), int(forward["n_nodes"])
+        for name, t, shape in (("weights", weights, (Kg, nn)), ("back_factor", back_factor, (Kg, n)), ("ratio", ratio, (Kh, n))):
+            if (not torch.is_tensor(t) or t.dtype != F64 or tuple(t.shape) != shape or
+                    (t.numel() > 0 and not t.is_contiguous())):
+                raise ValueError(f"event_grid: {name} must be a contiguous float64 tensor of shape {shape}")
+        key = self._halo_key(base)
+        if grid is None:
+            grid = self._zero_grid(g, models, key, R, nbins, errors)
+        if (grid["g"] != g or grid["models"] != models or grid["base"] != key or grid["R"] != R or
+                tuple(grid["flux"].shape) != (2 * nbins, Kg * Kh) or errors != ("moment_totals" in grid)):
+            raise ValueError("event_grid: `grid` was made for other couplings, models, groups or tables")
+        ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
+        go = _lib.EventGridOut(Kg, Kh, nbins, R or 0, _p(weights), _p(back_factor), _p(ratio), _p(grid["flux"]),
+                               _p(grid["totals"]), _p(grid.get("flux_rep")), _p(grid.get("totals_rep")),
+                               _p(grid.get("groups")), _p(grid.get("moment_totals")))
+        check(self.lib.art_event_grid_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]), C.byref(go),
+                                             _stream()))
+        grid["n_events"] += n
+        return grid
+
     def _cyclotron_rerun(self, sample, forward, nn, n):
         """The final photon segments of a forward forest, packed (art_event_gather_photons_device) and run
         again with the cyclotron observation: slot per node, the batch size m, its tau and end states."""
@@ -551,7 +614,8 @@ class Engine:
 
     def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
                    max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
-                   cyclotron=False, rows=True, halo=None, errors=False, couplings=None, halos=None, replicates=None) -> dict:
+                   cyclotron=False, rows=True, halo=None, errors=False, couplings=None, halos=None, replicates=None,
+                   grid=False) -> dict:
         """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
         n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
         event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
@@ -611,6 +675,18 @@ class Engine:
         error. It needs neither rows nor errors=True. Replicate tables of more than Engine.REPLICATES_MAX_BYTES (1 GiB)
         per set of tables are a ValueError before any work is done. None (the default): exactly the keys below.
 
+        grid (needs couplings=, halos= and halo=; DESIGN.md §3, "Coupling x halo grid"): the two scans are each made at
+        the other's base value; with grid=True the run's flux and totals are also formed at every (coupling, halo
+        model) cell (event_grid per chunk, from the factors the two scans hand out: nothing is integrated or grown
+        again), and the result gets "grid", trees.grid_result's dict of host arrays: g (K_g), models (K_h), base, flux
+        (K_g, K_h, 2, nbins) and sum_weight_sln_prob (K_g, K_h, 2), both divided by f_inx, misplaced, raw; with errors
+        sum_weight_sln_prob_sigma (K_g, K_h, 2) and n_eff (K_g, K_h); with replicates "replicates", the per-group
+        tables from which trees.limit_band reads the limit on g under every halo model, the band between the models
+        and their errors. There is no sky map in the grid. Its tables -- (1 + R) copies under replicates=R plus the
+        moment totals -- may take at most Engine.REPLICATES_MAX_BYTES: beyond that, or without one of the three
+        keywords, a ValueError before any work is done. A misplaced record is an ArtError. False (the default):
+        exactly the keys below.
+
         Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
         or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
         f_inx, sum_weight_sln_prob, n_rows, n_photon_rows, and the raw, undivided parts for a caller that
@@ -619,6 +695,8 @@ class Engine:
         tensor `rows` is a divided copy of)."""
         from dataclasses import replace
         from .trees import AXION, PHOTON, halo_scan_models, sky_map_edges
+        if grid and (couplings is None or halos is None or halo is None):  # (before any work is done)
+            raise ValueError("grid: the coupling x halo grid needs couplings=, halos= and halo= (the base)")
         if replicates is not None:
             replicates = Engine._replicates_groups(replicates)  # (before any work is done)
         if halos is not None:
@@ -633,6 +711,8 @@ class Engine:
             raise ValueError("run_events: chunk must be >= 1")
         ncols = 29 if saveMode > 0 else 13
         _, shape, sky_kw = self._sky_spec(sky_map)
+        if grid:  # (before any work is done)
+            self._grid_fit(len(couplings), len(halos), replicates, int(nbins), errors)
         if replicates is not None:  # (before any work is done)
             for what, K in (("the run", 1), ("the coupling scan", couplings and len(couplings)),
                             ("the halo scan", halos and len(halos))):
@@ -646,8 +726,9 @@ class Engine:
         flux = torch.zeros(2 * int(nbins), dtype=F64, device=self.device)
         totals = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
         parts = []
-        moments = scan = hscan = rep = crep = hrep = None
+        moments = scan = hscan = rep = crep = hrep = cells = None
         want = replicates is not None
+        factors = want or bool(grid)  # the scans hand out their factors
         for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
             c = min(chunk, int(event_offset) + n_events - lo)
             s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r, halo=halo)
@@ -664,21 +745,29 @@ class Engine:
             if couplings is not None:
                 scan = self.event_reweight(s, w5, back, fwd, couplings, mc_nodes=MC_nodes, event_offset=lo, nbins=nbins,
                                            sky=sky_map, errors=errors, cyclotron_rerun=r["cyclotron_rerun"], scan=scan,
-                                           **({"return_weights": True} if want else {}))
+                                           **({"return_weights": True} if factors else {}))
             if halos is not None:
                 hscan = self.event_halo_scan(s, w5, back, fwd, halo, halos, event_offset=lo, nbins=nbins, sky=sky_map,
                                              errors=errors, cyclotron_rerun=r["cyclotron_rerun"], scan=hscan,
-                                             **({"return_ratio": True} if want else {}))
+                                             **({"return_ratio": True} if factors else {}))
+            if grid:
+                cells = self.event_grid(s, w5, back, fwd, weights=scan["weights"], back_factor=scan["back"],
+                                        ratio=hscan["ratio"], g=couplings, models=halos, base=halo, event_offset=lo,
+                                        nbins=nbins, replicates=replicates, errors=errors,
+                                        cyclotron_rerun=r["cyclotron_rerun"], grid=cells)
             if want:
                 kw = dict(event_offset=lo, nbins=nbins, sky=sky_map, cyclotron_rerun=r["cyclotron_rerun"])
                 rep = self.event_replicates(s, w5, back, fwd, replicates, rep=rep, **kw)
                 if couplings is not None:
                     crep = self.event_replicates(s, w5, back, fwd, replicates, rep=crep, kind="coupling",
-                                                 node_factor=scan.pop("weights"), event_factor=scan.pop("back"), **kw)
-                    del scan["back_prob"]
+                                                 node_factor=scan["weights"], event_factor=scan["back"], **kw)
                 if halos is not None:
                     hrep = self.event_replicates(s, w5, back, fwd, replicates, rep=hrep, kind="halo",
-                                                 event_factor=hscan.pop("ratio"), **kw)
+                                                 event_factor=hscan["ratio"], **kw)
+            if factors:  # (this chunk's factors are not part of the scans' tables)
+                for d, keys in ((scan, ("weights", "back", "back_prob")), (hscan, ("ratio",))):
+                    for k in keys if d is not None else ():
+                        d.pop(k, None)
             if rows:
                 parts.append(r["rows"] if len(r["rows"]) * 2 >= fwd["n_nodes"] else r["rows"].clone())
         tot = totals.cpu().numpy()
@@ -741,6 +830,13 @@ class Engine:
                 if out["replicates"]["misplaced"] != 0:
                     raise _lib.ArtError(f"run_events: {out['replicates']['misplaced']} node records lie in the range of "
                                         "another tree")
+        if grid:
+            from .trees import grid_raw, grid_result
+            if cells is None:  # (no events)
+                cells = self._zero_grid(couplings, halos, self._halo_key(halo), replicates, int(nbins), errors)
+            res["grid"] = grid_result(grid_raw(cells), f_inx)
+            if res["grid"]["misplaced"] != 0:
+                raise _lib.ArtError(f"run_events: {res['grid']['misplaced']} node records lie in the range of another tree")
         return res
 
     # ---- pointwise physics (parity tests)

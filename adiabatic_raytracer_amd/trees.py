@@ -198,7 +198,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
                      sky_map=None, device_trees=False, device_events=False, halo=None, errors=False,
-                     couplings=None, halos=None, replicates=None):
+                     couplings=None, halos=None, replicates=None, grid=False):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -283,7 +283,18 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     jackknife(run_info["replicates"], fn) gives the value and error of any function of the flux, the sky map and the
     totals. The host paths take the tables from the rows (rows_replicates with the sampler's attempts); device_events
     takes them from art_event_replicates_device, and there the scans' dicts get "replicates" too. With the default
-    None every row, file, run_info key and the reduced vector are unchanged."""
+    None every row, file, run_info key and the reduced vector are unchanged.
+
+    grid (beyond the reference; device_events only, ValueError on the other two paths; needs couplings=, halos= and
+    halo=; DESIGN.md §3, "Coupling x halo grid"): the run's first-moment tables at every (coupling, halo model) cell
+    (Engine.run_events(grid=True)), with the per-group tables under replicates= and the moment totals under errors=.
+    run_info["grid"] is grid_result's dict from the tables summed over the ranks, the last part of the vector of the
+    same all-reduce; limit_band(run_info["grid"], power) reads the limit on g per halo model off it. With the default
+    False every row, file, run_info key and the reduced vector are unchanged."""
+    if grid and not device_events:
+        raise ValueError("grid: the coupling x halo grid is formed from forests held in HBM and needs device_events=True")
+    if grid and (couplings is None or halos is None or halo is None):
+        raise ValueError("grid: the coupling x halo grid needs couplings=, halos= and halo= (the base)")
     if replicates is not None and not _lib.REPLICATES_MIN_GROUPS <= int(replicates) <= _lib.REPLICATES_MAX_GROUPS:
         raise ValueError(f"replicates: {_lib.REPLICATES_MIN_GROUPS} to {_lib.REPLICATES_MAX_GROUPS} groups, not {replicates!r}")
     if couplings is not None and not device_events:
@@ -301,7 +312,8 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                                         prob_cutoff=prob_cutoff, saveMode=saveMode, dir_tag=dir_tag, file_tag=file_tag,
                                         backtrace_cap=backtrace_cap, rank=rank, world=world, nbins=nbins, run_info=run_info,
                                         cyclotron=cyclotron, sky_map=sky_map, halo=halo, errors=errors,
-                                        couplings=couplings, halos=halos, replicates=replicates)
+                                        couplings=couplings, halos=halos, replicates=replicates,
+                                        **({"grid": True} if grid else {}))
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -396,7 +408,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
 
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
                              saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map,
-                             halo=None, errors=False, couplings=None, halos=None, replicates=None):
+                             halo=None, errors=False, couplings=None, halos=None, replicates=None, grid=False):
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
@@ -412,7 +424,8 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                                   sky_map=sky_kw, cyclotron=cyclotron, rows=True, halo=halo, errors=errors,
                                   **({} if couplings is None else {"couplings": couplings}),
                                   **({} if halos is None else {"halos": halos}),
-                                  **({} if replicates is None else {"replicates": replicates}))
+                                  **({} if replicates is None else {"replicates": replicates}),
+                                  **({"grid": True} if grid else {}))
     rep = None
     if replicates is not None:
         rep = {"run": r["replicates"]["raw"]}
@@ -427,7 +440,7 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
     return _finish_run(rows, tot, None if couplings is None else r["coupling_scan"]["raw"],
                        None if halos is None else r["halo_scan"]["raw"], nbins=nbins, sky_kw=sky_kw, errors=errors,
                        world=world, run_info=run_info, events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path,
-                       **({} if rep is None else {"replicates": rep}))
+                       **({} if rep is None else {"replicates": rep}), **({"grid": r["grid"]["raw"]} if grid else {}))
 
 
 def cyclotron_optical_depth(params: Params, fin, erg) -> np.ndarray:
@@ -1152,6 +1165,213 @@ def coupling_crossing(scan, power, species=PHOTON) -> dict:
     return jackknife(scan["replicates"], lambda t: _loglog_crossing(g, t["sum_weight_sln_prob"][:, sp], power))
 
 
+GRID_KEYS = ("flux", "totals", "flux_rep", "totals_rep", "groups", "moment_totals")
+
+
+def grid_tables(rows_raw, weights, back, ratio, final_index, nbins, R=None, attempts=None, event_lo=0) -> dict:
+    """art_event_grid_device's tables in numpy, the statement of its definition ("Coupling x halo grid"):
+    rows_raw, the run's own rows of one chunk (column 7 raw; column 14, τ, is read when there are 29 columns), weights
+    (K_g, n_nodes) and back (K_g, n_events), the coupling scan's W and B of the chunk, ratio (K_h, n_events), the halo
+    scan's R, and final_index, per row the index of its node record. The power of row r of event e at cell (kg, kh)
+    is ((W[kg, final_index[r]] B[kg, e]) [exp(-τ)] sln_prob) * R[kh, e], each product rounded on its own, in the
+    rows' own flux bins (hist_bins of column 3). Returns the tables as grid_raw lays them out: flux (K_g, K_h, 2 nbins),
+    totals (K_g, K_h, 3: Σ power of the axion and of the photon rows, 0 misplaced records), with R groups
+    (g = global event id mod R) flux_rep (K_g, K_h, R, 2 nbins), totals_rep (K_g, K_h, R, 2) and groups (R, 3: n_g,
+    a_g, 0), and with attempts (the sampler's, of the events event_lo .. event_lo + n_events) moment_totals
+    (K_g, K_h, 8): n, A1, A2, Q and C of the two species from X_{e,s} = Σ power of e's rows of species s in row
+    order, 0. attempts=None: a_e counts the photon rows only, as the device does with a NULL attempts, and there is
+    no moment_totals."""
+    rows = np.asarray(rows_raw, np.float64)
+    W, B, Rt = (np.atleast_2d(np.asarray(v, np.float64)) for v in (weights, back, ratio))
+    Kg, Kh, n, nbins, lo = W.shape[0], Rt.shape[0], B.shape[1], int(nbins), int(event_lo)
+    if B.shape[0] != Kg or Rt.shape[1] != n:
+        raise ValueError("grid_tables: weights and back share the couplings, back and ratio the events")
+    fi = np.asarray(final_index, np.int64).reshape(-1)
+    ev = np.rint(rows[:, 0]).astype(np.int64) - 1 - lo
+    sp = (rows[:, 1] != 0).astype(np.int64)
+    sln = rows[:, 7]
+    absorb = np.exp(-rows[:, 14]) if rows.shape[1] > 14 and rows[:, 14].any() else None
+    fb = hist_bins(rows[:, 3], nbins) if nbins > 0 else np.full(len(rows), -1)
+    lab = np.where(fb >= 0, sp * nbins + fb, -1)
+    keep = lab >= 0
+    photons = np.bincount(ev[sp == 1], minlength=n)
+    a = photons if attempts is None else np.asarray(attempts, np.int64) - 1 + photons
+    out = {"flux": np.zeros((Kg, Kh, 2 * nbins)), "totals": np.zeros((Kg, Kh, len(_lib.GRID_TOTALS)))}
+    if R is not None:
+        R = int(R)
+        g_ev = (lo + np.arange(n, dtype=np.int64)) % R
+        g = g_ev[ev]
+        out.update(flux_rep=np.zeros((Kg, Kh, R, 2 * nbins)), totals_rep=np.zeros((Kg, Kh, R, 2)),
+                   groups=np.stack([np.bincount(g_ev, minlength=R), np.bincount(g_ev, weights=a, minlength=R), np.zeros(R)],
+                                   axis=1).astype(np.float64))
+    if attempts is not None:
+        out["moment_totals"] = np.zeros((Kg, Kh, len(_lib.MOMENT_TOTALS)))
+    for kg in range(Kg):
+        w = W[kg, fi] * B[kg, ev]
+        pg = (w if absorb is None else w * absorb) * sln
+        for kh in range(Kh):
+            pw = pg * Rt[kh, ev]
+            out["flux"][kg, kh] = np.bincount(lab[keep], weights=pw[keep], minlength=2 * nbins)
+            out["totals"][kg, kh, :2] = np.bincount(sp, weights=pw, minlength=2)
+            if R is not None:
+                out["flux_rep"][kg, kh] = np.bincount(g[keep] * 2 * nbins + lab[keep], weights=pw[keep],
+                                                      minlength=R * 2 * nbins).reshape(R, 2 * nbins)
+                out["totals_rep"][kg, kh] = np.bincount(g * 2 + sp, weights=pw, minlength=2 * R).reshape(R, 2)
+            if attempts is not None:
+                X = np.bincount(ev * 2 + sp, weights=pw, minlength=2 * n).reshape(n, 2)  # (adds in row order)
+                out["moment_totals"][kg, kh] = np.r_[float(n), a.sum(), (a * a).sum(), (X * X).sum(axis=0),
+                                                     (X * a[:, None]).sum(axis=0), 0.0]
+    return out
+
+
+def grid_raw(grid) -> dict:
+    """Engine.event_grid's dict with its tables on the host (numpy) and the cell axis, which the device keeps last
+    (art_event_grid_out's tables are cell-minor), turned into two leading axes: flux (K_g, K_h, 2 nbins), totals
+    (K_g, K_h, 3), flux_rep (K_g, K_h, R, 2 nbins), totals_rep (K_g, K_h, R, 2), groups (R, 3), moment_totals
+    (K_g, K_h, 8) -- those there are; what adds over chunks and ranks -- then g, models, base, R and n_events."""
+    Kg, Kh = len(grid["g"]), len(grid["models"])
+    out = {}
+    for k in GRID_KEYS:
+        v = grid.get(k)
+        if v is None:
+            continue
+        v = v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v, np.float64)
+        out[k] = v.copy() if k == "groups" else np.ascontiguousarray(np.moveaxis(v.reshape(*v.shape[:-1], Kg, Kh), (-2, -1), (0, 1)))
+    out.update(g=[float(v) for v in grid["g"]], models=[_halo_of(h) for h in grid["models"]], base=grid["base"],
+               R=None if grid.get("R") is None else int(grid["R"]), n_events=int(grid["n_events"]))
+    return out
+
+
+def grid_pack(raw) -> np.ndarray:
+    """A rank's grid tables (grid_raw) as one vector for the run's all-reduce: the tables there are, in GRID_KEYS'
+    order, then the number of events"""
+    parts = [np.asarray(raw[k], np.float64).reshape(-1) for k in GRID_KEYS if raw.get(k) is not None]
+    return np.concatenate(parts + [np.array([float(raw["n_events"])])])
+
+
+def grid_unpack(vec, like) -> dict:
+    """grid_pack's vector back into a dict shaped like `like` (the rank's own grid_raw)"""
+    out, at = {k: like[k] for k in ("g", "models", "base", "R")}, 0
+    for k in GRID_KEYS:
+        if like.get(k) is None:
+            continue
+        out[k] = np.asarray(vec[at:at + like[k].size], np.float64).reshape(like[k].shape)
+        at += like[k].size
+    out["n_events"] = int(round(vec[at]))
+    return out
+
+
+def grid_result(raw, f_inx) -> dict:
+    """The coupling x halo grid of a run from its raw tables (grid_raw, summed over the ranks) and the run's f_inx: g
+    (K_g), models (K_h), base, flux (K_g, K_h, 2, nbins) and sum_weight_sln_prob (K_g, K_h, 2), both divided by f_inx,
+    misplaced (records outside their tree's range, which must be 0), f_inx, raw; with moment totals
+    sum_weight_sln_prob_sigma (K_g, K_h, 2; moments_sigma: a_e and f_inx are the run's own in every cell) and n_eff
+    (K_g, K_h) = S_photon² / Q_photon, the Kish effective number of events behind a cell's photon total; with
+    replicate tables "replicates": the raw group tables flux (K_g, K_h, R, 2 nbins) and totals (K_g, K_h, R, 2), n_g
+    and a_g (R), R and f_inx, which grid_jackknife and limit_band read."""
+    f = float(f_inx) if f_inx > 0 else 1.0
+    tot = np.asarray(raw["totals"], np.float64)
+    Kg, Kh = tot.shape[:2]
+    nbins = raw["flux"].shape[-1] // 2
+    res = {"g": np.array(raw["g"], np.float64), "models": list(raw["models"]), "base": raw["base"],
+           "flux": (raw["flux"] / f).reshape(Kg, Kh, 2, nbins), "sum_weight_sln_prob": tot[:, :, 0:2] / f,
+           "misplaced": int(round(tot[0, 0, 2])), "f_inx": int(f_inx), "raw": raw}
+    mt = raw.get("moment_totals")
+    if mt is not None:
+        res["sum_weight_sln_prob_sigma"] = np.stack([np.stack([
+            moments_sigma(tot[i, j, 0:2], mt[i, j, 3:5], mt[i, j, 5:7], f_inx, mt[i, j, 2], mt[i, j, 0])
+            for j in range(Kh)]) for i in range(Kg)])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res["n_eff"] = tot[:, :, 1] * tot[:, :, 1] / mt[:, :, 4]
+    if raw.get("groups") is not None:
+        groups = np.asarray(raw["groups"], np.float64)
+        res["replicates"] = {"R": int(raw["R"]), "flux": raw["flux_rep"], "totals": raw["totals_rep"],
+                             "n_g": groups[:, 0].copy(), "a_g": groups[:, 1].copy(), "f_inx": int(f_inx)}
+        res["misplaced"] = max(res["misplaced"], int(round(groups[:, 2].sum())))
+    return res
+
+
+def grid_jackknife(grid, fn, cov=False) -> dict:
+    """trees.jackknife for the coupling x halo grid (grid_result's dict, made with replicates): fn gets a dict of the
+    normalised tables flux (K_g, K_h, 2, nbins) and sum_weight_sln_prob (K_g, K_h, 2) and returns a number or an
+    array. The same leave-one-group-out formula, the same NaN rules and the same groups_used as jackknife: value,
+    sigma, groups_used and with cov the covariance of the flattened result."""
+    rep = grid.get("replicates")
+    if rep is None:
+        raise ValueError("grid_jackknife: the grid has no replicates (run_events(grid=True, replicates=R))")
+    flux, totals = np.asarray(rep["flux"], np.float64), np.asarray(rep["totals"], np.float64)
+    Kg, Kh, R = totals.shape[:3]
+    groups = np.stack([rep["n_g"], rep["a_g"], np.zeros(R)], axis=1)
+    raw = {"kind": "grid", "R": R, "groups": groups, "sky": None, "flux": flux.reshape(Kg * Kh, R, -1),
+           "totals": totals.reshape(Kg * Kh, R, 2)}
+    cells = lambda t: {k: v.reshape(Kg, Kh, *v.shape[1:]) for k, v in t.items()}  # noqa: E731
+    return jackknife({"raw": raw, "f_inx": rep["f_inx"]}, lambda t: fn(cells(t)), cov=cov)
+
+
+def limit_band(grid, power, species=PHOTON, average=None) -> dict:
+    """The limit on g under every halo model of a coupling x halo grid (run_events' or run_info's "grid", made with
+    replicates), and the band between the models: per model kh the coupling at which column kh of the grid, the
+    radiated power of `species` against g, reaches `power` (> 0), by the log-log interpolation of coupling_crossing,
+    with its jackknife error. The models reweight the same events, so their limits are strongly correlated and the
+    width of the band has a far smaller error than the quadrature sum of the limits' -- which is what cov is for.
+    Returns g and sigma (K_h), cov (K_h, K_h; its diagonal is sigma²), lo, hi (the smallest and the largest limit
+    over the models that reach `power`), lo_model, hi_model (their indices, -1 for none), lo_sigma, hi_sigma, ratio =
+    hi / lo and ratio_sigma (each leave-one-out estimate takes its own smallest and largest), and groups_used.
+    average (a list of model indices, or a vector of K_h weights, normalised to sum 1): also g_avg and sigma_avg, the
+    crossing of the correspondingly averaged column. The tables are linear in the halo's velocity distribution, so
+    an average over models is the table of the averaged distribution: the way to treat an unknown direction of v_ns.
+    NaN where a column does not reach `power`."""
+    if not (power > 0.0 and math.isfinite(power)):
+        raise ValueError("limit_band: power must be finite and > 0")
+    if "replicates" not in grid:
+        raise ValueError("limit_band: the grid has no replicates (run_events(grid=True, replicates=R))")
+    sp = 0 if species == AXION else 1
+    g = np.asarray(grid["g"], np.float64)
+    Kh = len(grid["models"])
+    w = None
+    if average is not None:
+        av = np.asarray(average)
+        if av.size == 0:
+            raise ValueError("limit_band: average is empty")
+        if np.issubdtype(av.dtype, np.integer):
+            if av.min() < 0 or av.max() >= Kh:
+                raise ValueError("limit_band: average names a model outside the grid")
+            w = np.bincount(av.reshape(-1), minlength=Kh).astype(np.float64)
+        else:
+            w = np.asarray(av, np.float64).reshape(-1)
+            if w.size != Kh or not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError("limit_band: a weight vector has one finite weight >= 0 per model")
+        if not w.sum() > 0:
+            raise ValueError("limit_band: the weights sum to 0")
+        w = w / w.sum()
+
+    def ends(gh):
+        ok = np.isfinite(gh)
+        return (float(gh[ok].min()), float(gh[ok].max())) if ok.any() else (float("nan"), float("nan"))
+
+    def fn(t):
+        P = t["sum_weight_sln_prob"][:, :, sp]
+        gh = np.array([_loglog_crossing(g, P[:, h], power) for h in range(Kh)])
+        lo, hi = ends(gh)
+        tail = [lo, hi, hi / lo if lo > 0 else float("nan")]
+        if w is not None:
+            tail.append(_loglog_crossing(g, P @ w, power))
+        return np.r_[gh, tail]
+
+    jk = grid_jackknife(grid, fn, cov=True)
+    v, s = jk["value"], jk["sigma"]
+    gh = v[:Kh]
+    ok = np.isfinite(gh)
+    out = {"g": gh, "sigma": s[:Kh], "cov": jk["cov"][:Kh, :Kh], "lo": float(v[Kh]), "hi": float(v[Kh + 1]),
+           "lo_model": int(np.flatnonzero(ok)[np.argmin(gh[ok])]) if ok.any() else -1,
+           "hi_model": int(np.flatnonzero(ok)[np.argmax(gh[ok])]) if ok.any() else -1,
+           "lo_sigma": float(s[Kh]), "hi_sigma": float(s[Kh + 1]), "ratio": float(v[Kh + 2]),
+           "ratio_sigma": float(s[Kh + 2]), "groups_used": jk["groups_used"]}
+    if w is not None:
+        out.update(g_avg=float(v[Kh + 3]), sigma_avg=float(s[Kh + 3]), weights=w)
+    return out
+
+
 def pack_totals(flux, f_inx, sum_axion, sum_photon, n_rows, sky=None, moments=None) -> np.ndarray:
     """A rank's part of main_runner_tree's single all-reduce: [flux (2 nbins) | f_inx | Σ weight *
     sln_prob (axions, photons) | rows], then the sky map's table when there is one, then with moments
@@ -1203,27 +1423,31 @@ def _sigma_info(tt, nbins) -> dict:
 REPLICATE_PARTS = ("run", "coupling", "halo")  # the order of the replicate parts of a rank's vector
 
 
-def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None):
+def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None, grid=None):
     """A rank's vector for main_runner_tree's single all-reduce, [pack_totals | coupling scan | halo scan |
-    replicates...]: the rank's pack_totals vector, then scan_pack of its coupling scan's raw tables and halo_scan_pack
-    of its halo scan's, each only when there is one, then replicates_pack of each raw dict of `replicates` (a dict
-    with the keys "run", "coupling", "halo" there are, in that order; None: none), so every earlier part keeps its
-    place. Returns (the vector, where each of its parts ends)."""
+    replicates... | grid]: the rank's pack_totals vector, then scan_pack of its coupling scan's raw tables and
+    halo_scan_pack of its halo scan's, each only when there is one, then replicates_pack of each raw dict of
+    `replicates` (a dict with the keys "run", "coupling", "halo" there are, in that order; None: none), then grid_pack
+    of `grid` (the rank's grid_raw; None: none) LAST, so every earlier part keeps its place and its end. Returns (the
+    vector, where each of its parts ends)."""
     parts = [totals] + [pack(raw) for pack, raw in ((scan_pack, coupling_raw), (halo_scan_pack, halo_raw)) if raw is not None]
     parts += [replicates_pack(replicates[k]) for k in REPLICATE_PARTS if replicates and replicates.get(k) is not None]
+    if grid is not None:
+        parts.append(grid_pack(grid))
     return (np.concatenate(parts) if len(parts) > 1 else totals), np.cumsum([len(v) for v in parts])
 
 
 def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw, errors, world, run_info, events, n_events,
-                g0, path, replicates=None):
+                g0, path, replicates=None, grid=None):
     """The end of main_runner_tree on every path: the rank's vector (rank_vector of its pack_totals vector and its
     scans' raw tables) summed over the ranks in ONE all-reduce, σ from the reduced tables, column 8 of the rank's
     rows divided by the global f_inx, run_info (a dict or None; events: the rank's (lo, hi), n_events: the run's),
     and with `path` the npy file and, with a sky map, skymap_<its stem>.npz beside it. g0: the run's coupling, the
     coupling scan's base. replicates: the rank's raw replicate tables (rank_vector's keyword), which end the vector
-    and come back as run_info["replicates"] and as "replicates" in the scans' dicts. Returns the rows."""
+    and come back as run_info["replicates"] and as "replicates" in the scans' dicts. grid: the rank's grid_raw, the
+    vector's last part, which comes back as run_info["grid"] (grid_result). Returns the rows."""
     from .shard import allreduce_sum
-    tot, ends = rank_vector(totals, coupling_raw, halo_raw, replicates=replicates)
+    tot, ends = rank_vector(totals, coupling_raw, halo_raw, replicates=replicates, **({} if grid is None else {"grid": grid}))
     n_scans = (coupling_raw is not None) + (halo_raw is not None)
     if world > 1:
         tot = allreduce_sum(tot)
@@ -1251,6 +1475,8 @@ def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw
             raw = replicates_unpack(tot[ends[n_scans + j]:ends[n_scans + j + 1]], replicates[k])
             where = run_info if k == "run" else run_info[k + "_scan"]
             where["replicates"] = replicates_result(raw, int(round(f_glob)))
+        if grid is not None:
+            run_info["grid"] = grid_result(grid_unpack(tot[ends[-2]:ends[-1]], grid), int(round(f_glob)))
     if path is not None:
         os.makedirs(os.path.dirname(path), exist_ok=True)
         np.save(path, rows)

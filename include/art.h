@@ -783,6 +783,52 @@ typedef struct art_event_replicates_out {
 int art_event_replicates_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
                                 const art_event_replicates_out* out, void* stream);
 
+/* ---- coupling x halo grid: the first-moment tables at every (coupling, halo model) cell, from the two scans' factors ----
+ * The halo ratio is one scalar per event and does not depend on g, so at cell (kg, kh) the power of final row i of
+ * event e is  pw = (W_kg[i] B_kg[e] [exp(-τ)] sln_prob) * R_kh[e]:  the coupling scan's power at g_kg, then ONE
+ * multiplication by the halo scan's ratio, rounded on its own. node_factor = art_event_reweight_out::weights,
+ * back = art_event_reweight_out::back and ratio = art_event_halo_scan_out::ratio, all three of the same chunk. The
+ * rows counted and their bins are art_event_replicates_device's: a final record inside its own tree's range, in
+ * art_event_rows_device's flux bins; a record in the range of a tree other than its own is skipped and counted.
+ * With C = n_couplings n_models cells, cell = kg n_models + kh, every table is CELL-MINOR (the cell is the fastest
+ * index: the kernel's lanes cover consecutive cells, so one instruction adds to 512 contiguous bytes) and
+ * ACCUMULATED into (zero it first); ordinary device memory. The call ADDS
+ *   flux[(sp nbins + fb) C + cell] += pw      for a row of species sp (0 axion, 1 photon) in flux bin fb,
+ *   totals[sp C + cell]            += pw      for every final row, binned or not; totals[2 C + 0] += the misplaced
+ *                                             records (the first cell's only; must stay 0),
+ * with n_groups = R, g = (event_offset + tree) mod R:
+ *   flux_rep[((g 2 + sp) nbins + fb) C + cell] += pw,   totals_rep[(g 2 + sp) C + cell] += pw,
+ *   groups[g 3 + q]: art_event_replicates_device's n_g, a_g and misplaced records,
+ * and with moment_totals non-NULL, per cell art_event_moments_device's 8 totals,
+ *   moment_totals[q C + cell]: [0] the events n, [1] A1, [2] A2, [3], [4] Q of axions and photons, [5], [6] C of
+ *   axions and photons, [7] the misplaced records (the first cell's only),
+ * with X_{e,s}(kg, kh) = Σ pw over e's final rows of species s, summed in node order, and a_e the moments' a_e; so
+ * the delta-method σ of a cell's totals follows as for art_event_moments_device, and n_eff = S_photon² / Q_photon.
+ * There is NO sky map in the grid: 64 x 128 x 16 bins per cell would be 2 GiB at 32 x 32 cells, and the line shape
+ * per model is already in the halo scan. Everything adds over chunks and ranks. */
+typedef struct art_event_grid_out {
+  int32_t n_couplings;         /* K_g, 1 .. 32                                                        */
+  int32_t n_models;            /* K_h, 1 .. 32                                                        */
+  int32_t nbins;               /* flux bins over [-π, π], 0 .. 4096 (0: no flux tables)              */
+  int32_t n_groups;            /* R: 0 (no replicate tables) or 2 .. 64                               */
+  const double* node_factor;   /* K_g * n_nodes  INPUT: W_kg of every record                          */
+  const double* back;          /* K_g * n_events INPUT: B_kg of every event                           */
+  const double* ratio;         /* K_h * n_events INPUT: R_kh of every event                           */
+  double* flux;                /* 2 nbins * C                                                         */
+  double* totals;              /* 3 * C: Σ power of the axion rows, of the photon rows, misplaced     */
+  double* flux_rep;            /* R * 2 nbins * C (n_groups > 0)                                      */
+  double* totals_rep;          /* R * 2 * C       (n_groups > 0)                                      */
+  double* groups;              /* R * 3           (n_groups > 0): n_g, a_g, misplaced records         */
+  double* moment_totals;       /* may be NULL: 8 * C                                                  */
+} art_event_grid_out;
+/* Asynchronous on `stream`, no host read, no scratch and no carried state. Every table is ordinary device memory and
+ * takes float64 hardware adds. ART_E_INVALID before any device is touched: a NULL p, in or out; n_couplings or
+ * n_models outside 1 .. 32; n_groups of 1, negative or above 64; art_event_moments_device's faults on nbins; a NULL
+ * back or ratio with events, a NULL node_factor or node_start with n_nodes > 0; a NULL table that the call needs.
+ * n_events == 0: ART_OK, nothing touched. */
+int art_event_grid_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                          const art_event_grid_out* out, void* stream);
+
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the
  * other ranks (a file, MPI, the launcher); every rank then calls art_comm_init on its device.

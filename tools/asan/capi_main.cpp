@@ -240,6 +240,52 @@ int main() {
     CHECK(art_event_replicates_device(&p, &ei, ns, &po, nullptr) == ART_E_INVALID);
     ei.n_events = ei.n_nodes = 0;
     CHECK(art_event_replicates_device(&p, &ei, nullptr, &po, nullptr) == ART_OK);
+    // the coupling x halo grid: the three counts, its factor arrays, then the moments call's checks on nbins and
+    // node_start and the tables it needs, all before the device
+    art_event_grid_out go{};
+    go.n_couplings = 3; go.n_models = 2; go.nbins = 50; go.n_groups = 8;
+    go.node_factor = go.back = go.ratio = d;
+    go.flux = go.totals = go.flux_rep = go.totals_rep = go.groups = d;
+    ei.n_events = ei.n_nodes = 4;
+    CHECK(art_event_grid_device(nullptr, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    CHECK(art_event_grid_device(&p, nullptr, ns, &go, nullptr) == ART_E_INVALID);
+    CHECK(art_event_grid_device(&p, &ei, ns, nullptr, nullptr) == ART_E_INVALID);
+    for (int bad_count : {-1, 0, 33}) {
+      go.n_couplings = bad_count;
+      CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+      go.n_couplings = 32; go.n_models = bad_count;
+      CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+      go.n_models = 32;
+    }
+    for (int bad_groups : {-1, 1, 65}) {
+      go.n_groups = bad_groups;
+      CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    }
+    go.n_groups = 64; go.nbins = 4097;
+    CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    go.nbins = 50; go.node_factor = nullptr;  // the coupling scan's weights
+    CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    go.node_factor = d; go.back = nullptr;  // its back factors
+    CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    go.back = d; go.ratio = nullptr;  // the halo scan's ratios
+    CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    go.ratio = d;
+    CHECK(art_event_grid_device(&p, &ei, nullptr, &go, nullptr) == ART_E_INVALID);  // node_start
+    go.totals = nullptr;
+    CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    go.totals = d; go.flux = nullptr;
+    CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    go.flux = d; go.flux_rep = nullptr;
+    CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    go.flux_rep = d; go.groups = nullptr;
+    CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID);
+    go.n_groups = 0;  // no replicate tables: theirs are not asked for, and the checks reach the chunk's own buffers
+    go.flux_rep = go.totals_rep = nullptr;
+    CHECK(art_event_grid_device(&p, &ei, ns, &go, nullptr) == ART_E_INVALID &&
+          std::strstr(art_last_error(), "NULL input buffer") != nullptr);
+    ei.n_events = ei.n_nodes = 0;
+    go.node_factor = go.back = go.ratio = nullptr; go.flux = go.totals = nullptr;
+    CHECK(art_event_grid_device(&p, &ei, nullptr, &go, nullptr) == ART_OK);
     // where the four event calls differ on purpose (art_post.cpp's front-end flags). A call that passes its
     // argument checks goes on to the device, which this container does not have.
     auto went_on = [](int r) { return r == ART_E_HIP || r == ART_E_NOMEM || r == ART_OK; };

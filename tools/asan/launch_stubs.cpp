@@ -87,6 +87,7 @@ hipError_t launch_event_halo_scan(const EventRowsArgs&, const EventHaloScanArgs&
 hipError_t launch_event_replicates(const EventRowsArgs&, const EventReplicatesArgs&, const SkyAxes&, int, hipStream_t) {
   return hipErrorNoDevice;
 }
+hipError_t launch_event_grid(const EventRowsArgs&, const EventGridArgs&, hipStream_t) { return hipErrorNoDevice; }
 MFn nl_eval_math(int) { return nullptr; }
 hipError_t launch_eval_math(int, int, int64_t, const double*, const double*, double*, double*, hipStream_t) {
   return hipErrorNoDevice;
