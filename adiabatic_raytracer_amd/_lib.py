@@ -98,6 +98,16 @@ class EventGridOut(C.Structure):  # include/art.h art_event_grid_out
 GRID_TOTALS = ("sum_axion", "sum_photon", "misplaced")
 GRID_MAX_COUPLINGS, GRID_MAX_MODELS = 32, 32
 
+class EventSpectrumOut(C.Structure):  # include/art.h art_event_spectrum_out
+    _fields_ = [("kind", C.c_int32), ("n_sets", C.c_int32), ("sub_bits", C.c_int32), ("top", C.c_int32),
+                ("node_factor", C.c_void_p), ("event_factor", C.c_void_p), ("count", C.c_void_p), ("sum", C.c_void_p),
+                ("sum_sq", C.c_void_p), ("totals", C.c_void_p), ("top_power", C.c_void_p), ("top_event", C.c_void_p)]
+
+
+# art_event_spectrum_out::totals, per set and species; the limits of its bin rule and its list
+SPECTRUM_TOTALS = ("events", "positive", "zeros", "bad", "sum", "sum_sq", "misplaced", "reserved")
+SPECTRUM_MAX_SUB_BITS, SPECTRUM_MAX_TOP = 4, 256
+
 EVENT_TOTALS = ("rows", "photon_rows", "sum_axion", "sum_photon", "attempts_minus_1", "cyclotron_mismatches")
 # art_event_moments_out::totals
 MOMENT_TOTALS = ("events", "A1", "A2", "Q_axion", "Q_photon", "C_axion", "C_photon", "bad_nodes")
@@ -185,6 +195,7 @@ SIGNATURES = {
     "art_event_halo_scan_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, _H, _i32, _H, C.POINTER(EventHaloScanOut), _v]),
     "art_event_replicates_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventReplicatesOut), _v]),
     "art_event_grid_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventGridOut), _v]),
+    "art_event_spectrum_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventSpectrumOut), _v]),
     "art_comm_unique_id": (C.c_int, [_v]),
     "art_comm_init": (C.c_int, [_i32, _i32, _v]),
     "art_flux_allreduce": (C.c_int, [_v, _i64, _v]),

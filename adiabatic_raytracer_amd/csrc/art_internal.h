@@ -413,4 +413,19 @@ struct EventGridArgs {
   double *flux, *totals, *flux_rep, *totals_rep, *groups, *mtotals;
 };
 hipError_t launch_event_grid(const EventRowsArgs& a, const EventGridArgs& r, hipStream_t s);
+// The event power spectrum (art_event_spectrum_device; the kernels of art_event_spectrum.h): the inputs are an
+// EventRowsArgs (its outputs unused) and the forest's node_start; kind, node_factor and event_factor as
+// EventReplicatesArgs'. count, sum and sum_sq hold (set k, species s) at (2 k + s) (2047 << sub_bits), totals at
+// (2 k + s) 8, the lists top_power and top_event (carried in and out) at (2 k + s) top. Scratch: entries, n_nodes
+// MomentEntry, and X, n_k 2 n_events doubles, X_{e,s} of set k at (2 k + s) n_events + e.
+struct EventSpectrumArgs {
+  const int64_t* node_start;
+  int32_t kind, n_k, sub_bits, top;
+  const double *node_factor, *event_factor;
+  double *count, *sum, *sum_sq, *totals, *top_power;
+  int64_t* top_event;
+  MomentEntry* entries;
+  double* X;
+};
+hipError_t launch_event_spectrum(const EventRowsArgs& a, const EventSpectrumArgs& r, hipStream_t s);
 }  // namespace art

@@ -1161,3 +1161,8 @@ hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_a
 // the two scans' factors
 #define ART_EVENT_GRID_KERNELS
 #include "art_event_grid.h"
+
+// The event power spectrum (art_event_spectrum_device): the header's kernels, which take the powers as the event
+// rows and the scans do and sum them per event as the event moments do
+#define ART_EVENT_SPECTRUM_KERNELS
+#include "art_event_spectrum.h"

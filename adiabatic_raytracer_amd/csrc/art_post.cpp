@@ -1,6 +1,6 @@
 // art_post.cpp -- the entry points around the propagate calls (declared in include/art.h): the
 // non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows, event moments, the coupling
-// scan, the halo scan, the jackknife replicates, the coupling x halo grid and the eval entry points the tests compare against the oracle. Each checks its arguments, then
+// scan, the halo scan, the jackknife replicates, the coupling x halo grid, the event power spectrum and the eval entry points the tests compare against the oracle. Each checks its arguments, then
 // launches on the caller's stream (or stages through the context's pool, the *_host ones).
 #include <algorithm>
 #include <cmath>
@@ -12,6 +12,7 @@
 #include "art_event_replicates.h"
 #include "art_event_reweight.h"
 #include "art_event_rows.h"
+#include "art_event_spectrum.h"
 #include "art_host.h"
 
 namespace art {
@@ -799,6 +800,55 @@ int art_event_grid_device(const art_params* p, const art_event_rows_in* in, cons
     r.flux_rep = out->flux_rep; r.totals_rep = out->totals_rep; r.groups = out->groups;
   }
   HIP_OK(art::launch_event_grid(a, r, (hipStream_t)stream));
+  return ART_OK;
+}
+
+// The event power spectrum of a chunk (include/art.h): one entry per node record and X per set, species and event in
+// scratch, then the tables and the top lists (art_event_spectrum.h), three kernels on `stream`.
+int art_event_spectrum_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                              const art_event_spectrum_out* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
+  if (out->kind < 0 || out->kind >= art::REP_KIND_COUNT)
+    return fail(ART_E_INVALID, "kind must be 0 (the run), 1 (a coupling scan) or 2 (a halo scan)");
+  if (out->n_sets < 1 || out->n_sets > art::SPECTRUM_MAX_SETS) return fail(ART_E_INVALID, "n_sets must be in [1, 32]");
+  if (out->kind == art::REP_KIND_RUN && out->n_sets != 1) return fail(ART_E_INVALID, "n_sets must be 1 with kind 0");
+  if (out->sub_bits < 0 || out->sub_bits > art::SPECTRUM_MAX_SUB_BITS) return fail(ART_E_INVALID, "sub_bits must be in [0, 4]");
+  if (out->top < 0 || out->top > art::SPECTRUM_MAX_TOP) return fail(ART_E_INVALID, "top must be in [0, 256]");
+  if ((rc = event_in_ranges(in))) return rc;
+  if (out->kind == art::REP_KIND_COUPLING && in->n_nodes > 0 && !out->node_factor)
+    return fail(ART_E_INVALID, "node_factor is NULL (kind 1: the coupling scan's weights)");
+  if (out->kind != art::REP_KIND_RUN && !out->event_factor)
+    return fail(ART_E_INVALID, "event_factor is NULL (kind 1: the coupling scan's back, kind 2: the halo scan's ratio)");
+  if ((rc = need_node_start(in, node_start))) return rc;
+  if (!out->count || !out->sum || !out->sum_sq || !out->totals) return fail(ART_E_INVALID, "count, sum, sum_sq or totals is NULL");
+  if (out->top > 0 && (!out->top_power || !out->top_event)) return fail(ART_E_INVALID, "top_power or top_event is NULL");
+  if (in->n_events == 0) return ART_OK;
+  // IN_CYC_END_STATES: the moments call's check, whose chunk and re-run this call is handed; the kernels read
+  // cyc_tau alone.
+  if ((rc = event_in_buffers(in, node_start, IN_CYC_END_STATES))) return rc;
+  if (out->kind == art::REP_KIND_COUPLING && !in->weight5) return fail(ART_E_INVALID, "NULL input buffer");
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const art::EventRowsArgs a = event_args(p, in, /*end_states=*/false);
+  art::EventSpectrumArgs r{};
+  r.node_start = node_start; r.kind = out->kind; r.n_k = out->n_sets; r.sub_bits = out->sub_bits; r.top = out->top;
+  r.node_factor = out->node_factor; r.event_factor = out->event_factor;
+  r.count = out->count; r.sum = out->sum; r.sum_sq = out->sum_sq; r.totals = out->totals;
+  r.top_power = out->top_power; r.top_event = out->top_event;
+  Carve cv;  // [X | entries]
+  const size_t o_x = cv.add((size_t)out->n_sets * 2 * (size_t)in->n_events * 8),
+               o_en = cv.add((size_t)in->n_nodes * sizeof(art::MomentEntry));
+  void* block = nullptr;
+  if ((rc = scratch_alloc(s, cv.bytes, &block))) return rc;
+  r.X = (double*)((char*)block + o_x);
+  r.entries = (art::MomentEntry*)((char*)block + o_en);
+  const hipError_t e = art::launch_event_spectrum(a, r, s);
+  (void)hipFreeAsync(block, s);
+  HIP_OK(e);
   return ART_OK;
 }
 

@@ -528,6 +528,72 @@ class Engine:
                                                    _stream()))
         return rep
 
+    # The most bytes the spectrum tables of one set of tables (the run's, a coupling scan's or a halo scan's) may take
+    SPECTRUM_MAX_BYTES = 64 << 20
+
+    @classmethod
+    def _spectrum_fit(cls, what, K, sub_bits):
+        """ValueError when the spectrum tables of K sets exceed SPECTRUM_MAX_BYTES"""
+        size = 8 * K * 2 * 3 * (2047 << sub_bits)
+        if size > cls.SPECTRUM_MAX_BYTES:
+            raise ValueError(f"spectrum: the tables of {what} ({K} sets, sub_bits {sub_bits}) would take {size} bytes, "
+                             f"more than {cls.SPECTRUM_MAX_BYTES}: lower sub_bits or the number of sets")
+
+    def _zero_spectrum(self, kind, K, sub_bits, top):
+        z = lambda *d: torch.zeros(*d, dtype=F64, device=self.device)  # noqa: E731
+        NB = 2047 << sub_bits
+        return {"kind": kind, "sub_bits": sub_bits, "top": top, "count": z(K, 2, NB), "sum": z(K, 2, NB), "sum_sq": z(K, 2, NB),
+                "totals": z(K, 2, len(_lib.SPECTRUM_TOTALS)), "top_power": z(K, 2, top),
+                "top_event": torch.full((K, 2, top), -1, dtype=torch.int64, device=self.device)}
+
+    def event_spectrum(self, sample, weight5, back, forward, *, sub_bits=3, top=64, kind="run", node_factor=None,
+                       event_factor=None, event_offset=0, cyclotron_rerun=None, spec=None) -> dict:
+        """The event power spectrum of one chunk (art_event_spectrum_device; DESIGN.md §3, "Event power spectrum"), on
+        the current stream and without a synchronisation: the arguments of event_rows for the same chunk, of whose
+        per-event power X_{e,s} (the moments' X: the powers of e's final rows of species s, summed in node order) it
+        keeps the distribution. The sets and their powers by kind are event_replicates': "run", one set; "coupling"
+        from node_factor = event_reweight(return_weights=True)'s "weights" and event_factor = its "back"; "halo" from
+        event_factor = event_halo_scan(return_ratio=True)'s "ratio". Returns a dict of device tensors: count, sum and
+        sum_sq (K, 2, 2047 << sub_bits: the events, Σ X and Σ X² per bin, bin = bits(X) >> (52 - sub_bits), float64),
+        totals (K, 2, 8: _lib.SPECTRUM_TOTALS), top_power (K, 2, top) and top_event (K, 2, top; int64, the global
+        ids event_offset + tree), the `top` events with the largest X by (X descending, id ascending), padded with
+        (0.0, -1), with kind, sub_bits and top. spec: such a dict of an earlier chunk, ACCUMULATED into -- its lists
+        are candidates of this call -- and returned. cyclotron_rerun: event_rows' "cyclotron_rerun" of this chunk, so
+        exp(-τ) is in the powers. trees.spectrum_result turns the tables into n_eff, shares and the tail index."""
+        from .trees import _spectrum_check
+        m, T = _spectrum_check(sub_bits, top)
+        if kind not in _lib.REPLICATE_KINDS:
+            raise ValueError(f"event_spectrum: kind must be one of {sorted(_lib.REPLICATE_KINDS)}, not {kind!r}")
+        if (kind == "coupling" and node_factor is None) or (kind != "run" and event_factor is None):
+            raise ValueError(f"event_spectrum: kind {kind!r} needs its factor arrays")
+        if kind != "run" and not (torch.is_tensor(event_factor) and event_factor.dim() == 2):
+            raise ValueError("event_spectrum: event_factor must be a contiguous float64 (K, n_events) tensor on the "
+                             "engine's device")
+        K = 1 if kind == "run" else int(event_factor.shape[0])
+        if spec is None:
+            spec = self._zero_spectrum(kind, K, m, T)
+        if (spec["kind"] != kind or spec["sub_bits"] != m or spec["top"] != T or
+                tuple(spec["count"].shape) != (K, 2, 2047 << m)):
+            raise ValueError("event_spectrum: `spec` was made for another kind, other bins, another list or other sets")
+        n, nn = sample["erg"].numel(), int(forward["n_nodes"])
+        here = lambda t: torch.is_tensor(t) and t.dtype == F64 and t.device == self.device  # noqa: E731
+        if kind != "run" and (not here(event_factor) or tuple(event_factor.shape) != (K, n) or
+                              not event_factor.is_contiguous()):
+            raise ValueError("event_spectrum: event_factor must be a contiguous float64 (K, n_events) tensor on the "
+                             "engine's device")
+        if kind == "coupling" and (not here(node_factor) or tuple(node_factor.shape) != (K, nn) or
+                                   (nn > 0 and not node_factor.is_contiguous())):
+            raise ValueError("event_spectrum: node_factor must be a contiguous float64 (K, n_nodes) tensor on the "
+                             "engine's device")
+        ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
+        so = _lib.EventSpectrumOut(_lib.REPLICATE_KINDS[kind], K, m, T, _p(node_factor) if kind == "coupling" else None,
+                                   _p(event_factor) if kind != "run" else None, _p(spec["count"]), _p(spec["sum"]),
+                                   _p(spec["sum_sq"]), _p(spec["totals"]), _p(spec["top_power"]) if T else None,
+                                   _p(spec["top_event"]) if T else None)
+        check(self.lib.art_event_spectrum_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]), C.byref(so),
+                                                 _stream()))
+        return spec
+
     @classmethod
     def _grid_fit(cls, Kg, Kh, R, nbins, errors):
         """ValueError when the grid's tables -- (1 + R) copies under replicates=R, plus the moment totals -- exceed
@@ -615,7 +681,7 @@ class Engine:
     def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
                    max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
                    cyclotron=False, rows=True, halo=None, errors=False, couplings=None, halos=None, replicates=None,
-                   grid=False) -> dict:
+                   grid=False, spectrum=None) -> dict:
         """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
         n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
         event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
@@ -687,6 +753,18 @@ class Engine:
         keywords, a ValueError before any work is done. A misplaced record is an ArtError. False (the default):
         exactly the keys below.
 
+        spectrum ({} or a dict of sub_bits, 0 to 4, default 3, and top, 0 to 256, default 64; DESIGN.md §3, "Event
+        power spectrum"): the distribution of the per-event power (event_spectrum per chunk), and the result gets
+        "spectrum", trees.spectrum_result's dict of host arrays: the histogram over range-free bins (edges, counts,
+        power), events, positive, zeros, bad, n_eff = S² / Q, top_event (global ids: run_events(1, event_offset=id)
+        replays one), top_power, top_share, max_share, and the Hill tail index alpha ± alpha_sigma with the Hill plot
+        hill. alpha <= 2: the variance does not exist and no σ of this run means what it says; alpha <= 1: nor does
+        the mean converge; otherwise read n_eff and top_share. With couplings= or halos= the scan's dict gets
+        "spectrum" too, with the scan's leading axis (the scans are then called with return_weights / return_ratio);
+        the grid gets none. It needs neither rows, errors nor replicates. Unknown keys, values out of range and tables
+        of more than Engine.SPECTRUM_MAX_BYTES (64 MiB) per set of tables are a ValueError before any work is done.
+        None (the default): exactly the keys below.
+
         Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
         or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
         f_inx, sum_weight_sln_prob, n_rows, n_photon_rows, and the raw, undivided parts for a caller that
@@ -699,6 +777,9 @@ class Engine:
             raise ValueError("grid: the coupling x halo grid needs couplings=, halos= and halo= (the base)")
         if replicates is not None:
             replicates = Engine._replicates_groups(replicates)  # (before any work is done)
+        if spectrum is not None:
+            from .trees import spectrum_keywords
+            spectrum = spectrum_keywords(spectrum)  # (before any work is done)
         if halos is not None:
             halos = halo_scan_models(halo, halos)  # (before any work is done)
         n_events = int(n_events)
@@ -718,6 +799,11 @@ class Engine:
                             ("the halo scan", halos and len(halos))):
                 if K:
                     self._replicates_fit(what, K, replicates, int(nbins), shape)
+        if spectrum is not None:  # (before any work is done)
+            for what, K in (("the run", 1), ("the coupling scan", couplings and len(couplings)),
+                            ("the halo scan", halos and len(halos))):
+                if K:
+                    self._spectrum_fit(what, K, spectrum[0])
         sky_hist = torch.zeros(*shape, dtype=F64, device=self.device) if shape else None
         max_r = self.params.max_r()
         if max_r < self.params.rNS:
@@ -726,9 +812,9 @@ class Engine:
         flux = torch.zeros(2 * int(nbins), dtype=F64, device=self.device)
         totals = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
         parts = []
-        moments = scan = hscan = rep = crep = hrep = cells = None
+        moments = scan = hscan = rep = crep = hrep = cells = spec = cspec = hspec = None
         want = replicates is not None
-        factors = want or bool(grid)  # the scans hand out their factors
+        factors = want or bool(grid) or spectrum is not None  # the scans hand out their factors
         for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
             c = min(chunk, int(event_offset) + n_events - lo)
             s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r, halo=halo)
@@ -764,6 +850,14 @@ class Engine:
                 if halos is not None:
                     hrep = self.event_replicates(s, w5, back, fwd, replicates, rep=hrep, kind="halo",
                                                  event_factor=hscan["ratio"], **kw)
+            if spectrum is not None:
+                kw = dict(sub_bits=spectrum[0], top=spectrum[1], event_offset=lo, cyclotron_rerun=r["cyclotron_rerun"])
+                spec = self.event_spectrum(s, w5, back, fwd, spec=spec, **kw)
+                if couplings is not None:
+                    cspec = self.event_spectrum(s, w5, back, fwd, spec=cspec, kind="coupling", node_factor=scan["weights"],
+                                                event_factor=scan["back"], **kw)
+                if halos is not None:
+                    hspec = self.event_spectrum(s, w5, back, fwd, spec=hspec, kind="halo", event_factor=hscan["ratio"], **kw)
             if factors:  # (this chunk's factors are not part of the scans' tables)
                 for d, keys in ((scan, ("weights", "back", "back_prob")), (hscan, ("ratio",))):
                     for k in keys if d is not None else ():
@@ -829,6 +923,17 @@ class Engine:
                 out["replicates"] = replicates_result(replicates_raw(have), f_inx)
                 if out["replicates"]["misplaced"] != 0:
                     raise _lib.ArtError(f"run_events: {out['replicates']['misplaced']} node records lie in the range of "
+                                        "another tree")
+        if spectrum is not None:
+            from .trees import spectrum_raw, spectrum_result
+            for out, have, kind, K in ((res, spec, "run", 1), (res.get("coupling_scan"), cspec, "coupling", len(couplings or ())),
+                                       (res.get("halo_scan"), hspec, "halo", len(halos or ()))):
+                if out is None:
+                    continue
+                have = self._zero_spectrum(kind, K, *spectrum) if have is None else have  # (no events)
+                out["spectrum"] = spectrum_result(spectrum_raw(have), f_inx)
+                if out["spectrum"]["misplaced"] != 0:
+                    raise _lib.ArtError(f"run_events: {out['spectrum']['misplaced']} node records lie in the range of "
                                         "another tree")
         if grid:
             from .trees import grid_raw, grid_result

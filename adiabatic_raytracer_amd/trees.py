@@ -198,7 +198,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
                      sky_map=None, device_trees=False, device_events=False, halo=None, errors=False,
-                     couplings=None, halos=None, replicates=None, grid=False):
+                     couplings=None, halos=None, replicates=None, grid=False, spectrum=None):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -290,7 +290,17 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     (Engine.run_events(grid=True)), with the per-group tables under replicates= and the moment totals under errors=.
     run_info["grid"] is grid_result's dict from the tables summed over the ranks, the last part of the vector of the
     same all-reduce; limit_band(run_info["grid"], power) reads the limit on g per halo model off it. With the default
-    False every row, file, run_info key and the reduced vector are unchanged."""
+    False every row, file, run_info key and the reduced vector are unchanged.
+
+    spectrum (beyond the reference; {} or a dict of sub_bits, 0 to 4, and top, 0 to 256; DESIGN.md §3, "Event power
+    spectrum"): the distribution of the per-event power, on all three paths: run_info["spectrum"] is spectrum_result's
+    dict -- the histogram over range-free bins, n_eff, the top events with their global ids and the share of the
+    power they carry, and the Hill tail index α -- from the tables summed over the ranks and the ranks' lists merged,
+    the last parts of the vector of the same all-reduce. The host paths take the tables from the rank's rows
+    (rows_spectrum); device_events takes them from art_event_spectrum_device, and there the scans' dicts get
+    "spectrum" too. With the default None every row, file, run_info key and the reduced vector are unchanged."""
+    if spectrum is not None:
+        spectrum_keywords(spectrum)  # (before any work is done)
     if grid and not device_events:
         raise ValueError("grid: the coupling x halo grid is formed from forests held in HBM and needs device_events=True")
     if grid and (couplings is None or halos is None or halo is None):
@@ -313,7 +323,8 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                                         backtrace_cap=backtrace_cap, rank=rank, world=world, nbins=nbins, run_info=run_info,
                                         cyclotron=cyclotron, sky_map=sky_map, halo=halo, errors=errors,
                                         couplings=couplings, halos=halos, replicates=replicates,
-                                        **({"grid": True} if grid else {}))
+                                        **({"grid": True} if grid else {}),
+                                        **({} if spectrum is None else {"spectrum": spectrum}))
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -402,13 +413,16 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     path = None if dir_tag is None else tree_file_name(dir_tag, params.mass_a, params.g_agg, params.theta_m, params.omega_pul,
                                                        params.B0, Ntajs, ntimes, num_cutoff, MC_nodes, max_nodes, tag)
     rep = None if replicates is None else {"run": rows_replicates(rows, replicates, nbins, sky_kw, s["attempts"], lo)}
+    spec = None if spectrum is None else {"run": rows_spectrum(rows, *spectrum_keywords(spectrum), event_lo=lo, n_events=n_ev)}
     return _finish_run(rows, tot, nbins=nbins, sky_kw=sky_kw, errors=errors, world=world, run_info=run_info,
-                       events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path, **({} if rep is None else {"replicates": rep}))
+                       events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path, **({} if rep is None else {"replicates": rep}),
+                       **({} if spec is None else {"spectrum": spec, "rank": rank}))
 
 
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
                              saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map,
-                             halo=None, errors=False, couplings=None, halos=None, replicates=None, grid=False):
+                             halo=None, errors=False, couplings=None, halos=None, replicates=None, grid=False,
+                             spectrum=None):
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
@@ -425,7 +439,12 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                                   **({} if couplings is None else {"couplings": couplings}),
                                   **({} if halos is None else {"halos": halos}),
                                   **({} if replicates is None else {"replicates": replicates}),
-                                  **({"grid": True} if grid else {}))
+                                  **({"grid": True} if grid else {}),
+                                  **({} if spectrum is None else {"spectrum": spectrum}))
+    spec = None
+    if spectrum is not None:
+        spec = {"run": r["spectrum"]["raw"]}
+        spec.update({k: r[k + "_scan"]["spectrum"]["raw"] for k in ("coupling", "halo") if k + "_scan" in r})
     rep = None
     if replicates is not None:
         rep = {"run": r["replicates"]["raw"]}
@@ -440,7 +459,8 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
     return _finish_run(rows, tot, None if couplings is None else r["coupling_scan"]["raw"],
                        None if halos is None else r["halo_scan"]["raw"], nbins=nbins, sky_kw=sky_kw, errors=errors,
                        world=world, run_info=run_info, events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path,
-                       **({} if rep is None else {"replicates": rep}), **({"grid": r["grid"]["raw"]} if grid else {}))
+                       **({} if rep is None else {"replicates": rep}), **({"grid": r["grid"]["raw"]} if grid else {}),
+                       **({} if spec is None else {"spectrum": spec, "rank": rank}))
 
 
 def cyclotron_optical_depth(params: Params, fin, erg) -> np.ndarray:
@@ -1372,6 +1392,238 @@ def limit_band(grid, power, species=PHOTON, average=None) -> dict:
     return out
 
 
+SPECTRUM_TABLES = ("count", "sum", "sum_sq", "totals")  # what adds; the lists top_power and top_event merge
+
+
+def spectrum_bins(sub_bits) -> int:
+    """The bins of the event power spectrum with sub_bits sub-octave bits: 2047 << sub_bits"""
+    return 2047 << int(sub_bits)
+
+
+def spectrum_bin(x, sub_bits) -> np.ndarray:
+    """The bin of each x by art_event_spectrum_device's rule: the top 11 + sub_bits bits of the IEEE-754 pattern,
+    x.view(int64) >> (52 - sub_bits), for a finite x > 0; -1 otherwise (0, -0.0, negatives, NaN, inf)"""
+    x = np.ascontiguousarray(x, np.float64)
+    ok = np.isfinite(x) & (x > 0)
+    return np.where(ok, x.view(np.int64) >> (52 - int(sub_bits)), -1)
+
+
+def spectrum_edges(lo, hi, sub_bits) -> np.ndarray:
+    """The lower edges of the bins lo .. hi (hi included: hi - lo + 1 doubles; the edge of bin 2047 << sub_bits, the
+    upper edge of the last bin, is inf): the doubles whose pattern is b << (52 - sub_bits)"""
+    return (np.arange(int(lo), int(hi) + 1, dtype=np.int64) << (52 - int(sub_bits))).view(np.float64)
+
+
+def _spectrum_check(sub_bits, top):
+    m, T = int(sub_bits), int(top)
+    if m != sub_bits or not 0 <= m <= _lib.SPECTRUM_MAX_SUB_BITS:
+        raise ValueError(f"spectrum: sub_bits is 0 to {_lib.SPECTRUM_MAX_SUB_BITS}, not {sub_bits!r}")
+    if T != top or not 0 <= T <= _lib.SPECTRUM_MAX_TOP:
+        raise ValueError(f"spectrum: top is 0 to {_lib.SPECTRUM_MAX_TOP}, not {top!r}")
+    return m, T
+
+
+def spectrum_keywords(spectrum) -> tuple:
+    """(sub_bits, top) of a spectrum= keyword ({}: the defaults 3 and 64); unknown keys and values out of range are a
+    ValueError"""
+    from collections.abc import Mapping
+    if not isinstance(spectrum, Mapping):
+        raise ValueError(f"spectrum: a dict of sub_bits and top ({{}}: the defaults), not {spectrum!r}")
+    extra = set(spectrum) - {"sub_bits", "top"}
+    if extra:
+        raise ValueError(f"spectrum: unknown keys {sorted(extra)} (sub_bits, top)")
+    return _spectrum_check(spectrum.get("sub_bits", 3), spectrum.get("top", 64))
+
+
+def _spectrum_top(X, ids, T):
+    """The list of one (set, species): the T pairs with the largest finite X > 0 by (X descending, id ascending),
+    padded with (0.0, -1)"""
+    X, ids = np.asarray(X, np.float64), np.asarray(ids, np.int64)
+    ok = np.isfinite(X) & (X > 0)
+    X, ids = X[ok], ids[ok]
+    order = np.lexsort((ids, -X.view(np.int64)))[:T]  # (the pattern of a finite X > 0 is monotone in X)
+    tp, te = np.zeros(T), np.full(T, -1, np.int64)
+    tp[:len(order)], te[:len(order)] = X[order], ids[order]
+    return tp, te
+
+
+def _spectrum_tables(X, ids, m, T) -> dict:
+    """The raw dict of the sets X (K, 2, n): X[k, s, i] the power of species s of the event with the global id ids[i]"""
+    K, NB = X.shape[0], spectrum_bins(m)
+    out = {"count": np.zeros((K, 2, NB)), "sum": np.zeros((K, 2, NB)), "sum_sq": np.zeros((K, 2, NB)),
+           "totals": np.zeros((K, 2, len(_lib.SPECTRUM_TOTALS))), "top_power": np.zeros((K, 2, T)),
+           "top_event": np.full((K, 2, T), -1, np.int64)}
+    for k in range(K):
+        for s in range(2):
+            x = np.ascontiguousarray(X[k, s])
+            b = spectrum_bin(x, m)
+            ok = b >= 0
+            xp = x[ok]
+            with np.errstate(over="ignore", under="ignore"):
+                x2 = xp * xp
+            out["count"][k, s] = np.bincount(b[ok], minlength=NB)
+            out["sum"][k, s] = np.bincount(b[ok], weights=xp, minlength=NB)
+            out["sum_sq"][k, s] = np.bincount(b[ok], weights=x2, minlength=NB)
+            zeros = int(np.count_nonzero(x == 0))
+            out["totals"][k, s, :6] = (len(x), len(xp), zeros, len(x) - len(xp) - zeros, xp.sum(), x2.sum())
+            out["top_power"][k, s], out["top_event"][k, s] = _spectrum_top(x, ids, T)
+    return out
+
+
+def rows_spectrum(rows, sub_bits, top, event_lo=0, n_events=None) -> dict:
+    """art_event_spectrum_device's tables in numpy from npy rows (column 7 raw: the tables are in the powers' own
+    units), for kind "run": the oracle of the device tables, and the path for row files written earlier. X of an event
+    and species is Σ column 8 * column 7 over its rows of that species in row order (np.bincount), its global id is
+    column 0 - 1. The events are event_lo .. event_lo + n_events (n_events=None: up to the last event that has a
+    row); one without a row of a species has X = 0 and is counted under zeros. Returns the raw dict that
+    spectrum_raw returns: kind, sub_bits, top, count, sum, sum_sq (1, 2, 2047 << sub_bits), totals (1, 2, 8:
+    _lib.SPECTRUM_TOTALS), top_power (1, 2, top) and top_event (1, 2, top; int64)."""
+    m, T = _spectrum_check(sub_bits, top)
+    rows = np.asarray(rows, np.float64)
+    lo = int(event_lo)
+    gid = np.rint(rows[:, 0]).astype(np.int64) - 1
+    n = int(n_events) if n_events is not None else (int(gid.max()) + 1 - lo if len(rows) else 0)
+    if len(rows) and (gid.min() < lo or gid.max() >= lo + n):
+        raise ValueError("rows_spectrum: a row's event lies outside event_lo .. event_lo + n_events")
+    sp = rows[:, 1] != 0
+    p = rows[:, 8] * rows[:, 7]
+    X = np.stack([np.bincount(gid[w] - lo, weights=p[w], minlength=n) if n else np.zeros(0) for w in (~sp, sp)])[None]
+    return {"kind": "run", "sub_bits": m, "top": T, **_spectrum_tables(X, np.arange(lo, lo + n, dtype=np.int64), m, T)}
+
+
+def spectrum_raw(spec) -> dict:
+    """Engine.event_spectrum's dict with its tables and lists on the host (numpy): the tables add over chunks and
+    ranks, the lists merge (spectrum_merge)"""
+    host = lambda v: v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)  # noqa: E731
+    out = {"kind": spec["kind"], "sub_bits": int(spec["sub_bits"]), "top": int(spec["top"])}
+    out.update({k: host(spec[k]).astype(np.float64, copy=False) for k in SPECTRUM_TABLES + ("top_power",)})
+    out["top_event"] = host(spec["top_event"]).astype(np.int64, copy=False)
+    return out
+
+
+def spectrum_merge(raws) -> dict:
+    """The raw spectrum of several chunks, ranks or files (raw dicts of one kind, sub_bits, top and number of sets):
+    the tables summed, the lists merged into the best `top` of all their entries by (X descending, id ascending). The
+    lists are a function of the multiset of their entries, so the merge is associative and does not depend on the
+    order of `raws`; the tables' sums are float64 adds in the order given."""
+    raws = list(raws)
+    if not raws:
+        raise ValueError("spectrum_merge: nothing to merge")
+    a = raws[0]
+    for b in raws[1:]:
+        if any(b[k] != a[k] for k in ("kind", "sub_bits", "top")) or b["count"].shape != a["count"].shape:
+            raise ValueError("spectrum_merge: the spectra were made for another kind, sub_bits, top or number of sets")
+    out = {"kind": a["kind"], "sub_bits": a["sub_bits"], "top": a["top"]}
+    for k in SPECTRUM_TABLES:
+        out[k] = np.asarray(a[k], np.float64).copy()
+        for b in raws[1:]:
+            out[k] = out[k] + np.asarray(b[k], np.float64)
+    K, T = a["count"].shape[0], int(a["top"])
+    out["top_power"], out["top_event"] = np.zeros((K, 2, T)), np.full((K, 2, T), -1, np.int64)
+    for k in range(K):
+        for s in range(2):
+            X = np.concatenate([np.asarray(r["top_power"], np.float64)[k, s] for r in raws])
+            ids = np.concatenate([np.asarray(r["top_event"], np.int64)[k, s] for r in raws])
+            have = ids >= 0
+            out["top_power"][k, s], out["top_event"][k, s] = _spectrum_top(X[have], ids[have], T)
+    return out
+
+
+def spectrum_pack(raw, rank=0, world=1) -> np.ndarray:
+    """A rank's raw spectrum as one vector for the run's all-reduce: [count | sum | sum_sq | totals | powers | ids].
+    A sum cannot merge lists, so powers and ids are zeroed blocks of world x (K 2 top) in which the rank fills slot
+    `rank` alone: after the sum slot r holds rank r's list (an id as float64 is exact below 2^53)."""
+    tp, te = np.asarray(raw["top_power"], np.float64).reshape(-1), np.asarray(raw["top_event"], np.int64).reshape(-1)
+    if te.size and te.max() >= 2 ** 53:
+        raise ValueError("spectrum_pack: an event id of 2^53 or more is not exact as float64")
+    blocks = np.zeros((2, int(world), tp.size))
+    blocks[0, int(rank)], blocks[1, int(rank)] = tp, te
+    return np.concatenate([np.asarray(raw[k], np.float64).reshape(-1) for k in SPECTRUM_TABLES] + [blocks.reshape(-1)])
+
+
+def spectrum_unpack(vec, like, world=1) -> dict:
+    """spectrum_pack's vector, summed over the ranks, back into a raw dict shaped like `like` (the rank's own): the
+    tables as they are, the `world` lists merged by spectrum_merge"""
+    out, at = {"kind": like["kind"], "sub_bits": like["sub_bits"], "top": like["top"]}, 0
+    for k in SPECTRUM_TABLES:
+        out[k] = np.asarray(vec[at:at + like[k].size], np.float64).reshape(like[k].shape)
+        at += like[k].size
+    shape, size = like["top_power"].shape, like["top_power"].size
+    blocks = np.asarray(vec[at:at + 2 * int(world) * size], np.float64).reshape(2, int(world), size)
+    zero = {k: np.zeros_like(out[k]) for k in SPECTRUM_TABLES}
+    lists = [{**out, **zero, "top_power": blocks[0, r].reshape(shape), "top_event": np.rint(blocks[1, r]).astype(np.int64).reshape(shape)}
+             for r in range(int(world))]
+    merged = spectrum_merge(lists)
+    out["top_power"], out["top_event"] = merged["top_power"], merged["top_event"]
+    return out
+
+
+def tail_index(top_power, k=None) -> dict:
+    """The Hill estimator of the tail index α of P(X > x) ~ x^-α from a top list: over its valid entries
+    X_(1) >= X_(2) >= ... (finite, > 0; T' of them), α̂_k = k / Σ_{i<=k} ln(X_(i) / X_(k+1)) with σ = α̂_k / √k.
+    Returns alpha and alpha_sigma at k (None: the largest, T' - 1), k, and hill, α̂_k for k = 2 .. T' - 1 (the Hill
+    plot: read α where it is flat). NaN below 3 entries, or where the logs sum to 0 (equal entries).
+    α <= 2: the variance of X does not exist and no σ of a sum of X means what it says; α <= 1: nor does the mean."""
+    x = np.asarray(top_power, np.float64).reshape(-1)
+    x = np.sort(x[np.isfinite(x) & (x > 0)])[::-1]
+    n = len(x)
+    nan = float("nan")
+    if n < 3:
+        return {"alpha": nan, "alpha_sigma": nan, "k": 0, "hill": np.zeros(0)}
+    lg = np.log(x)
+    ks = np.arange(2, n)
+    sums = np.cumsum(lg)[ks - 1] - ks * lg[ks]  # Σ_{i<=k} ln X_(i) - k ln X_(k+1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        hill = np.where(sums > 0, ks / sums, nan)
+    kk = n - 1 if k is None else int(k)
+    if not 2 <= kk <= n - 1:
+        raise ValueError(f"tail_index: k must be in 2 .. {n - 1}, not {k!r}")
+    alpha = float(hill[kk - 2])
+    return {"alpha": alpha, "alpha_sigma": alpha / np.sqrt(kk), "k": kk, "hill": hill}
+
+
+def spectrum_result(raw, f_inx) -> dict:
+    """The event power spectrum of a run from its raw tables (spectrum_raw, rows_spectrum or spectrum_merge) and the
+    run's f_inx. With the leading K axis of a scan's sets (none for kind "run") and then the species axis (0 axion,
+    1 photon): bins (the first and last non-empty bin over all sets, or None), edges (the bins' edges, one more than
+    bins), counts and power (sum / f_inx) over that span; events, positive, zeros, bad; n_eff = S² / Q, how many
+    equal events would scatter as these do; top_event, top_power_raw and top_power (/ f_inx); top_share, the share
+    of S in the top 1 .. T events, and max_share, the largest event's; alpha, alpha_sigma and hill (NaN-padded to
+    T - 2) by tail_index of each list; misplaced (must be 0); sub_bits, top, kind, f_inx and raw."""
+    m, T = int(raw["sub_bits"]), int(raw["top"])
+    tot = np.asarray(raw["totals"], np.float64)
+    count = np.asarray(raw["count"], np.float64)
+    f = float(f_inx)
+    S, Q = tot[..., 4], tot[..., 5]
+    tp = np.asarray(raw["top_power"], np.float64)
+    K = count.shape[0]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        res = {"n_eff": np.where(Q > 0, S * S / Q, np.nan), "top_share": np.cumsum(tp, axis=-1) / S[..., None],
+               "top_power": tp / f if f != 0 else np.full(tp.shape, np.nan)}
+    res["max_share"] = res["top_share"][..., 0] if T > 0 else np.full(S.shape, np.nan)
+    used = np.flatnonzero(count.sum(axis=(0, 1)) > 0)
+    if len(used):
+        lo, hi = int(used[0]), int(used[-1])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            power = np.asarray(raw["sum"], np.float64)[..., lo:hi + 1] / f if f != 0 else np.full(count[..., lo:hi + 1].shape, np.nan)
+        res.update(bins=(lo, hi), edges=spectrum_edges(lo, hi + 1, m), counts=count[..., lo:hi + 1], power=power)
+    else:
+        res.update(bins=None, edges=np.zeros(0), counts=count[..., :0], power=count[..., :0])
+    res.update(events=tot[..., 0], positive=tot[..., 1], zeros=tot[..., 2], bad=tot[..., 3],
+               top_event=np.asarray(raw["top_event"], np.int64), top_power_raw=tp)
+    alpha, sigma, hill = np.full((K, 2), np.nan), np.full((K, 2), np.nan), np.full((K, 2, max(T - 2, 0)), np.nan)
+    for k in range(K):
+        for s in range(2):
+            t = tail_index(tp[k, s])
+            alpha[k, s], sigma[k, s] = t["alpha"], t["alpha_sigma"]
+            hill[k, s, :len(t["hill"])] = t["hill"]
+    res.update(alpha=alpha, alpha_sigma=sigma, hill=hill)
+    if raw["kind"] == "run":
+        res = {k: (v[0] if isinstance(v, np.ndarray) and v.ndim >= 2 and k != "edges" else v) for k, v in res.items()}
+    res.update(misplaced=int(round(float(tot[..., 6].sum()))), sub_bits=m, top=T, kind=raw["kind"], f_inx=int(f_inx), raw=raw)
+    return res
+
+
 def pack_totals(flux, f_inx, sum_axion, sum_photon, n_rows, sky=None, moments=None) -> np.ndarray:
     """A rank's part of main_runner_tree's single all-reduce: [flux (2 nbins) | f_inx | Σ weight *
     sln_prob (axions, photons) | rows], then the sky map's table when there is one, then with moments
@@ -1423,31 +1675,40 @@ def _sigma_info(tt, nbins) -> dict:
 REPLICATE_PARTS = ("run", "coupling", "halo")  # the order of the replicate parts of a rank's vector
 
 
-def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None, grid=None):
+SPECTRUM_PARTS = ("run", "coupling", "halo")  # the order of the spectrum parts of a rank's vector
+
+
+def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None, grid=None, spectrum=None, rank=0, world=1):
     """A rank's vector for main_runner_tree's single all-reduce, [pack_totals | coupling scan | halo scan |
     replicates... | grid]: the rank's pack_totals vector, then scan_pack of its coupling scan's raw tables and
     halo_scan_pack of its halo scan's, each only when there is one, then replicates_pack of each raw dict of
     `replicates` (a dict with the keys "run", "coupling", "halo" there are, in that order; None: none), then grid_pack
-    of `grid` (the rank's grid_raw; None: none) LAST, so every earlier part keeps its place and its end. Returns (the
-    vector, where each of its parts ends)."""
+    of `grid` (the rank's grid_raw; None: none), so every earlier part keeps its place and its end, and LAST
+    spectrum_pack(raw, rank, world) of each raw dict of `spectrum` (a dict with the keys "run", "coupling", "halo"
+    there are, in that order; None: none, and the vector is what it is without the keyword). Returns (the vector,
+    where each of its parts ends)."""
     parts = [totals] + [pack(raw) for pack, raw in ((scan_pack, coupling_raw), (halo_scan_pack, halo_raw)) if raw is not None]
     parts += [replicates_pack(replicates[k]) for k in REPLICATE_PARTS if replicates and replicates.get(k) is not None]
     if grid is not None:
         parts.append(grid_pack(grid))
+    parts += [spectrum_pack(spectrum[k], rank, world) for k in SPECTRUM_PARTS if spectrum and spectrum.get(k) is not None]
     return (np.concatenate(parts) if len(parts) > 1 else totals), np.cumsum([len(v) for v in parts])
 
 
 def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw, errors, world, run_info, events, n_events,
-                g0, path, replicates=None, grid=None):
+                g0, path, replicates=None, grid=None, spectrum=None, rank=0):
     """The end of main_runner_tree on every path: the rank's vector (rank_vector of its pack_totals vector and its
     scans' raw tables) summed over the ranks in ONE all-reduce, σ from the reduced tables, column 8 of the rank's
     rows divided by the global f_inx, run_info (a dict or None; events: the rank's (lo, hi), n_events: the run's),
     and with `path` the npy file and, with a sky map, skymap_<its stem>.npz beside it. g0: the run's coupling, the
     coupling scan's base. replicates: the rank's raw replicate tables (rank_vector's keyword), which end the vector
     and come back as run_info["replicates"] and as "replicates" in the scans' dicts. grid: the rank's grid_raw, the
-    vector's last part, which comes back as run_info["grid"] (grid_result). Returns the rows."""
+    vector's part after them, which comes back as run_info["grid"] (grid_result). spectrum: the rank's raw spectra
+    (rank_vector's keyword; rank: this rank's slot for its lists), the vector's last parts, which come back merged
+    over the ranks as run_info["spectrum"] and as "spectrum" in the scans' dicts (spectrum_result). Returns the rows."""
     from .shard import allreduce_sum
-    tot, ends = rank_vector(totals, coupling_raw, halo_raw, replicates=replicates, **({} if grid is None else {"grid": grid}))
+    tot, ends = rank_vector(totals, coupling_raw, halo_raw, replicates=replicates, **({} if grid is None else {"grid": grid}),
+                            **({} if spectrum is None else {"spectrum": spectrum, "rank": rank, "world": world}))
     n_scans = (coupling_raw is not None) + (halo_raw is not None)
     if world > 1:
         tot = allreduce_sum(tot)
@@ -1475,8 +1736,15 @@ def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw
             raw = replicates_unpack(tot[ends[n_scans + j]:ends[n_scans + j + 1]], replicates[k])
             where = run_info if k == "run" else run_info[k + "_scan"]
             where["replicates"] = replicates_result(raw, int(round(f_glob)))
+        n_rep = len(have)
         if grid is not None:
-            run_info["grid"] = grid_result(grid_unpack(tot[ends[-2]:ends[-1]], grid), int(round(f_glob)))
+            at = n_scans + n_rep
+            run_info["grid"] = grid_result(grid_unpack(tot[ends[at]:ends[at + 1]], grid), int(round(f_glob)))
+        at = n_scans + n_rep + (grid is not None)
+        for j, k in enumerate(k for k in SPECTRUM_PARTS if spectrum and spectrum.get(k) is not None):
+            raw = spectrum_unpack(tot[ends[at + j]:ends[at + j + 1]], spectrum[k], world)
+            where = run_info if k == "run" else run_info[k + "_scan"]
+            where["spectrum"] = spectrum_result(raw, int(round(f_glob)))
     if path is not None:
         os.makedirs(os.path.dirname(path), exist_ok=True)
         np.save(path, rows)

@@ -829,6 +829,49 @@ typedef struct art_event_grid_out {
 int art_event_grid_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
                           const art_event_grid_out* out, void* stream);
 
+/* ---- event power spectrum: the distribution of the per-event power, its tail and its largest events ----
+ * Every product of a run is a sum over events of X_{e,s}, art_event_moments_device's X: the powers of event e's final
+ * rows of species s (0 axion, 1 photon), binned or not, summed in node order (a record in the range of a tree other
+ * than its own is skipped and counted). This call keeps the DISTRIBUTION of X per set k and species s; the sets and
+ * their powers by kind are art_event_replicates_device's (0 the run's own, n_sets = 1; 1 a coupling scan's from
+ * node_factor and event_factor; 2 a halo scan's from event_factor). Everything is ACCUMULATED into (zero it first),
+ * ordinary device memory, float64, and adds over chunks and ranks; entry (k, s) of a table lies at 2 k + s times
+ * the table's size.
+ *   Bins need no range: for a finite X > 0, bin = bits(X) >> (52 - sub_bits), the top 11 + sub_bits bits of the
+ *   IEEE-754 pattern: 2^sub_bits bins per octave, NB = 2047 << sub_bits bins from the subnormals to the largest
+ *   finite double, monotone in X; the lower edge of bin b is the double with the pattern b << (52 - sub_bits).
+ *   count[b], sum[b], sum_sq[b]: the events whose X falls in bin b, their Σ X and Σ X².
+ *   totals (8): [0] events, [1] events with finite X > 0, [2] with X == 0, [3] bad ones (negative, NaN, infinite:
+ *   counted, and kept out of every table and list), [4] S = Σ X and [5] Q = Σ X² over [1], [6] misplaced records (in
+ *   entry (0, 0) only; must stay 0), [7] reserved, 0. n_eff = S² / Q.
+ *   The list: the `top` events with the largest finite X > 0, ordered by (X descending, global id ascending), as
+ *   top_power and top_event (the 0-based id event_offset + tree, column 0 - 1 of a row), unused entries (0.0, -1).
+ *   It is carried IN and OUT: the entries with id >= 0 found in the buffers are candidates of the call, so after any
+ *   number of calls the list is a function of the multiset of (X, id) seen, whatever the chunks and their order.
+ *   Start it as (0.0, -1). */
+typedef struct art_event_spectrum_out {
+  int32_t kind;                /* art_event_replicates_out's: 0 the run, 1 a coupling scan, 2 a halo scan */
+  int32_t n_sets;              /* K, 1 .. 32; 1 with kind 0                                           */
+  int32_t sub_bits;            /* m, 0 .. 4                                                           */
+  int32_t top;                 /* T, 0 .. 256 (0: no list)                                            */
+  const double* node_factor;   /* K * n_nodes  INPUT, kind 1: W_k of every record                    */
+  const double* event_factor;  /* K * n_events INPUT, kind 1: B_k; kind 2: R_k of every event         */
+  double* count;               /* K * 2 * (2047 << m)                                                 */
+  double* sum;                 /* K * 2 * (2047 << m)                                                 */
+  double* sum_sq;              /* K * 2 * (2047 << m)                                                 */
+  double* totals;              /* K * 2 * 8                                                           */
+  double* top_power;           /* K * 2 * T, IN and OUT                                               */
+  int64_t* top_event;          /* K * 2 * T, IN and OUT                                               */
+} art_event_spectrum_out;
+/* Asynchronous on `stream`, no host read and no host synchronisation; scratch (K 2 n_events doubles and 16 B per
+ * record) comes from the stream-ordered allocator. Every table takes float64 hardware adds. ART_E_INVALID before any
+ * device is touched: a NULL p, in or out; an unknown kind; n_sets outside 1 .. 32, or not 1 with kind 0; sub_bits
+ * outside 0 .. 4; top outside 0 .. 256; a NULL event_factor with kind 1 or 2, a NULL node_factor with kind 1 and
+ * n_nodes > 0; a NULL node_start with n_nodes > 0; a NULL count, sum, sum_sq or totals; a NULL top_power or
+ * top_event with top > 0. n_events == 0: ART_OK, nothing touched. */
+int art_event_spectrum_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                              const art_event_spectrum_out* out, void* stream);
+
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the
  * other ranks (a file, MPI, the launcher); every rank then calls art_comm_init on its device.

@@ -286,6 +286,44 @@ int main() {
     ei.n_events = ei.n_nodes = 0;
     go.node_factor = go.back = go.ratio = nullptr; go.flux = go.totals = nullptr;
     CHECK(art_event_grid_device(&p, &ei, nullptr, &go, nullptr) == ART_OK);
+    // the event power spectrum: the kind, the sets, the bins, the list and its factor arrays, node_start and the
+    // tables, all before the device
+    art_event_spectrum_out so{};
+    so.kind = 0; so.n_sets = 1; so.sub_bits = 3; so.top = 64;
+    so.count = so.sum = so.sum_sq = so.totals = so.top_power = d; so.top_event = (int64_t*)d;
+    ei.n_events = ei.n_nodes = 4;
+    CHECK(art_event_spectrum_device(nullptr, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    CHECK(art_event_spectrum_device(&p, nullptr, ns, &so, nullptr) == ART_E_INVALID);
+    CHECK(art_event_spectrum_device(&p, &ei, ns, nullptr, nullptr) == ART_E_INVALID);
+    so.kind = 3;
+    CHECK(art_event_spectrum_device(&p, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    so.kind = 0; so.n_sets = 2;  // the run has one set
+    CHECK(art_event_spectrum_device(&p, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    so.n_sets = 1;
+    for (int bad_bits : {-1, 5}) {
+      so.sub_bits = bad_bits;
+      CHECK(art_event_spectrum_device(&p, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    }
+    so.sub_bits = 4;
+    for (int bad_top : {-1, 257}) {
+      so.top = bad_top;
+      CHECK(art_event_spectrum_device(&p, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    }
+    so.top = 256; so.kind = 1; so.n_sets = 33; so.node_factor = so.event_factor = d;
+    CHECK(art_event_spectrum_device(&p, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    so.n_sets = 32; so.node_factor = nullptr;  // a coupling scan's weights
+    CHECK(art_event_spectrum_device(&p, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    so.kind = 2; so.event_factor = nullptr;  // a halo scan's ratios
+    CHECK(art_event_spectrum_device(&p, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    so.kind = 0; so.n_sets = 1;
+    CHECK(art_event_spectrum_device(&p, &ei, nullptr, &so, nullptr) == ART_E_INVALID);  // node_start
+    so.sum_sq = nullptr;
+    CHECK(art_event_spectrum_device(&p, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    so.sum_sq = d; so.top_event = nullptr;
+    CHECK(art_event_spectrum_device(&p, &ei, ns, &so, nullptr) == ART_E_INVALID);
+    so.top = 0; so.top_power = nullptr;  // no list: its buffers are not asked for
+    ei.n_events = ei.n_nodes = 0;
+    CHECK(art_event_spectrum_device(&p, &ei, nullptr, &so, nullptr) == ART_OK);
     // where the four event calls differ on purpose (art_post.cpp's front-end flags). A call that passes its
     // argument checks goes on to the device, which this container does not have.
     auto went_on = [](int r) { return r == ART_E_HIP || r == ART_E_NOMEM || r == ART_OK; };

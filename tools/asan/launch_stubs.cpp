@@ -88,6 +88,7 @@ hipError_t launch_event_replicates(const EventRowsArgs&, const EventReplicatesAr
   return hipErrorNoDevice;
 }
 hipError_t launch_event_grid(const EventRowsArgs&, const EventGridArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_event_spectrum(const EventRowsArgs&, const EventSpectrumArgs&, hipStream_t) { return hipErrorNoDevice; }
 MFn nl_eval_math(int) { return nullptr; }
 hipError_t launch_eval_math(int, int, int64_t, const double*, const double*, double*, double*, hipStream_t) {
   return hipErrorNoDevice;
