@@ -249,6 +249,9 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
     for (int s = 0; s < NSLOT; ++s) {
       const SlotRow R = PF ? Rnext : T.row[s];
       const double cf = R.cf, cA = R.cA;
+      double cq[LDS_SLOTS];  // the row of LDS coefficients, loaded with R: one scalar wait per slot
+#pragma unroll
+      for (int q = 0; q < LDS_SLOTS; ++q) cq[q] = T.cL[s][q];
       double acc[7];
 #pragma unroll
       for (int i = 0; i < 7; ++i) acc[i] = cf * f[i];
@@ -256,16 +259,19 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
 #pragma unroll
         for (int i = 0; i < 7; ++i) acc[i] = fma(cf, f[i], cA * kA[i]);  // (the rounding of the general form)
       }
-      // the LDS slots this stage reads form one contiguous range [qlo, qhi) (lmask): no
-      // per-slot load-compare-branch, and each coefficient load overlaps the slot's LDS reads
+      // one block per LDS slot, guarded by the slot's wave-uniform bit of lmask (compile-time bounds:
+      // no trip count, no remainder loop). A block's seven reads land in temporaries of their own, so
+      // all are in flight before its first FMA and nothing but LDS reads is waited for. The order of
+      // the sum, ascending q, is the results' (art_tail.h folds the same sums).
       const int lm = R.lmask;
-      if (lm != 0) {
-        const int qhi = 32 - __builtin_clz(lm);
-#pragma unroll QUNROLL
-        for (int q = __builtin_ctz(lm); q < qhi; ++q) {
-          const double c = T.cL[s][q];
 #pragma unroll
-          for (int i = 0; i < 7; ++i) acc[i] += c * L[(q * 7 + i) * BLOCK];
+      for (int q = 0; q < LDS_SLOTS; ++q) {
+        if ((lm >> q) & 1) {
+          double t[7];
+#pragma unroll
+          for (int i = 0; i < 7; ++i) t[i] = L[(q * 7 + i) * BLOCK];
+#pragma unroll
+          for (int i = 0; i < 7; ++i) acc[i] += cq[q] * t[i];
         }
       }
 #pragma unroll

@@ -177,12 +177,14 @@ __device__ inline int affect(const KParams& P, const SegIn& in, const SegOut& ou
 // overlap) and L_0..L_4 are stage vectors parked in LDS (k3..k7 for Vern6; k3, k4 for RK4).
 // Coefficients are wave-uniform scalar loads; the RHS is inlined once.
 constexpr int LDS_SLOTS = 5;
-// The wave-uniform scalars of one slot in one 48-byte row: a single scalar load and wait at
-// the slot's start (the cL coefficients are loaded inside the LDS loop, where their latency
-// overlaps the LDS reads).
+// The wave-uniform scalars of one slot in one 48-byte row, and its five LDS coefficients in one
+// 40-byte row of cL: both loaded at the slot's start and waited for once, ahead of the cf*f
+// products, so that no scalar load stands among the slot's LDS reads (scalar loads return out
+// of order: a wait for one would drain the LDS reads with it). (The five folded into SlotRow, for
+// the flat builds' prefetch to carry them, did not reproduce the results bit for bit: DESIGN §6.)
 struct alignas(16) SlotRow {
   double cf, cA, ct;
-  int lmask;   // bit q: cL[s][q] != 0 -- the LDS slots stage s reads, one contiguous range
+  int lmask;   // bit q: cL[s][q] != 0 -- the LDS slots stage s reads (bit q guards block q of the glue)
   int storeA;  // after the slot: kk -> kA?
   int storeL;  // after the slot: kk -> L[storeL] (-1: no)
   int pad;
@@ -234,7 +236,6 @@ constexpr int BLOCK = 256;
 constexpr int SCAN_WORDS = 4;  // 2-bit codes for up to 64 grid points (interp_points <= 65)
 constexpr int SUNROLL_FLAT = 1;  // the stage slot loop: one RHS site
 constexpr int SUNROLL_GR = 2;  // GR: two RHS sites (A/B: lone GR tail ray -6%; flat: bulk +-0, lone +1%)
-constexpr int QUNROLL = 5;  // = LDS_SLOTS: the slot range fully unrolled (A/B: -0.8% bulk, -3% lone ray)
 constexpr int PRIO_ITERS = 1024;  // attempts from which a ray counts as an outlier (propagate_kernel, s_setprio)
 // Waves per SIMD the integrator is register-budgeted for (1: 512 VGPR+AGPR, 2: 256).
 #ifndef ART_WAVES_PER_SIMD

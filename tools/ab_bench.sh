@@ -2,6 +2,7 @@
 # Interleaved A/B of libart builds on bench.py's host path (the streamed pipeline, 1e7 flat rays):
 # one process per run so each loads its own library; one JSON line per run.
 # Usage: ROUNDS=3 STEPS=10 bash tools/ab_bench.sh OUT.jsonl LIB [LIB ...]   ("base" = the in-tree libart.so)
+set -o pipefail  # (a run that fails ends the script: nothing more is started on the GPU after a fault)
 OUT=$1; shift
 ROUNDS=${ROUNDS:-3}
 STEPS=${STEPS:-10}
