@@ -29,6 +29,23 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
                                                                               unsigned long long* __restrict__ queue,
                                                                               unsigned long long* __restrict__ stats) {
   const KParams P = specialize<GEOM>(P_in);
+  // HEAD: the headline build (the streamed host call's flat Vern6 integrator) keeps fewer wave-uniform
+  // scalars live across the stage slots, where the allocator parks them in lanes of v254/v255 and reads
+  // them back tuple by tuple (DESIGN §3 "Register budget", §6 "Spilled scalars"):
+  //  * its cold blocks (a crossing's record, a finishing lane's stores, the piece counts, the wave's end)
+  //    read `in`, `out`, n and the statistics' address from the kernel-argument segment when they run
+  //    (cold_args, art_ray_io.h);
+  //  * ln_t_end and dtmin are scalar pairs of their own (own_pair) and the step size is one basic block:
+  //    4 lane reads on every path, not 16-24;
+  //  * the sign-code fast paths rebuild their masks from one scalar instead of restoring eight.
+  // 127 -> 85 spill slots, 233 -> 118 lane reads in the main loop outside the slot loop; the host call
+  // 87.1-87.7 -> 85.7-86.2 ms. Every other instantiation compiles to the code it had before: applied to
+  // all builds, the same changes cost the device launch 0.5-0.9 ms and the GR batch 1%. The refill keeps
+  // its arguments in registers: written through references, it changed every build's code.
+  constexpr bool HEAD = DON == 3 && GEOM == GEOM_FLAT && !SAVE && !CYC && INTEG != ART_RK4;
+  constexpr bool COLD = HEAD, OWN = HEAD, FASTN = HEAD;
+  const SegIn& in_k = in;
+  const SegOut& out_k = out;
   constexpr bool RK4 = (INTEG == ART_RK4);
   // the work queue: fresh rays [0, n), or in a continuation launch the donated records
   const bool cont = DON == 1 && out.cont_mode;
@@ -49,7 +66,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
   double* const L = lds + threadIdx.x;
   const int wbase = threadIdx.x & ~63;
   const int lane = threadIdx.x & 63;
-  const double tend = P.ln_t_end;
+  const double tend = OWN ? own_pair(P.ln_t_end) : P.ln_t_end, dtmin = OWN ? own_pair(P.dtmin) : P.dtmin;
   const int npts = P.interp_points;
   for (int j = threadIdx.x; j < npts; j += BLOCK) thgrid[j] = double(j) / double(npts - 1);
   if constexpr (DON == 3) {
@@ -230,9 +247,17 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
     if (mode == M_ROOT) {
       hs = r_t * hroot;
     } else if (mode == M_STEP) {
-      hs = dt;  // (min(dt, dtmax) is implied: the span end clips every step)
-      if (tau + hs >= tend) { hs = tend - tau; last = true; }
-      else if (!RK4 && hs < P.dtmin) { hs = P.dtmin; forced = true; }
+      // (min(dt, dtmax) is implied: the span end clips every step.) OWN: one basic block, selects and no
+      // branches, so each of tend and dtmin is restored from its spill lanes once, whichever case the lane is
+      if constexpr (OWN) {
+        last = tau + dt >= tend;
+        forced = !RK4 && !last && dt < dtmin;
+        hs = last ? tend - tau : (forced ? dtmin : dt);
+      } else {
+        hs = dt;
+        if (tau + hs >= tend) { hs = tend - tau; last = true; }
+        else if (!RK4 && hs < dtmin) { hs = dtmin; forced = true; }
+      }
     }
 
     // ---- stage slots: one RHS per slot per lane ----
@@ -496,12 +521,16 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
         cw[w] = cert ? 0x55555555u * (unsigned)ccode : codes[w * BLOCK + threadIdx.x];
       // fast path: every grid point has the previous sign (or the previous sign is unknown
       // and every point has one common nonzero sign)
+      // (FASTN: nper through an empty asm, so the masks below are rebuilt from this one scalar here and not
+      // hoisted out of the main loop, spilled and restored, two to four lane reads a block)
+      int nper_f = nper;
+      if constexpr (FASTN) asm volatile("" : "+s"(nper_f));
       const unsigned s0 = cw[0] & 3u;
       if (s0 == 1u || s0 == 2u) {
         bool same = (last_s == 0) || (last_s == (s0 == 1u ? 1 : -1));
 #pragma unroll
         for (int w = 0; w < SCAN_WORDS; ++w) {
-          const int nw = nper - 16 * w;
+          const int nw = nper_f - 16 * w;
           if (nw <= 0) break;
           const unsigned m = nw >= 16 ? 0xffffffffu : ((1u << (2 * nw)) - 1u);
           same = same && ((cw[w] & m) == ((s0 * 0x55555555u) & m));
@@ -517,7 +546,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
         bool all = true;
 #pragma unroll
         for (int w = 0; w < SCAN_WORDS; ++w) {
-          const int nw = nper - 16 * w;
+          const int nw = nper_f - 16 * w;
           if (nw <= 0) break;
           const unsigned m = nw >= 16 ? 0xffffffffu : ((1u << (2 * nw)) - 1u);
           all = all && ((cw[w] & m) == m);
@@ -799,7 +828,9 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
     if (root_done || (scan && !hit)) bstart = bend;
     if (root_done) {
       const double tau_r = tau + hs;
-      const int a = affect(P, in, out, n, ray, u, tau_r, erg, ncross, max_crossings);
+      const PropArgs* const A = cold_args_if<COLD>();  // (cold: a crossing is recorded)
+      const int a = affect(P, COLD ? A->in : in_k, COLD ? A->out : out_k, COLD ? A->n : n, ray, u, tau_r, erg, ncross,
+                           COLD ? A->max_crossings : max_crossings);
       tau = tau_r;
       cprev = post_c;  // the post-event side (DiffEq repeat_nudge): the root is not re-found
       cprev_ok = true;
@@ -835,6 +866,8 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
     }
     int fin_piece = -1;  // (DON = 3) the piece of a ray finishing now
     if (finish >= 0) {  // the raw end record; finalize_kernel back-transforms it (RayTracer.jl:393-416)
+      const PropArgs* const A = cold_args_if<COLD>();  // (cold: a ray's end record)
+      const SegOut& out = COLD ? A->out : out_k;
       if constexpr (DON == 3) fin_piece = piece_of(out.pieces, ray);
       double2* rq = reinterpret_cast<double2*>(out.rec + (int64_t)ray * END_REC);
       rq[0] = make_double2(u[0], u[1]);
@@ -857,7 +890,7 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
       if (fin_piece >= 0) atomicAdd(&pend_lds[threadIdx.x >> 6][fin_piece], 1u);
       ++tick;
       if ((tick & STREAM_FLUSH) == 0 || (exhausted && (tick & DRAIN_FLUSH_MASK) == 0))
-        stream_flush(out, pend_lds[threadIdx.x >> 6], lane);
+        stream_flush(COLD ? cold_args_if<COLD>()->out : out_k, pend_lds[threadIdx.x >> 6], lane);
     }
     ART_TMARK(0)  // saveat, reload, events, finish and the output stores (+ refill)
     // graduation (SegOut::graduate): a ray past `graduate` attempts, at a step boundary, leaves
@@ -944,10 +977,12 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
 
   // wave-reduce the statistics and add them once per wave (DON = 3: before the wave counts itself
   // done and flushes its last piece counts, so the helper that ends the call finds them complete)
+  const PropArgs* const Ae = cold_args_if<COLD>();  // (COLD: nothing of this is held across the loop)
+  unsigned long long* const stats_e = COLD ? Ae->stats : stats;
 #if defined(ART_SECTION_TIMING)
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) atomicAdd(&stats[k], t_sec[k]);
+    for (int k = 0; k < 8; ++k) atomicAdd(&stats_e[k], t_sec[k]);
   }
 #else
   const unsigned v[7] = {s_att, s_acc, s_root, s_scan, s_interp, s_rays, s_cert};
@@ -956,11 +991,12 @@ __global__ __launch_bounds__(BLOCK, WPS) void propagate_kernel(const KParams P_i
   for (int k = 0; k < 7; ++k) {
     unsigned long long x = v[k];
     for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    if (lane == 0 && x) atomicAdd(&stats[slot[k]], x);
+    if (lane == 0 && x) atomicAdd(&stats_e[slot[k]], x);
   }
 #endif
-  span_stamp(stats, true);
+  span_stamp(stats_e, true);
   if constexpr (DON == 3) {
+    const SegOut& out = COLD ? Ae->out : out_k;
     if (out.waves_done) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       if (lane == 0) __hip_atomic_fetch_add(out.waves_done, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -6,6 +6,46 @@
 
 namespace art {
 
+// propagate_kernel's arguments as the kernel-argument segment holds them: its parameter list in order,
+// each at its natural alignment. The headline build's cold blocks (a crossing's record, a finishing lane's
+// stores, the piece counts, the wave's end) read what they need from there when they run (cold_args)
+// instead of holding the pointers, counts and caps live across the stage slots, where the register
+// allocator parks them in lanes of a VGPR and brings them back tuple by tuple (DESIGN §3 "Register budget").
+struct PropArgs {
+  KParams P;
+  int64_t n;
+  SegIn in;
+  SegOut out;
+  int32_t max_crossings;
+  unsigned long long* queue;
+  unsigned long long* stats;
+};
+static_assert(offsetof(PropArgs, n) == sizeof(KParams) && offsetof(PropArgs, in) == sizeof(KParams) + 8 &&
+                  offsetof(PropArgs, out) == offsetof(PropArgs, in) + sizeof(SegIn) &&
+                  offsetof(PropArgs, max_crossings) == offsetof(PropArgs, out) + sizeof(SegOut) &&
+                  offsetof(PropArgs, queue) == offsetof(PropArgs, max_crossings) + 8,
+              "PropArgs mirrors propagate_kernel's parameter list without padding of its own");
+// The arguments, for one cold block: called at the block's head. The empty volatile asm hands the segment's
+// address back as a value the optimiser knows nothing about, so the block's scalar loads can be neither
+// hoisted out of it nor merged with another block's; they stay loads from the constant address space.
+__device__ __forceinline__ const PropArgs& cold_args() {
+  auto p = (const __attribute__((address_space(4))) PropArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const PropArgs*)p;
+}
+template <bool COLD>
+__device__ __forceinline__ const PropArgs* cold_args_if() {
+  if constexpr (COLD) return &cold_args();
+  else return nullptr;
+}
+// One wave-uniform double as a scalar pair of its own: arguments that arrive in one wide scalar load form
+// one register tuple, and a tuple is spilled and restored whole (8 lane reads for one double).
+__device__ __forceinline__ double own_pair(double x) {
+  double r;
+  asm("s_mov_b64 %0, %1" : "=s"(r) : "s"(x));
+  return r;
+}
+
 // (DON = 3) a wave's LDS histogram of finished rays per piece (lane l: piece l) into the
 // pieces' global counts: the wave's end-record stores released once (agent scope), then one
 // atomic add per piece with a count (the helpers poll piece_cnt)
