@@ -34,6 +34,16 @@ class CyclotronOut(C.Structure):  # include/art.h art_cyclotron_out
     _fields_ = [("tau", C.c_void_p), ("count", C.c_void_p), ("pos", C.c_void_p), ("ln_t", C.c_void_p)]
 
 
+LAUNCH_PATH_DECISIONS = ("launches", "streamed", "small_tail", "bulk", "integrator", "geom", "save", "don", "wps", "cyc",
+                         "bulk_grid", "donate", "cont", "cont_wps", "cont_donate", "tail", "tail_geom", "tail_grid", "hot",
+                         "sorted", "graduate", "hot_at")
+LAUNCH_PATH_COUNTS = ("donated", "donated2", "grad_count", "grad_cap", "hot_count", "hot_cap", "hot_claimed")
+
+
+class LaunchPath(C.Structure):  # include/art.h art_launch_path
+    _fields_ = [(k, C.c_int32) for k in LAUNCH_PATH_DECISIONS] + [(k, C.c_uint64) for k in LAUNCH_PATH_COUNTS]
+
+
 class SkySpec(C.Structure):  # include/art.h art_sky_spec
     _fields_ = [("n_theta", C.c_int32), ("n_phi", C.c_int32), ("n_dw", C.c_int32), ("theta_axis", C.c_int32),
                 ("mode", C.c_int32), ("dw_lo", C.c_double), ("dw_hi", C.c_double)]
@@ -144,6 +154,7 @@ SIGNATURES = {
     "art_shutdown": (C.c_int, []),
     "art_last_kernel_ms": (C.c_double, []),
     "art_last_stats": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
+    "art_last_launch_path": (C.c_int, [C.POINTER(LaunchPath)]),
     "art_vern6_tableau": (C.c_int, [_v, _v, _v, _v]),
     "art_find_conversion_surface": (C.c_double, [_P]),
     "art_propagate_host": (C.c_int, [_P, _i64, _v, _v, _v, _v, _v, _v, _i32, C.POINTER(SegmentOut),

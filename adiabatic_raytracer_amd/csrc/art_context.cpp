@@ -17,6 +17,7 @@ thread_local std::string g_err;
 double g_last_ms = 0.0;
 unsigned long long g_last_stats[art::N_STATS] = {0};
 int g_last_grid = 0;
+art_launch_path g_last_path{};
 std::atomic<uint64_t> g_host_cnt[HC_N] = {};
 // (pointers: a context never moves, so a worker thread may hold one while another device's is created)
 std::vector<std::unique_ptr<DeviceCtx>> g_ctx;
@@ -55,14 +56,14 @@ int current_ctx(DeviceCtx** out) {
   if (c.device < 0) {
     HIP_OK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     unsigned long long* hs = nullptr;
-    HIP_OK(hipHostMalloc((void**)&hs, sizeof(unsigned long long) * art::N_STATS_DEV * RING, hipHostMallocDefault));
+    HIP_OK(hipHostMalloc((void**)&hs, sizeof(unsigned long long) * HOST_WORDS * RING, hipHostMallocDefault));
     for (int i = 0; i < RING; ++i) {
       HIP_OK(hipEventCreate(&c.ring[i].ev0));
       HIP_OK(hipEventCreate(&c.ring[i].ev1));
       HIP_OK(hipEventCreateWithFlags(&c.ring[i].done, hipEventDisableTiming));
       HIP_OK(hipEventCreateWithFlags(&c.ring[i].hot_fork, hipEventDisableTiming));
       HIP_OK(hipEventCreateWithFlags(&c.ring[i].hot_join, hipEventDisableTiming));
-      c.ring[i].host_stats = hs + i * art::N_STATS_DEV;
+      c.ring[i].host_stats = hs + i * HOST_WORDS;
     }
     // per-launch scratch comes from the stream-ordered allocator: keep what it frees cached
     // so a steady stream of launches does not go back to the driver
@@ -334,6 +335,19 @@ int check_segment_args(const art_params* p, int64_t n, const double* x0, const d
   return ART_OK;
 }
 
+// A launch's record with its counts: the record words the launch copied back beside its statistics
+// (the streamed call's integrator has none)
+static art_launch_path path_with_counts(const LaunchRec& L) {
+  art_launch_path r = L.path;
+  if (r.streamed) return r;
+  r.donated = L.host_stats[HS_DONATED];
+  r.donated2 = L.host_stats[HS_DONATED2];
+  r.grad_count = L.host_stats[HS_GRAD_COUNT];
+  r.hot_count = L.host_stats[HS_HOT_COUNT];
+  r.hot_claimed = L.host_stats[HS_HOT_QUEUE];
+  return r;
+}
+
 int finish_timing_slot(DeviceCtx* c, LaunchRec* Lp) {
   std::lock_guard<std::mutex> rlk(g_ring_mu);
   if (!Lp && c->last < 0) return ART_OK;
@@ -344,6 +358,7 @@ int finish_timing_slot(DeviceCtx* c, LaunchRec* Lp) {
   g_last_ms = ms;
   g_last_grid = L.grid;
   for (int i = 0; i < art::N_STATS; ++i) g_last_stats[i] = L.host_stats[i];
+  g_last_path = path_with_counts(L);
   L.held.store(false, std::memory_order_release);
   return ART_OK;
 }
@@ -354,6 +369,7 @@ int finish_timing_sum(DeviceCtx* c, const std::vector<int>& slots) {
   double ms_sum = 0.0;
   unsigned long long st[art::N_STATS] = {0};
   int grid = 0;
+  art_launch_path path{};  // the last launch's decisions, the counts summed (as the statistics are)
   for (int i : slots) {
     LaunchRec& L = c->ring[i];
     HIP_OK(hipEventSynchronize(L.done));
@@ -362,7 +378,19 @@ int finish_timing_sum(DeviceCtx* c, const std::vector<int>& slots) {
     ms_sum += ms;
     for (int k = 0; k < art::N_STATS; ++k) st[k] += L.host_stats[k];
     grid = std::max(grid, L.grid);
+    const art_launch_path one = path_with_counts(L), sum = path;
+    path = one;
+    path.launches = sum.launches + one.launches;
+    path.bulk_grid = std::max(sum.bulk_grid, one.bulk_grid);
+    path.donated += sum.donated;
+    path.donated2 += sum.donated2;
+    path.grad_count += sum.grad_count;
+    path.grad_cap += sum.grad_cap;
+    path.hot_count += sum.hot_count;
+    path.hot_cap += sum.hot_cap;
+    path.hot_claimed += sum.hot_claimed;
   }
+  g_last_path = path;
   g_last_ms = ms_sum;
   g_last_grid = grid;
   for (int k = 0; k < art::N_STATS; ++k) g_last_stats[k] = st[k];
@@ -378,6 +406,7 @@ int latch_launch(DeviceCtx* c, LaunchRec* L, const unsigned long long* st) {
   g_last_ms = ms;
   g_last_grid = L->grid;
   for (int i = 0; i < art::N_STATS; ++i) g_last_stats[i] = st[i];
+  g_last_path = path_with_counts(*L);
   L->held.store(false, std::memory_order_release);
   return ART_OK;
 }
@@ -453,6 +482,12 @@ double art_last_kernel_ms(void) { return g_last_ms; }
 int art_last_stats(uint64_t* stats, int32_t* grid) {
   for (int i = 0; i < art::N_STATS; ++i) stats[i] = g_last_stats[i];
   if (grid) *grid = g_last_grid;
+  return ART_OK;
+}
+
+int art_last_launch_path(art_launch_path* out) {
+  if (!out) return fail(ART_E_INVALID, "out is NULL");
+  *out = g_last_path;
   return ART_OK;
 }
 

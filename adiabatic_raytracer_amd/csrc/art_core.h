@@ -25,6 +25,9 @@
 // scan and the back-transform). The ray equations' right-hand side keeps "fast" contraction
 // (ART_FP_FAST at the top of its functions): it is 2% of the headline kernel's time faster
 // that way, and its roundings were checked equal between the kernels (the ART_TRACE per-attempt build; the trace tools are in git history).
+// That check covered rhs_photon_gj, the flat and Schwarzschild kernels' form. The general rhs_photon rounds
+// differently in the two kernels (equal once built without "fast"), so the general geometry has no tail kernel
+// (art_launch_plan.h, DESIGN.md "Launch paths").
 #if defined(__clang__)
 #define ART_FP_FAST _Pragma("clang fp contract(fast)")
 #else

@@ -10,26 +10,55 @@
 namespace art {
 namespace host {
 
-constexpr size_t HOT_CAP = 1024;  // early-graduation records of one launch (SegOut::hot)
-
-// Tail donation of a launch: the caller's choice, else the device's setting, else (-1, the
-// default) by geometry. A Schwarzschild batch is bound by its few longest rays (configs[3]: ray
-// 717277 takes 23 592 attempts), which a lone pass would run on one lane of a draining wave
-// (13.5 us per attempt); donated, they finish on the one-wave-per-ray tail kernel (7.7 us). A
-// flat lone pass has no such ray, and donation costs its drain 0.5-1.3%.
-static int launch_donate(DeviceCtx* c, const LaunchOpts& o, const art_params* p, const TrajArgs& tr) {
-  if (o.donate >= 0) return o.donate;
-  if (c->donate >= 0) return c->donate;
-  const bool sch = !p->flat && !(p->bndry_lyr > 0.0) && !p->isotropic;
-  return (sch && p->integrator == ART_VERN6 && tr.none()) ? 16 : 0;
+// The environment's share of a launch's plan, read once per launch (tests switch the variables):
+// ART_SMALL_TAIL, ART_TAIL, ART_TAIL_DONATE, ART_W1, ART_GRADUATE, ART_HOT_AT, ART_HOT_ORDER.
+static void plan_env(art::LaunchPlanIn* in) {
+  const char* e = std::getenv("ART_SMALL_TAIL");
+  in->small_tail_set = e && *e;
+  in->small_tail_max = in->small_tail_set ? std::atoll(e) : 0;
+  in->tail_rays = env_int("ART_TAIL", 1);
+  in->tail_donate = std::min(63, std::max(1, env_int("ART_TAIL_DONATE", 4)));
+  e = std::getenv("ART_W1");  // the 1-wave/SIMD builds are on unless ART_W1=0
+  in->w1 = !(e && e[0] == '0');
+  in->graduate_env = env_int("ART_GRADUATE", 2048);
+  in->hot_at_env = env_int("ART_HOT_AT", 128);
+  in->hot_order = env_int("ART_HOT_ORDER", 1) != 0;
 }
 
-// A small Vern6 batch without saveat runs every ray on a wave of its own (tail_kernel): the
+// The inputs of a launch's plan (art_launch_plan.h) but for its stream and its kernel's occupancy.
+// Tail donation by default goes by geometry: a Schwarzschild batch is bound by its few longest rays
+// (configs[3]: ray 717277 takes 23 592 attempts), which a lone pass would run on one lane of a
+// draining wave (13.5 us per attempt); donated, they finish on the one-wave-per-ray tail kernel
+// (7.7 us). A flat lone pass has no such ray, and donation costs its drain 0.5-1.3%.
+static int plan_inputs(DeviceCtx* c, const art_params* p, int64_t n, const TrajArgs& tr, int donate_caller,
+                       art::LaunchPlanIn* in) {
+  in->n = n;
+  in->integrator = p->integrator;
+  in->geom = art::geom_of(kparams(*p));
+  in->save = tr.ntimes >= 2;
+  in->cyc = tr.cyc != nullptr;
+  in->donate_caller = donate_caller;
+  in->donate_device = c->donate;
+  in->graduate_device = c->graduate;
+  HIP_OK(hipDeviceGetAttribute(&in->ncu, hipDeviceAttributeMultiprocessorCount, c->device));
+  plan_env(in);
+  return ART_OK;
+}
+
+// A small Vern6 batch without saveat, in flat space or Schwarzschild, runs every ray on a wave of its own (tail_kernel): the
 // latency of a Julia host's per-event calls (its rays run ~40% faster per attempt than a lone
-// lane of the persistent integrator), bit-identical results. One decision for the launch and
-// for every caller that lays out a launch's scratch ahead of it (the chunked host pipeline).
+// lane of the persistent integrator), bit-identical results. One decision (lp_small_tail) for the
+// launch and for every caller that lays out a launch's scratch ahead of it (the chunked host pipeline).
 bool use_small_tail(const art_params* p, int64_t n, const TrajArgs& tr) {
-  return tr.none() && p->integrator == ART_VERN6 && n <= art::small_tail_limit();
+  art::LaunchPlanIn in;
+  in.n = n;
+  in.integrator = p->integrator;
+  in.geom = art::geom_of(kparams(*p));
+  in.save = tr.ntimes != 0;
+  in.cyc = tr.cyc != nullptr;
+  in.small_tail_set = true;
+  in.small_tail_max = art::small_tail_limit();
+  return art::lp_small_tail(in);
 }
 
 int scratch_layout(DeviceCtx* c, int64_t n, int cap, int32_t donate, ScratchLayout* L, bool small_tail) {
@@ -39,18 +68,13 @@ int scratch_layout(DeviceCtx* c, int64_t n, int cap, int32_t donate, ScratchLayo
   L->xrb = (size_t)cap * nd * art::X_REC * sizeof(double);
   // tail donation: at most (resident waves) x donate records of CONT_REC doubles; a small batch
   // sent to the tail kernel: one record per ray
-  L->ncont = 0;
-  if (small_tail) {
-    L->ncont = nd;
-  } else if (donate > 0) {
-    int ncu = 0;
-    HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
-    L->ncont = std::min(nd, (size_t)ncu * 32 * (size_t)donate);
-  }
+  int ncu = 0;
+  if (!small_tail && donate > 0) HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
+  L->ncont = art::lp_ncont(n, ncu, donate, small_tail);
   // the second level (the packed continuation's own donations, resumed by the tail kernel):
   // never more than the first level's; then as many graduation records (SegOut::grad) and the
   // early-graduation records (SegOut::hot) and their ready words
-  L->nhot = small_tail ? 0 : std::min(L->ncont, (size_t)HOT_CAP);
+  L->nhot = art::lp_nhot(L->ncont, small_tail);
   L->contb = ((small_tail ? 2 : 3) * L->ncont + L->nhot) * art::CONT_REC * sizeof(double) + L->nhot * sizeof(unsigned);
   // (then the claim order's sort, SegOut::order)
   L->ordb = L->nhot ? art::claim_order_bytes(n) + 256 : 0;
@@ -69,8 +93,17 @@ int propagate_device_impl(const art_params* p, int64_t n, const double* x0, cons
   hipStream_t s = (hipStream_t)stream;
   const art::KParams K = kparams(*p);
   const int cap = (xc && xc->count) ? xc->capacity : 0;
-  const bool small_tail = use_small_tail(p, n, tr);
-  const int32_t donate = small_tail ? 0 : launch_donate(c, opt, p, tr);
+  // the launch's plan (art_launch_plan.h): every choice below and in launch_propagate is one of its
+  // fields. (Early graduation only on a non-blocking stream: its side stream is a blocking one, and
+  // work on a blocking stream -- the null stream above all -- would wait for the hot launch, which
+  // waits for this launch's own kernels.)
+  art::LaunchPlanIn pin;
+  if ((rc = plan_inputs(c, p, n, tr, opt.donate, &pin))) return rc;
+  unsigned sflags = 0;
+  pin.nonblocking = s != nullptr && hipStreamGetFlags(s, &sflags) == hipSuccess && (sflags & hipStreamNonBlocking);
+  const art::LaunchPlan plan = art::plan_launch(pin);
+  const bool small_tail = plan.small_tail;
+  const int32_t donate = plan.donate;
   ScratchLayout SL;
   if ((rc = scratch_layout(c, n, cap, donate, &SL, small_tail))) return rc;
   if (opt.scratch && SL.total() > opt.scratch_bytes)
@@ -119,39 +152,35 @@ int propagate_device_impl(const art_params* p, int64_t n, const double* x0, cons
     so.cont2 = so.cont + ncont * art::CONT_REC;
     so.cont2_count = words + 18;
     so.cont2_queue = words + 19;
-    if (!small_tail && tr.none() && p->integrator == ART_VERN6) {
+    if (plan.grad_cap > 0) {
       // graduation of a pass's outlier rays to the tail kernel (ART_GRADUATE attempts, default
       // 2048 -- about 23x the mean GR ray, never reached by a flat one; 0 = off;
-      // profiles/r04av_graduation_threshold.txt)
+      // profiles/r04av_graduation_threshold.txt): the records' place, which launch_propagate hands
+      // to the kernels where the tail kernel runs (plan.grad_records)
       so.grad = so.cont2 + ncont * art::CONT_REC;
       so.grad_count = words + 20;
       so.grad_queue = words + 21;
-      so.grad_cap = (int32_t)std::min(ncont, (size_t)INT32_MAX);
+      so.grad_cap = plan.grad_cap;
       // (the caller's setting, art_set_graduation: a host that keeps several passes in flight turns
       // it off -- each graduated ray then holds a whole tail wave while the other passes fill the
       // CUs it would free, profiles/r04al_graduation_in_flight.txt; round 4 decided this per launch
       // from the other streams' events, which made it depend on host timing)
-      so.graduate = c->graduate >= 0 ? c->graduate : std::max(0, env_int("ART_GRADUATE", 2048));
+      so.graduate = plan.graduate;
       // early graduation (SegOut::hot), with graduation only: from ART_HOT_AT attempts (default
       // 128) a ray whose progress in ln t is below ART_HOT_DTAU + ART_HOT_SLOPE log2(attempts /
       // 256) (defaults 15.95, 0.75): on configs[3] 102 rays, 90 of them past 5000 attempts, among
       // them every one of the 20 longest (tools/exp_gr_predict.py)
-      // (only on a non-blocking stream: the side stream below is a blocking one, and work on a
-      // blocking stream -- the null stream above all -- would wait for the hot launch, which waits
-      // for this launch's own kernels)
-      unsigned sflags = 0;
-      const bool nonblocking = s != nullptr && hipStreamGetFlags(s, &sflags) == hipSuccess && (sflags & hipStreamNonBlocking);
-      if (SL.nhot && so.graduate > 0 && nonblocking) {
+      if (plan.hot_records) {
         so.hot = so.grad + ncont * art::CONT_REC;
         so.hot_ready = (unsigned*)(so.hot + SL.nhot * art::CONT_REC);
         so.hot_count = words + 22;
         so.hot_queue = words + 23;
         so.hot_done = (unsigned*)(words + 26);
-        so.hot_cap = (int32_t)SL.nhot;
-        so.hot_at = std::max(0, env_int("ART_HOT_AT", 128));
+        so.hot_cap = plan.hot_cap;
+        so.hot_at = plan.hot_at;
         so.hot_dtau = env_double("ART_HOT_DTAU", 15.95);
         so.hot_slope = env_double("ART_HOT_SLOPE", 0.75);
-        if (SL.ordb && env_int("ART_HOT_ORDER", 1)) {  // (256-byte aligned)
+        if (plan.sorted) {  // (256-byte aligned)
           const uintptr_t o = (uintptr_t)blk + SL.total() - SL.ordb;
           so.order_tmp = (void*)((o + 255) & ~(uintptr_t)255);
         }
@@ -174,9 +203,15 @@ int propagate_device_impl(const art_params* p, int64_t n, const double* x0, cons
   }
   HIP_OK(hipMemsetAsync(words, 0, head, s));
   if (so.hot_ready) HIP_OK(hipMemsetAsync(so.hot_ready, 0, SL.nhot * sizeof(unsigned), s));
-  HIP_OK(art::launch_propagate(K, n, in, so, max_crossings, words, words + 1, s, &L->grid, L->ev0, L->ev1,
+  art::LaunchPlan ran;  // the plan with its grids from the bulk kernel's occupancy: what was launched
+  HIP_OK(art::launch_propagate(K, n, in, so, max_crossings, words, words + 1, s, pin, &ran, L->ev0, L->ev1,
                                opt.finalize_stream, hot));
-  HIP_OK(hipMemcpyAsync(L->host_stats, words + 1, sizeof(unsigned long long) * art::N_STATS_DEV, hipMemcpyDeviceToHost, s));
+  L->grid = ran.small_tail ? ran.tail_grid : ran.bulk_grid;
+  L->path = art::plan_record(ran, false);
+  L->path.grad_cap = ran.grad_records ? (uint64_t)ran.grad_cap : 0;
+  L->path.hot_cap = ran.hot ? (uint64_t)ran.hot_cap : 0;
+  // (the statistics and, in the same copy, the launch's record words: head words 1 .. HOST_WORDS)
+  HIP_OK(hipMemcpyAsync(L->host_stats, words + 1, sizeof(unsigned long long) * HOST_WORDS, hipMemcpyDeviceToHost, s));
   HIP_OK(hipEventRecord(L->done, s));
   if (!opt.scratch) HIP_OK(hipFreeAsync(blk, s));
   L->stream = s;

@@ -33,6 +33,7 @@
 #include "art_core.h"
 #include "art_internal.h"
 #include "art_host_plan.h"
+#include "art_launch_plan.h"
 
 namespace art {
 namespace host {
@@ -45,6 +46,7 @@ extern thread_local std::string g_err;
 extern double g_last_ms;
 extern unsigned long long g_last_stats[art::N_STATS];
 extern int g_last_grid;
+extern art_launch_path g_last_path;  // (art_last_launch_path: latched with the statistics)
 // What the art_propagate_host* calls ran as (art_host_path_counters): calls, streamed
 // pipeline completions, streamed give-ups (each batch then ran again as one launch), chunked
 // pipeline calls, single-launch calls
@@ -56,11 +58,17 @@ extern std::atomic<uint64_t> g_host_cnt[HC_N];
 // device lets launches on different streams be in flight together; a slot is reused only after
 // its previous launch completed.
 constexpr int RING = 64;
+// The words a device launch copies back: its statistics (head words 1 .. N_STATS_DEV) and, in the
+// same copy, its record words (head words 16 .. 23: the donated, second-level, graduated and hot
+// counts and their queue heads), so host_stats[w - 1] is head word w.
+constexpr int HOST_WORDS = 23;
+enum { HS_DONATED = 15, HS_DONATED2 = 17, HS_GRAD_COUNT = 19, HS_HOT_COUNT = 21, HS_HOT_QUEUE = 22 };
 struct LaunchRec {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
   hipEvent_t hot_fork = nullptr, hot_join = nullptr;  // the hot rays' side launch (art::HotSide)
-  unsigned long long* host_stats = nullptr;  // N_STATS_DEV words (pinned): statistics, then the clock stamps
+  unsigned long long* host_stats = nullptr;  // HOST_WORDS words (pinned): statistics, the clock stamps, the record words
   int grid = 0;
+  art_launch_path path{};  // the launch's plan as a record (plan_record); the counts are filled in when it is latched
   hipStream_t stream = nullptr;
   bool pending = false;
   // an asynchronous host call holds its record from its launch until it latches it at its end

@@ -428,15 +428,16 @@ int StreamCall::launch_main() {
   if (env_int("ART_HOST_INITPASS", 1))  // (dev: 0 leaves the first piece to the helpers)
     HIP_OK(art::launch_helpers(K, n, in, so, iblocks, first, 0, words + HW_STATS, H->m_comp));
   HIP_OK(hipEventRecord(L->ev0, H->m_comp));
-  int grid = 0;
+  art::LaunchPlan ran;
   if (overlap && ticket >= 0) {  // (see prev_resident)
     so.resident_host = H->hsig_dev + HSIG_RESIDENT;
     so.resident_value = (unsigned long long)ticket + 1ull;
     so.waves_total = (int32_t)std::min((n + 255) / 256, (int64_t)iblocks) * 4;
   }
   HIP_OK(art::launch_integrator_streamed(K, n, in, so, max_crossings, words + HW_QUEUE, words + HW_STATS, iblocks, H->m_comp,
-                                         &grid));
-  L->grid = grid;
+                                         &ran));
+  L->grid = ran.bulk_grid;
+  L->path = art::plan_record(ran, true);
   HIP_OK(hipEventRecord(L->ev1, H->m_comp));
   if (final_pass) {
     HIP_OK(art::launch_helpers(K, n, in, so, slots, -1, 0, words + HW_STATS, H->m_comp));

@@ -5,6 +5,7 @@
 
 #include "art_core.h"
 #include "art_halo.h"
+#include "art_launch_plan.h"
 #include "art_pieces.h"
 #include "art_tree_step.h"
 
@@ -188,13 +189,18 @@ size_t claim_order_bytes(int64_t n);
 // continuation, and so the raising of *hot_done, only after this launch has ended.
 constexpr unsigned long long HOT_WAIT_TICKS = 20000000ull;
 constexpr int HOT_BLOCKS = 32;  // the hot rays' tail launch: 32 blocks of 4 waves (one ray a wave)
+// pin: the launch's plan inputs (art_launch_plan.h; the caller laid the scratch out from plan_launch(pin));
+// launch_propagate adds the bulk kernel's occupancy, launches what the plan then names and returns
+// that plan in *ran (may be null). A plan that names a build nobody instantiated is an error.
 hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const SegOut& out, int32_t max_crossings,
-                            unsigned long long* queue, unsigned long long* stats, hipStream_t s, int* grid_out,
-                            hipEvent_t ev0, hipEvent_t ev1, hipStream_t fs = nullptr, const HotSide& hs = HotSide());
-// The streamed host pipeline's integrator (DON = 3) with at most `blocks` persistent blocks.
+                            unsigned long long* queue, unsigned long long* stats, hipStream_t s, const LaunchPlanIn& pin,
+                            LaunchPlan* ran, hipEvent_t ev0, hipEvent_t ev1, hipStream_t fs = nullptr,
+                            const HotSide& hs = HotSide());
+// The streamed host pipeline's integrator (DON = 3) with at most `blocks` persistent blocks
+// (plan_streamed; *ran, may be null: the plan it launched).
 hipError_t launch_integrator_streamed(const KParams& P, int64_t n, const SegIn& in, const SegOut& out,
                                       int32_t max_crossings, unsigned long long* queue, unsigned long long* stats,
-                                      int blocks, hipStream_t s, int* grid_out);
+                                      int blocks, hipStream_t s, LaunchPlan* ran);
 // The maskless streamed pipeline's helper duty (helper_kernel HK_TILES, SegOut::host_ready ...):
 // `blocks` blocks; init_limit >= 0 initialises only (tiles below it), -1 serves to the end;
 // announce counts each block into host_flags[64] as it starts.
@@ -216,6 +222,7 @@ using KFn = void (*)(const KParams, const int64_t, const SegIn, const SegOut, co
                      unsigned long long*);
 using TFn = void (*)(const KParams, const int64_t, const SegIn, const SegOut, const int32_t, const int32_t,
                      unsigned long long*);
+// (the lists: ART_BUILDS_NL, ART_BUILDS_NL_CYC and ART_BUILDS_TAIL of art_launch_plan.h)
 KFn nl_propagate(int integ, int geom, bool save, int don, int wps);
 KFn nl_propagate_cyc(int geom, int don);  // (Vern6 with the cyclotron observation, SegOut::cyc_tau)
 TFn nl_tail(int geom);
@@ -231,7 +238,8 @@ using SHFn = void (*)(const KParams, const double, const uint64_t, const int64_t
 SHFn nl_sample_halo(int wps, bool blocks);
 int helper_waves_per_simd(const KParams& P);
 // The batch size up to which launch_propagate runs every ray on a wave of its own (tail_kernel):
-// ART_SMALL_TAIL, default one ray per SIMD of the device; 0 switches it off.
+// ART_SMALL_TAIL, default one ray per SIMD of the device; 0 switches it off. (Flat space and Schwarzschild:
+// the general geometry has no tail kernel, art_launch_plan.h.)
 int64_t small_tail_limit();
 hipError_t launch_sample(const KParams& P, double maxR, uint64_t seed, int64_t ray_offset, int64_t n, double* x,
                          double* k, double* erg, double* vifty, int32_t* w, int32_t* att, unsigned long long* queue,

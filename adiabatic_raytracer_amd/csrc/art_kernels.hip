@@ -347,8 +347,8 @@ static int cu_count() {
   return ncu;
 }
 
-int persistent_blocks(const void* func, int64_t work, int block, int fallback_per_cu) {
-  const int ncu = cu_count();
+// resident blocks of `func` per CU
+static int resident_blocks_per_cu(const void* func, int block, int fallback_per_cu) {
   int per_cu = 0;
   const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, func, block, 0);
   if (oe != hipSuccess || per_cu < 1) {
@@ -361,6 +361,12 @@ int persistent_blocks(const void* func, int64_t work, int block, int fallback_pe
     (void)hipGetLastError();
     per_cu = blocks_per_cu_from_attributes(func, block, fallback_per_cu);
   }
+  return per_cu;
+}
+
+int persistent_blocks(const void* func, int64_t work, int block, int fallback_per_cu) {
+  const int ncu = cu_count();
+  const int per_cu = resident_blocks_per_cu(func, block, fallback_per_cu);
   const int64_t need = (work + block - 1) / block;
   const int64_t full = (int64_t)ncu * per_cu;
   return (int)(need < full ? need : full);
@@ -374,45 +380,28 @@ int geom_of(const KParams& P) {
   return P.rs_eff == 0.0 ? GEOM_FLAT : (P.rs_eff > 0.0 ? GEOM_GR : GEOM_ANY);
 }
 
-// flat's instantiations live here; every other one comes from art_kernels_nolicm.hip (nl_propagate),
-// where RK4 has the general geometry's builds only
-template <int DON>
-static KFn pick_propagate(bool save, bool rk4, int geom, bool cyc) {
-  const bool flat = geom == GEOM_FLAT;
-  if (cyc)  // the cyclotron observation (Vern6 without saveat: the entry points refuse the rest)
-    return flat ? propagate_kernel<ART_VERN6, GEOM_FLAT, false, DON, ART_WAVES_PER_SIMD, true> : nl_propagate_cyc(geom, DON);
-  if (save && !rk4 && flat) return propagate_kernel<ART_VERN6, GEOM_FLAT, true, DON>;  // (saveat: the saving instantiations)
-  if (!save && flat) return rk4 ? propagate_kernel<ART_RK4, GEOM_FLAT, false, DON> : propagate_kernel<ART_VERN6, GEOM_FLAT, false, DON>;
-  return nl_propagate(rk4 ? ART_RK4 : ART_VERN6, (!rk4 && geom == GEOM_GR) ? GEOM_GR : GEOM_ANY, save, DON, ART_WAVES_PER_SIMD);
+// The propagate_kernel instantiation a plan names (art_launch_plan.h): flat's live here
+// (ART_BUILDS_FLAT); every other one comes from art_kernels_nolicm.hip (nl_propagate,
+// nl_propagate_cyc), where RK4 has the general geometry's builds only. nullptr: nobody instantiated it.
+static KFn kernel_of(const LaunchBuild& b) {
+  if (b.geom == GEOM_FLAT) {
+#define ART_FL(I, G, S, D, W, C) \
+  if (b == LaunchBuild{I, G, S, D, W, C}) return propagate_kernel<I, G, S, D, W, C>;
+    ART_BUILDS_FLAT(ART_FL)
+#undef ART_FL
+    return nullptr;
+  }
+  if (b.cyc) return (b.integrator == ART_VERN6 && !b.save && b.wps == ART_WAVES_PER_SIMD) ? nl_propagate_cyc(b.geom, b.don) : nullptr;
+  return nl_propagate(b.integrator, b.geom, b.save, b.don, b.wps);
 }
+static_assert(GEOM_ANY == LP_GEOM_ANY && GEOM_FLAT == LP_GEOM_FLAT && GEOM_GR == LP_GEOM_GR && ART_WAVES_PER_SIMD == LP_WPS &&
+                  BLOCK == LP_BLOCK && HOT_BLOCKS == LP_HOT_BLOCKS,
+              "art_launch_plan.h plans with the kernels' own constants");
 
 int64_t small_tail_limit() {
   const char* e = std::getenv("ART_SMALL_TAIL");  // read per launch (tests switch it)
   if (e && *e) return std::atoll(e);
   return (int64_t)cu_count() * 4;
-}
-
-// The one-wave-per-ray tail kernel for donated rays: ART_TAIL=0 off, ART_TAIL=k at most k rays
-// (default 1: one per SIMD of the device).
-static int tail_rays() {
-  const char* e = std::getenv("ART_TAIL");  // read per launch (tests switch it)
-  return (e && *e) ? std::atoi(e) : 1;
-}
-
-// lanes a drained wave of the packed continuation hands to the tail kernel (ART_TAIL_DONATE)
-static int tail_donate() {
-  const char* e = std::getenv("ART_TAIL_DONATE");
-  const int v = (e && *e) ? std::atoi(e) : 4;
-  return v < 1 ? 1 : (v > 63 ? 63 : v);
-}
-
-// The 1-wave/SIMD instantiations (small batches, GR continuations) are on unless ART_W1=0.
-static bool w1_builds() {
-  static const bool on = [] {
-    const char* e = std::getenv("ART_W1");
-    return !(e && e[0] == '0');
-  }();
-  return on;
 }
 
 // The claim order (SegOut::order): 32-bit keys of the rays' initial step sizes (positive floats sort
@@ -455,38 +444,49 @@ __global__ void hot_done_kernel(unsigned* w) {
 }
 
 hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const SegOut& out_arg, int32_t max_crossings,
-                            unsigned long long* queue, unsigned long long* stats, hipStream_t s, int* grid_out,
-                            hipEvent_t ev0, hipEvent_t ev1, hipStream_t fs, const HotSide& hs) {
+                            unsigned long long* queue, unsigned long long* stats, hipStream_t s, const LaunchPlanIn& pin_arg,
+                            LaunchPlan* ran, hipEvent_t ev0, hipEvent_t ev1, hipStream_t fs, const HotSide& hs) {
   const int64_t gr = (n + 255) / 256;
   const unsigned g1 = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(pick_helper(P), dim3((unsigned)(gr < 2048 ? gr : 2048)), dim3(256), 0, s, P, n, in, out_arg, (int)HK_INIT,
                      (int64_t)0, n, (int64_t)-1, 0, stats);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int geom = geom_of(P);
-  const bool flat = geom == GEOM_FLAT, sch = geom == GEOM_GR;
-  const bool rk4 = P.integrator == ART_RK4;
+  // The plan (art_launch_plan.h): first for the bulk kernel it names, then again with that kernel's
+  // resident blocks per CU, which size the grids (the choice of kernels does not depend on them).
+  LaunchPlanIn pin = pin_arg;
+  LaunchPlan plan = plan_launch(pin);
+  KFn fn = nullptr, cfn = nullptr;
+  const TFn tfn = (plan.tail || plan.hot) ? nl_tail(plan.tail_geom) : nullptr;
+  if (plan.bulk) {
+    if (!(fn = kernel_of(plan.bulk_build))) return hipErrorInvalidDeviceFunction;
+    pin.blocks_per_cu = resident_blocks_per_cu((const void*)fn, BLOCK, plan.bulk_build.wps == 1 ? 1 : ART_WAVES_PER_SIMD * 4 / (BLOCK / 64));
+    plan = plan_launch(pin);
+    if (plan.cont && !(cfn = kernel_of(plan.cont_build))) return hipErrorInvalidDeviceFunction;
+  }
+  // (the side stream and its events come from the caller: without them no launch graduates early)
+  if ((plan.tail || plan.hot) && !tfn) return hipErrorInvalidDeviceFunction;
+  if (plan.hot && !(out_arg.hot && out_arg.hot_ready && out_arg.hot_done && hs.stream && hs.fork && hs.join && hs.zero_word))
+    return hipErrorInvalidValue;
+  if (ran) *ran = plan;
   // graduation (SegOut::grad) only where the tail kernel runs after the continuation to resume
   // the graduated rays
-  SegOut out = out_arg;
   // (saveat and the cyclotron observation: the persistent integrator and its packed continuation
   // alone -- no tail kernel, graduation, hot side stream or 1-wave build)
-  const bool plain = out.ntimes < 2 && !out.cyc_tau;
-  if (out.small_tail || !(out.donate > 0 && tail_rays() != 0 && !rk4 && plain && out.cont2)) {
+  SegOut out = out_arg;
+  if (!plan.grad_records) {
     out.grad = nullptr;
     out.graduate = 0;
   }
   // early graduation (SegOut::hot): only with graduation, and with the side stream that the hot
   // rays' tail launch runs on beside the bulk pass and the continuation
-  const bool hot = out.graduate > 0 && out.hot && out.hot_ready && out.hot_done && out.hot_at > 0 &&
-                   out.hot_cap > 0 &&
-                   hs.stream && hs.fork && hs.join && hs.zero_word;
+  const bool hot = plan.hot;
   if (!hot) {
     out.hot = nullptr;
     out.hot_at = 0;
   }
   out.order = nullptr;
-  if (hot && out.order_tmp && !out.small_tail && n < INT32_MAX) {
+  if (plan.sorted) {
     // the bulk pass claims the rays smallest initial step first (SegOut::order)
     const OrderLayout L = order_layout(n);
     char* b = (char*)out.order_tmp;
@@ -500,18 +500,15 @@ hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const 
       return e;
     out.order = (const int32_t*)(b + L.ids_out);
   }
-  if (out.small_tail) {  // a small Vern6 batch: every ray on a wave of its own (tail_kernel)
-    const int ncu = cu_count();
+  if (plan.small_tail) {  // a small Vern6 batch: every ray on a wave of its own (tail_kernel)
     SegOut ot = out;
     ot.cont_count = out.cont_count;
     ot.cont_queue = out.cont_queue;
     hipLaunchKernelGGL(pack_fresh_kernel, dim3(g1), dim3(256), 0, s, n, in, ot, stats);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    const int waves = (int)(n < (int64_t)ncu * 4 ? n : (int64_t)ncu * 4);
-    if (grid_out) *grid_out = waves;
+    const int waves = plan.tail_waves;
     if (ev0 && (e = hipEventRecord(ev0, s)) != hipSuccess) return e;
-    const TFn tfn = nl_tail(geom);
-    hipLaunchKernelGGL(tfn, dim3(waves), dim3(64), 0, s, P, n, in, ot, max_crossings, waves, stats);
+    hipLaunchKernelGGL(tfn, dim3(plan.tail_grid), dim3(64), 0, s, P, n, in, ot, max_crossings, waves, stats);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (ev1 && (e = hipEventRecord(ev1, s)) != hipSuccess) return e;
     hipStream_t sf = s;
@@ -523,24 +520,12 @@ hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const 
                        (int64_t)-1, 0, stats);
     return hipGetLastError();
   }
-  KFn fn = out.donate > 0 ? pick_propagate<1>(out.ntimes >= 2, rk4, geom, out.cyc_tau != nullptr)
-                           : pick_propagate<0>(out.ntimes >= 2, rk4, geom, out.cyc_tau != nullptr);
-  // A batch that fits one ray per lane of 1 wave per SIMD runs the 1-wave/SIMD build, which
-  // does not spill: lone GR tail ray -3%, flat -4.5% per attempt, bit-identical
-  // (profiles/r02j_small_batch_w1_ab.txt, tests/test_edges.py). ART_W1=0 switches it off (A/B).
-  bool w1 = false;
-  if (w1_builds() && out.donate <= 0 && plain && !rk4 && (flat || sch)) {
-    if (n <= (int64_t)cu_count() * 4 * 64) {
-      fn = flat ? propagate_kernel<ART_VERN6, GEOM_FLAT, false, 0, 1> : nl_propagate(ART_VERN6, GEOM_GR, false, 0, 1);
-      w1 = true;
-    }
-  }
-  // (the integrator's blocks per CU by design: its waves per SIMD, 4 waves a block)
-  int grid = persistent_blocks((const void*)fn, n, BLOCK, w1 ? 1 : ART_WAVES_PER_SIMD * 4 / (BLOCK / 64));
-  // the hot rays' launch: HOT_BLOCKS blocks of 4 waves, each beside one integrator block on a CU
-  // (one wave of each per SIMD), so the bulk pass gives up that many of its blocks
-  if (hot) grid = grid > 2 * HOT_BLOCKS ? grid - HOT_BLOCKS : grid;
-  if (grid_out) *grid_out = grid;
+  // (the plan's bulk build: a batch that fits one ray per lane of 1 wave per SIMD runs the 1-wave/SIMD
+  // build, which does not spill: lone GR tail ray -3%, flat -4.5% per attempt, bit-identical,
+  // profiles/r02j_small_batch_w1_ab.txt, tests/test_edges.py; ART_W1=0 switches it off. Its grid: the
+  // hot rays' launch is HOT_BLOCKS blocks of 4 waves, each beside one integrator block on a CU, one
+  // wave of each per SIMD, so the bulk pass gives up that many of its blocks)
+  const int grid = plan.bulk_grid;
   if (ev0 && (e = hipEventRecord(ev0, s)) != hipSuccess) return e;
   if (hot) {
     // on the side stream from the bulk pass's start: each wave resumes a hot record as soon as
@@ -554,7 +539,7 @@ hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const 
     oh.hot_at = 0;
     oh.cont_count = hs.zero_word;  // (no drained-wave records: word 0 stays zero, word 1 is its queue)
     oh.cont_queue = hs.zero_word + 1;
-    hipLaunchKernelGGL(nl_tail(geom), dim3(HOT_BLOCKS), dim3(256), 0,
+    hipLaunchKernelGGL(tfn, dim3(HOT_BLOCKS), dim3(256), 0,
                        hs.stream, P, n, in, oh, max_crossings, 4 * HOT_BLOCKS, stats);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = hipEventRecord(hs.join, hs.stream)) != hipSuccess) return e;
@@ -569,39 +554,31 @@ hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const 
   };
   hipLaunchKernelGGL(fn, dim3(grid), dim3(BLOCK), 0, s, P, n, in, out, max_crossings, queue, stats);
   if ((e = hipGetLastError()) != hipSuccess) return hot_done(e);
-  if (out.donate > 0) {  // the donated tail rays, packed into full waves (at most waves x donate of them)
+  if (plan.cont) {  // the donated tail rays, packed into full waves (at most waves x donate of them)
     // with the tail kernel (ART_TAIL != 0, Vern6 without saveat) the packed continuation donates
     // in its turn: its drained waves' last rays (at most ART_TAIL_DONATE each, default 4) go to
     // the second-level records, and tail_kernel resumes each of those on a wave of its own
-    const bool tail = tail_rays() != 0 && !rk4 && plain && out.cont2;
     SegOut oc = out;  // (the continuation sends its lagging rays to the hot records too)
     oc.cont_mode = 1;
     oc.cont_src = out.cont;
     oc.cont_src_count = out.cont_count;
-    oc.donate = tail ? tail_donate() : 0;
+    oc.donate = plan.cont_donate;
     oc.cont = out.cont2;
     oc.cont_count = out.cont2_count;
-    const int64_t maxc = (int64_t)grid * (BLOCK / 64) * out.donate;
-    const int cgrid = (int)((maxc + BLOCK - 1) / BLOCK);
     // GR continuations at 1 wave/SIMD: no spills (68 VGPRs spill to scratch at 2). A/B on the
     // configs[3] bench line: 3.21e8 -> 3.35e8 ray-steps/s, bit-identical
     // (profiles/r02h_continuation_w1_ab.txt); flat stays at 2 (measured -3.5% at 1).
-    const KFn cfn = (w1_builds() && sch && !rk4 && plain) ? nl_propagate(ART_VERN6, GEOM_GR, false, 1, 1) : fn;
-    hipLaunchKernelGGL(cfn, dim3(cgrid), dim3(BLOCK), 0, s, P, n, in, oc, max_crossings, queue, stats);
+    hipLaunchKernelGGL(cfn, dim3(plan.cont_grid), dim3(BLOCK), 0, s, P, n, in, oc, max_crossings, queue, stats);
     if ((e = hipGetLastError()) != hipSuccess) return hot_done(e);
     if ((e = hot_done(hipSuccess)) != hipSuccess) return e;
-    if (tail) {
+    if (plan.tail) {
       // one wave per ray, at most one per SIMD of the device (ART_TAIL=k: k waves); more
       // second-level rays queue behind them
-      const int64_t maxc2 = (int64_t)cgrid * (BLOCK / 64) * oc.donate + (out.grad ? (int64_t)out.grad_cap : 0);
-      const int waves = tail_rays() == 1 ? cu_count() * 4 : tail_rays();
-      const int tgrid = (int)(maxc2 < waves ? maxc2 : waves);
       SegOut ot = out;
       ot.cont = out.cont2;
       ot.cont_count = out.cont2_count;
       ot.cont_queue = out.cont2_queue;
-      const TFn tfn = nl_tail(geom);
-      if (tgrid > 0) hipLaunchKernelGGL(tfn, dim3(tgrid), dim3(64), 0, s, P, n, in, ot, max_crossings, waves, stats);
+      hipLaunchKernelGGL(tfn, dim3(plan.tail_grid), dim3(64), 0, s, P, n, in, ot, max_crossings, plan.tail_waves, stats);
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
   } else if ((e = hot_done(hipSuccess)) != hipSuccess) {
@@ -624,13 +601,12 @@ hipError_t launch_propagate(const KParams& P, int64_t n, const SegIn& in, const 
 // finalize kernels of the pieces).
 hipError_t launch_integrator_streamed(const KParams& P, int64_t n, const SegIn& in, const SegOut& out,
                                       int32_t max_crossings, unsigned long long* queue, unsigned long long* stats,
-                                      int blocks, hipStream_t s, int* grid_out) {
-  const int geom = geom_of(P);
-  const KFn fn = geom == GEOM_FLAT ? propagate_kernel<ART_VERN6, GEOM_FLAT, false, 3>
-                                   : nl_propagate(ART_VERN6, geom, false, 3, ART_WAVES_PER_SIMD);
-  const int64_t need = (n + BLOCK - 1) / BLOCK;
-  const int grid = (int)(need < (int64_t)blocks ? need : (int64_t)blocks);
-  if (grid_out) *grid_out = grid;
+                                      int blocks, hipStream_t s, LaunchPlan* ran) {
+  const LaunchPlan plan = plan_streamed(n, geom_of(P), blocks);
+  const KFn fn = kernel_of(plan.bulk_build);
+  if (!fn) return hipErrorInvalidDeviceFunction;
+  const int grid = plan.bulk_grid;
+  if (ran) *ran = plan;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(BLOCK), 0, s, P, n, in, out, max_crossings, queue, stats);
   return hipGetLastError();
 }

@@ -56,27 +56,30 @@ int helper_waves_per_simd(const KParams& P) {
 // -> 226), bit-identical (profiles/r06q_gr_licm.jsonl); the flat integrator stays in art_kernels.hip,
 // 3% faster with the pass (profiles/r06o_ab_device_licm_off_everywhere.jsonl).
 KFn nl_propagate(int integ, int geom, bool save, int don, int wps) {
-#define ART_NL(I, G, S, D, W) \
-  if (integ == I && geom == G && save == S && don == D && wps == W) return propagate_kernel<I, G, S, D, W>;
-  ART_NL(ART_VERN6, GEOM_GR, true, 0, 2) ART_NL(ART_VERN6, GEOM_GR, true, 1, 2)
-  ART_NL(ART_VERN6, GEOM_ANY, true, 0, 2) ART_NL(ART_VERN6, GEOM_ANY, true, 1, 2)
-  ART_NL(ART_RK4, GEOM_ANY, true, 0, 2) ART_NL(ART_RK4, GEOM_ANY, true, 1, 2)
-  ART_NL(ART_RK4, GEOM_ANY, false, 0, 2) ART_NL(ART_RK4, GEOM_ANY, false, 1, 2)
-  ART_NL(ART_VERN6, GEOM_GR, false, 0, 2) ART_NL(ART_VERN6, GEOM_GR, false, 1, 2) ART_NL(ART_VERN6, GEOM_GR, false, 3, 2)
-  ART_NL(ART_VERN6, GEOM_ANY, false, 0, 2) ART_NL(ART_VERN6, GEOM_ANY, false, 1, 2) ART_NL(ART_VERN6, GEOM_ANY, false, 3, 2)
-  ART_NL(ART_VERN6, GEOM_GR, false, 0, 1) ART_NL(ART_VERN6, GEOM_GR, false, 1, 1)
+#define ART_NL(I, G, S, D, W, C) \
+  if (integ == I && geom == G && save == S && don == D && wps == W) return propagate_kernel<I, G, S, D, W, C>;
+  ART_BUILDS_NL(ART_NL)  // (the list: art_launch_plan.h)
 #undef ART_NL
   return nullptr;
 }
 // (the cyclotron-observing Vern6 integrators, SegOut::cyc_tau: GR and the general geometry)
 KFn nl_propagate_cyc(int geom, int don) {
-  if (geom == GEOM_GR)
-    return don ? propagate_kernel<ART_VERN6, GEOM_GR, false, 1, ART_WAVES_PER_SIMD, true>
-               : propagate_kernel<ART_VERN6, GEOM_GR, false, 0, ART_WAVES_PER_SIMD, true>;
-  return don ? propagate_kernel<ART_VERN6, GEOM_ANY, false, 1, ART_WAVES_PER_SIMD, true>
-             : propagate_kernel<ART_VERN6, GEOM_ANY, false, 0, ART_WAVES_PER_SIMD, true>;
+#define ART_NL(I, G, S, D, W, C) \
+  if (geom == G && don == D) return propagate_kernel<I, G, S, D, W, C>;
+  ART_BUILDS_NL_CYC(ART_NL)
+#undef ART_NL
+  return nullptr;
 }
-TFn nl_tail(int geom) { return geom == GEOM_FLAT ? tail_kernel<GEOM_FLAT> : (geom == GEOM_GR ? tail_kernel<GEOM_GR> : tail_kernel<GEOM_ANY>); }
+TFn nl_tail(int geom) {
+#define ART_NL(G) \
+  if (geom == G) return tail_kernel<G>;
+  ART_BUILDS_TAIL(ART_NL)
+#undef ART_NL
+  return nullptr;
+}
+static_assert(GEOM_ANY == LP_GEOM_ANY && GEOM_FLAT == LP_GEOM_FLAT && GEOM_GR == LP_GEOM_GR && ART_WAVES_PER_SIMD == LP_WPS &&
+                  BLOCK == LP_BLOCK && HOT_BLOCKS == LP_HOT_BLOCKS,
+              "art_launch_plan.h plans with the kernels' own constants");
 
 // the sampler's builds, compiled here without MachineLICM (art_kernels_nolicm.hip)
 SFn nl_sample(int wps, bool blocks) {

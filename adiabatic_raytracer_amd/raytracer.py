@@ -326,6 +326,27 @@ def last_stats() -> dict:
     return d
 
 
+GEOM_NAMES = {0: "ANY", 1: "FLAT", 2: "GR"}  # include/art.h ART_GEOM_*
+
+
+def last_launch_path() -> dict:
+    """Which kernels the last propagate launch ran (art_last_launch_path; latched with last_stats):
+    the launch plan's decisions -- small_tail, the bulk integrator's template arguments (integrator,
+    geom, save, don, wps, cyc) and grid, the packed continuation, the tail kernel, the hot side launch,
+    the sorted claim order, the effective graduate and hot_at thresholds -- and the launch's counts
+    (donated, donated2, grad_count / grad_cap, hot_count / hot_cap / hot_claimed). Integers as in
+    include/art.h, flags as bools; geom and tail_geom as "FLAT" / "GR" / "ANY", integrator as
+    "vern6" / "rk4"."""
+    r = _lib.LaunchPath()
+    check(_lib.load().art_last_launch_path(C.byref(r)))
+    d = {k: int(getattr(r, k)) for k in _lib.LAUNCH_PATH_DECISIONS + _lib.LAUNCH_PATH_COUNTS}
+    for k in ("streamed", "small_tail", "bulk", "save", "cyc", "cont", "tail", "hot", "sorted"):
+        d[k] = bool(d[k])
+    d["geom"], d["tail_geom"] = GEOM_NAMES[d["geom"]], GEOM_NAMES[d["tail_geom"]]
+    d["integrator"] = {ART_VERN6: "vern6", ART_RK4: "rk4"}[d["integrator"]]
+    return d
+
+
 HOST_PATH_KEYS = ("calls", "streamed", "stream_giveups", "chunked", "single")
 
 

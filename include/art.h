@@ -160,6 +160,53 @@ double art_last_kernel_ms(void);
  * scan condition evals, interpolant-root condition evals, rays, init RHS evals, 0] and the
  * persistent grid size; they feed the roofline accounting of bench.py. */
 int art_last_stats(uint64_t* stats, int32_t* grid);
+
+/* the geometry an integrator or tail kernel is built for */
+#define ART_GEOM_ANY 0  /* the general one: boundary layer, isotropic plasma, RK4 outside flat space */
+#define ART_GEOM_FLAT 1 /* flat space, anisotropic plasma, no boundary layer                       */
+#define ART_GEOM_GR 2   /* Schwarzschild, anisotropic plasma, no boundary layer                    */
+
+/* Which kernels the last propagate launch ran (latched with art_last_stats: after
+ * art_synchronize or a host entry point). The decisions are the launch plan's own values, the
+ * ones the kernels were selected by; the counts are the launch's record words, read back with its
+ * statistics. A host call made of several launches (the chunked pipeline) reports what
+ * art_last_stats reports for it: one record for the call, `launches` its number of launches, the
+ * counts summed over them, bulk_grid the largest, every other decision the last launch's. The
+ * streamed host call reports streamed = 1, don = 3 and zero counts. */
+typedef struct art_launch_path {
+  /* decisions */
+  int32_t launches;    /* launches this record covers                                          */
+  int32_t streamed;    /* 1: the streamed host call's integrator                              */
+  int32_t small_tail;  /* 1: every ray on a wave of its own, tail_kernel alone (no bulk pass)  */
+  int32_t bulk;        /* 1: the persistent integrator (propagate_kernel) ran ...              */
+  int32_t integrator;  /* ... its template arguments: ART_VERN6 / ART_RK4,                     */
+  int32_t geom;        /*     ART_GEOM_* (small_tail: the tail kernel's),                      */
+  int32_t save;        /*     saveat,                                                          */
+  int32_t don;         /*     DON: 0 none, 1 donating, 3 streamed,                             */
+  int32_t wps;         /*     waves per SIMD,                                                  */
+  int32_t cyc;         /*     the cyclotron observation                                        */
+  int32_t bulk_grid;   /* ... and its grid                                                     */
+  int32_t donate;      /* first-level donation lanes of the launch                             */
+  int32_t cont;        /* 1: the packed continuation ran; its waves per SIMD and the lanes     */
+  int32_t cont_wps;    /*    its drained waves hand to the tail kernel (0: no second level)    */
+  int32_t cont_donate;
+  int32_t tail;        /* 1: tail_kernel ran; its geometry and grid                            */
+  int32_t tail_geom;
+  int32_t tail_grid;
+  int32_t hot;         /* 1: the early-graduation side launch ran                              */
+  int32_t sorted;      /* 1: the bulk pass claimed its rays in sorted order                    */
+  int32_t graduate;    /* the effective graduate threshold [attempts], 0: no graduation        */
+  int32_t hot_at;      /* the effective early-graduation threshold [attempts], 0: off          */
+  /* counts */
+  uint64_t donated;     /* first-level donated records (small_tail: the batch's rays)          */
+  uint64_t donated2;    /* second-level donated records                                        */
+  uint64_t grad_count;  /* rays that asked to graduate (may pass grad_cap: the rest stayed)     */
+  uint64_t grad_cap;
+  uint64_t hot_count;   /* rays that asked for a hot record (may pass hot_cap)                 */
+  uint64_t hot_cap;
+  uint64_t hot_claimed; /* hot records claimed by the side launch and the tail kernel          */
+} art_launch_path;
+int art_last_launch_path(art_launch_path* out);
 /* Integrator-kernel durations [ms] of the last min(n, 64) propagate launches on the current
  * device, oldest first, each from the HIP events around that launch on its own stream (waits
  * for them). Returns the number written (>= 0) or a negative ART_E* code. */

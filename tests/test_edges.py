@@ -26,6 +26,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import launch_path
 from conftest import CONFIGS
 
 
@@ -123,6 +124,7 @@ def test_ray_result_independent_of_batch(cfg, oracle_lib, monkeypatch):
 
     monkeypatch.setenv("ART_SMALL_TAIL", "0")
     full, _ = run(np.arange(n))
+    launch_path.persistent(launch_path.last(), (cfg, "reference"), geom="FLAT" if cfg == "flat" else "GR")
     monkeypatch.delenv("ART_SMALL_TAIL")
     ref = _rows(full, np.arange(n), n)
     perm = np.random.default_rng(7).permutation(n)
@@ -132,6 +134,7 @@ def test_ray_result_independent_of_batch(cfg, oracle_lib, monkeypatch):
     assert empty.any() and np.all(np.isnan(ref["xc_pos"][:, empty])) and np.all(np.isnan(ref["xc_p"][:, empty]))
     for idx in batches:
         r, m = run(idx)
+        launch_path.small_tail(launch_path.last(), (cfg, m), m)
         got = _rows(r, np.arange(m), m)
         for key in KEYS:
             want = ref[key][:, idx]
@@ -161,22 +164,40 @@ def test_crossing_buffer_overflow_reports_count(oracle_lib):
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", ["flat", "gr"])
 def test_small_batch_build_matches_large_batch_build(cfg):
-    """Rays of a 70000-ray batch against the same rays as a batch of 2000: bit-identical per ray
-    (the second runs the 1-wave/SIMD build)."""
+    """Rays of a 70000-ray batch against the same rays as a batch of 2000: bit-identical per ray.
+    Without donation (flat's default; GR with art_set_tail_donation(0)) the first runs the 2-wave/SIMD
+    DON = 0 build and the second the 1-wave/SIMD one. By default a GR batch donates 16 lanes, and
+    both sizes then run the 2-wave/SIMD DON = 1 build with its 1-wave/SIMD continuation, the tail
+    kernel and the hot side launch; the larger one gives 32 of its 274 blocks to the hot launch."""
     import adiabatic_raytracer_amd as A
     p = A.Params(**CONFIGS[cfg])
+    lib = A._lib.load()
     n, m = 70000, 2000
     s = A.sample_conversion_points(p, n, seed=1769)
     x, k, e = s["x"].reshape(3, n), s["k_init"].reshape(3, n), s["erg"]
+    G = "FLAT" if cfg == "flat" else "GR"
 
-    def run(idx):
+    def run(idx, want, **fields):
         c = len(idx)
-        return A.propagate_batch(p, x[:, idx].ravel(), k[:, idx].ravel(), e[idx], -np.ones(c), np.full(c, -30.0),
-                                 np.ones(c, np.int8), max_crossings=-1, capacity=1)
-    big = _rows(run(np.arange(n)), np.arange(m), n)
-    small = _rows(run(np.arange(m)), np.arange(m), m)
-    for key in KEYS:
-        assert np.array_equal(small[key], big[key], equal_nan=True), (cfg, key)
+        r = A.propagate_batch(p, x[:, idx].ravel(), k[:, idx].ravel(), e[idx], -np.ones(c), np.full(c, -30.0),
+                              np.ones(c, np.int8), max_crossings=-1, capacity=1)
+        launch_path.persistent(launch_path.last(), (cfg, c), build_is=want, **fields)
+        return r
+    for lanes in ([-1] if cfg == "flat" else [-1, 0]):
+        A._lib.check(lib.art_set_tail_donation(lanes))
+        try:
+            if cfg == "gr" and lanes == -1:
+                on = dict(donate=16, cont=True, cont_wps=1, tail=True, hot=True)
+                big = run(np.arange(n), ("vern6", G, False, 1, 2, False), bulk_grid=274 - 32, **on)
+                small = run(np.arange(m), ("vern6", G, False, 1, 2, False), bulk_grid=8, **on)
+            else:
+                big = run(np.arange(n), ("vern6", G, False, 0, 2, False), bulk_grid=274, cont=False, tail=False)
+                small = run(np.arange(m), ("vern6", G, False, 0, 1, False), bulk_grid=8, cont=False, tail=False)
+        finally:
+            A._lib.check(lib.art_set_tail_donation(-1))
+        big, small = _rows(big, np.arange(m), n), _rows(small, np.arange(m), m)
+        for key in KEYS:
+            assert np.array_equal(small[key], big[key], equal_nan=True), (cfg, lanes, key)
 
 
 @pytest.mark.gpu
@@ -213,7 +234,9 @@ for species in (1, 0):
     q, k, mc = (p, s["k_init"], -1) if species == 1 else (replace(p, B0=-p.B0), -s["k_init"], 100000)
     r = A.propagate_batch(q, s["x"], k, s["erg"], -np.ones(n), np.full(n, -30.0), np.full(n, species, np.int8),
                           max_crossings=mc, capacity=8)
-    out[species] = [int(r["n_accept"].sum()), int(r["n_cross"].sum()), r["stats"]["grid"]]
+    path = A.raytracer.last_launch_path()
+    out[species] = [int(r["n_accept"].sum()), int(r["n_cross"].sum()), r["stats"]["grid"],
+                    [path["small_tail"], path["bulk"], path["geom"], path["don"], path["wps"], path["bulk_grid"]]]
 print(json.dumps(out))
 """
 
@@ -231,8 +254,9 @@ def test_small_batch_w1_first_launch_in_fresh_process():
     r = subprocess.run([sys.executable, "-c", _FRESH, root], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
-    for species, (acc, ncross, grid) in out.items():
+    for species, (acc, ncross, grid, path) in out.items():
         assert acc > 0 and grid == 8, (species, acc, ncross, grid)  # 2000 rays: 8 blocks of 256
+        assert path == [False, True, "FLAT", 0, 1, 8], (species, path)  # ... of the 1-wave/SIMD DON = 0 build
 
 
 @pytest.mark.gpu
@@ -419,8 +443,12 @@ def test_small_batch_tail_mode_is_bit_exact(cfg, species, cap, monkeypatch):
     args = (s["x"], k, s["erg"], -np.ones(n), np.full(n, -30.0), np.full(n, species, np.int8))
     monkeypatch.setenv("ART_SMALL_TAIL", "0")
     ref = A.propagate_batch(q, *args, max_crossings=mc, capacity=cap)
+    # (the persistent integrator: flat's 1-wave/SIMD build, GR's donating one with its continuation and the tail kernel)
+    launch_path.persistent(launch_path.last(), (cfg, "persistent"), geom="FLAT" if cfg == "flat" else "GR",
+                           don=0 if cfg == "flat" else 1, wps=1 if cfg == "flat" else 2, tail=cfg != "flat")
     monkeypatch.setenv("ART_SMALL_TAIL", "1024")
     got = A.propagate_batch(q, *args, max_crossings=mc, capacity=cap)
+    launch_path.small_tail(launch_path.last(), (cfg, "tail"), n)
     for key, v in ref.items():
         if isinstance(v, np.ndarray):
             assert np.array_equal(v, got[key], equal_nan=True), (cfg, key)

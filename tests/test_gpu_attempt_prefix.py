@@ -17,6 +17,7 @@ default path is one of the copies held to it."""
 import numpy as np
 import pytest
 
+import launch_path
 from conftest import CONFIGS
 from test_attempt_prefix import (FORCED_OVER_ERROR, INTS, POISON_AT, PREFIX_CASES, SLOTS, STATE, WINDOW, attempts, case,
                                  check_m_values, check_poisoned, check_prefix, check_rk4, check_window, m_values,
@@ -79,20 +80,39 @@ def _device(c, lanes, x=None, k0=None, erg=None, ln_t0=-30.0, **numerics):
     return got
 
 
+def _is_the_copy(copy, c, capped):
+    """The last launch ran the copy of the kernel that COPIES names (raytracer.last_launch_path); without a cap
+    on the attempts, rays went the copy's way."""
+    rec = launch_path.last()
+    if copy == "small_tail":
+        launch_path.small_tail(rec, copy, c["n"])
+    elif copy == "graduate":
+        launch_path.persistent(rec, copy, don=1, cont=True, tail=True, graduate=1)
+        assert capped or rec["grad_count"] > 0, rec
+    else:
+        launch_path.persistent(rec, copy, don=1, cont=True, tail=True, hot=True, hot_at=16)
+        assert capped or rec["hot_count"] > 0, rec
+        assert rec["hot_claimed"] == min(rec["hot_count"], rec["hot_cap"]), rec
+
+
 def _copy(copy, c, monkeypatch, **kw):
     env, lanes = COPIES[copy]
     with monkeypatch.context() as mp:
         mp.delenv("ART_SMALL_TAIL", raising=False)
         for k, v in env.items():
             mp.setenv(k, v)
-        return _host(c, **kw) if lanes is None else _device(c, lanes, **kw)
+        got = _host(c, **kw) if lanes is None else _device(c, lanes, **kw)
+        _is_the_copy(copy, c, "maxiters" in kw)
+        return got
 
 
 def _bulk(c, monkeypatch, **kw):
     """The persistent integrator: this module's reference launch."""
     with monkeypatch.context() as mp:
         mp.setenv("ART_SMALL_TAIL", "0")
-        return _host(c, **kw)
+        got = _host(c, **kw)
+        launch_path.persistent(launch_path.last(), "the reference launch")
+        return got
 
 
 def _same(ref, got, n, cap, what):

@@ -24,6 +24,7 @@ compiler-version FMA differences and the h⁴ error of the root on the step's cu
 import numpy as np
 import pytest
 
+import launch_path
 from conftest import CONFIGS
 from test_cyclotron import CASES, POINT_SETS, load, random_points
 
@@ -100,6 +101,8 @@ def truth_errors(case, mode):
     p = A.Params(**NUMERICS[mode], **z["params"])
     g = A.propagate_batch(p, z["x0"], z["k0"], z["erg"], -np.ones(n), np.full(n, -30.0), np.ones(n, np.int8),
                           max_crossings=-1, cyclotron=True)
+    geom = "FLAT" if p.flat else "GR"
+    launch_path.persistent(launch_path.last(), (case, mode), build_is=("vern6", geom, False, 0, 2, True), cont=False, tail=False)
     bad = int(np.sum(g["cyc_count"] != z["count"]))
     one = (z["count"] == 1) & (g["cyc_count"] == 1)
     none = g["cyc_count"] == 0

@@ -26,6 +26,7 @@ import os
 import numpy as np
 import pytest
 
+import launch_path
 from conftest import CONFIGS
 
 pytestmark = pytest.mark.gpu
@@ -135,6 +136,10 @@ def _compare(g, o, o2, n):
 def test_vern6_photon_forward_roots(cfg, oracle_lib):
     n = 512
     g, o, o2 = _run(CONFIGS[cfg], n, oracle_lib=oracle_lib)
+    # Batches of at most one ray per SIMD (1024 on the MI355X) run on the tail kernel, so this module's Vern6
+    # cases hold tail_kernel to the oracle; tests/test_gpu_launch_paths.py holds the persistent integrator's
+    # builds to it. (The oracle's runs launch nothing: the record is still the GPU run's.)
+    launch_path.small_tail(launch_path.last(), cfg, n)
     _compare(g, o, o2, n)
 
 
@@ -165,6 +170,7 @@ def test_rk4_fixed_step(oracle_lib):
     n = 256
     kw = dict(CONFIGS["flat"], n_fixed=3000)
     g, o, o2 = _run(kw, n, integrator="rk4", oracle_lib=oracle_lib)
+    launch_path.persistent(launch_path.last(), "rk4", build_is=("rk4", "FLAT", False, 0, 2, False), cont=False, tail=False)
     _compare(g, o, o2, n)
     assert np.all(g["n_reject"] == 0)
 

@@ -10,6 +10,7 @@ error <= 1e-6 and 95th percentile <= 1e-3."""
 import numpy as np
 import pytest
 
+import launch_path
 from conftest import CONFIGS
 
 pytestmark = pytest.mark.gpu
@@ -52,6 +53,7 @@ def test_interior_points_match_the_oracle(oracle_lib):
     p, s = _sample(A, kw, n)
     g = A.propagate_batch(p, s["x"], s["k_init"], s["erg"], -np.ones(n), np.full(n, -30.0), np.ones(n, np.int8),
                           max_crossings=-1, ntimes=ntimes)
+    launch_path.persistent(launch_path.last(), "saveat", build_is=("vern6", "FLAT", True, 0, 2, False), cont=False, tail=False)
     errs = []
     for k in range(1, ntimes - 1):
         sel = np.flatnonzero(g["traj_n"] > k + 1)

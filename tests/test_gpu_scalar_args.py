@@ -5,14 +5,18 @@ tests/test_gpu_stage_glue.py pins the plain device launches; these are the insta
 values it does not reach, each pinned to what the build of a recorded parent commit gave
 (tests/golden/scalar_args/<case>.npz, written by tests/golden/make_scalar_args_fixture.py on that build):
 
-  streamed     the streamed host call (DON = 3: chunk flags, piece counts, the wave counters), forced the
+  streamed     the streamed host call (flat DON = 3: chunk flags, piece counts, the wave counters), forced the
                way tests/test_gpu_host_pieces.py forces it
-  donate16     a donating launch and its packed continuation (DON = 1, 16 lanes, ART_TAIL=0)
-  gr_graduate  a GR launch with graduation after 64 attempts (DON = 1, the graduation records, tail_kernel)
-  cyclotron    the cyclotron build (CYC)
-  no_callbacks max_crossings = ART_NO_CALLBACKS
-  cap8         crossing capacity 8: axion backtraces that record every crossing
-  mixed        every third segment an axion
+  donate16     a donating launch and its packed continuation (flat DON = 1 at 2 waves/SIMD twice, 16 lanes,
+               ART_TAIL=0)
+  gr_graduate  a GR launch with graduation after 64 attempts (GR DON = 1 at 2 waves/SIMD, its continuation at 1,
+               the graduation records, tail_kernel<GR> after them and, on this non-blocking stream, beside them
+               for the hot records)
+  cyclotron    the cyclotron build (flat CYC, DON = 0)
+  no_callbacks max_crossings = ART_NO_CALLBACKS   } flat DON = 0 at 1 wave/SIMD, as every plain flat batch of at
+  cap8         crossing capacity 8: axion backtraces that record every crossing   } most 65 536 rays
+  mixed        every third segment an axion       }
+(BUILDS below; each case asserts the build its launch reports, raytracer.last_launch_path.)
 
 2,048 rays per case (the stage-glue fixtures' forward roots): 32 chunks over 8 blocks' worth of lanes, so
 every wave refills and claims several chunks; one wave per block slot would exercise neither."""
@@ -23,6 +27,7 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+import launch_path
 from conftest import CONFIGS
 from test_gpu_stage_glue import N, load_inputs
 
@@ -41,6 +46,19 @@ CASES = {
     "cap8": ("flat", {}, dict(backtrace=True, call=dict(max_crossings=100000, capacity=8))),
     "mixed": ("flat", {}, dict(mixed=True)),
 }
+
+# case -> the bulk integrator's build (integrator, geometry, saveat, DON, waves per SIMD, cyclotron) and what else the launch reports
+BUILDS = {
+    "streamed": (("vern6", "FLAT", False, 3, 2, False), dict(streamed=True, cont=False, tail=False)),
+    "donate16": (("vern6", "FLAT", False, 1, 2, False), dict(donate=16, cont=True, cont_wps=2, tail=False, graduate=0)),
+    "gr_graduate": (("vern6", "GR", False, 1, 2, False), dict(donate=16, cont=True, cont_wps=1, tail=True, tail_geom="GR",
+                                                              graduate=64, hot=True, sorted=True)),
+    "cyclotron": (("vern6", "FLAT", False, 0, 2, True), dict(cont=False, tail=False)),
+    "no_callbacks": (("vern6", "FLAT", False, 0, 1, False), dict(cont=False, tail=False)),
+    "cap8": (("vern6", "FLAT", False, 0, 1, False), dict(cont=False, tail=False)),
+    "mixed": (("vern6", "FLAT", False, 0, 1, False), dict(cont=False, tail=False)),
+}
+PATHS = {}  # case -> the record of run_case's launch
 
 
 @contextlib.contextmanager
@@ -99,6 +117,7 @@ def run_case(case):
             res = {k: v.cpu().numpy() for k, v in out.items() if hasattr(v, "cpu")}
     for k in COUNTERS + (("init_rhs",) if how.get("host") else ()):
         res["counter_" + k] = np.array(stats[k], np.int64)
+    PATHS[case] = launch_path.last()
     return res
 
 
@@ -108,6 +127,11 @@ def test_scalar_arguments_are_bit_exact(case):
         ref = {k: z[k] for k in z.files}
     assert len(str(ref.pop("parent_sha"))) == 40
     got = run_case(case)
+    path = launch_path.expect(PATHS[case], case, build_is=BUILDS[case][0], small_tail=False, **BUILDS[case][1])
+    if case == "donate16":
+        assert path["donated"] > 0, path
+    if case == "gr_graduate":
+        assert path["grad_count"] > 0 and path["donated"] > 0, path
     assert sorted(got) == sorted(ref), (case, sorted(got), sorted(ref))
     for k in sorted(ref):
         assert got[k].dtype == ref[k].dtype and got[k].shape == ref[k].shape, (case, k)

@@ -1,19 +1,27 @@
 """The integrator's stage glue (the head of every stage slot: y = u + h (cf f + cA kA + Σ_q cL[q] L_q),
 and the error norm's sum over the parked stages) may be rescheduled -- coefficient loads hoisted, LDS
 reads batched -- but never re-associated: every component keeps cf*f (or fma(cf, f, cA*kA)), then
-+= cL[q]*L_q for ascending q. So every output of every instantiation is pinned bit for bit to what
++= cL[q]*L_q for ascending q. So every output of the instantiations below is pinned bit for bit to what
 the build of a recorded parent commit gave (tests/golden/stage_glue/<case>.npz, written by
 tests/golden/make_stage_glue_fixture.py on that build from the inputs stored beside them).
 
 2,048 rays per case take every slot row of both tables, the q = 1 start of Vern6's last row, both
 RK4 masks, refills (32 chunks over 8 waves' worth of lanes) and crossings. The cases: flat Vern6,
 GR, oblique GR, a boundary layer (GEOM_ANY; up to 4 crossings kept), RK4, and flat saved points
-(ntimes = 5: the SAVE build, whose only entry is the host call propagate_batch)."""
+(ntimes = 5: the SAVE build, whose only entry is the host call propagate_batch).
+
+The builds these launches run (BUILDS; each case asserts what its launch reports, raytracer.last_launch_path):
+flat: the 1-wave/SIMD DON = 0 build (2,048 rays are below the 65,536 of one ray per lane); gr and gr_oblique:
+GR DON = 1 at 2 waves/SIMD (16 lanes by default), its packed continuation at 1 wave/SIMD and tail_kernel<GR>;
+layer: ANY DON = 0; rk4: flat RK4 DON = 0; saveat5: flat SAVE DON = 0. The other builds, the flat 2-wave/SIMD
+DON = 0 one that the benchmark's device-resident launch runs among them, are held to the oracle and to these
+by tests/test_gpu_launch_paths.py."""
 import os
 
 import numpy as np
 import pytest
 
+import launch_path
 from conftest import CONFIGS
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +41,17 @@ CASES = {
     "saveat5": (CONFIGS["flat"], "flat", dict(max_crossings=-1, capacity=1, ntimes=5)),
 }
 INPUT_KEYS = ("x0", "k0", "erg")
+# case -> the bulk integrator's build (integrator, geometry, saveat, DON, waves per SIMD, cyclotron) and what else the launch reports
+_GR = (("vern6", "GR", False, 1, 2, False), dict(donate=16, cont=True, cont_wps=1, tail=True, tail_geom="GR", graduate=2048, hot=False))
+BUILDS = {
+    "flat": (("vern6", "FLAT", False, 0, 1, False), dict(cont=False, tail=False)),
+    "gr": _GR,
+    "gr_oblique": _GR,
+    "layer": (("vern6", "ANY", False, 0, 2, False), dict(cont=False, tail=False)),
+    "rk4": (("rk4", "FLAT", False, 0, 2, False), dict(cont=False, tail=False)),
+    "saveat5": (("vern6", "FLAT", True, 0, 2, False), dict(cont=False, tail=False)),
+}
+PATHS = {}  # case -> the record of run_case's launch
 
 
 def make_inputs(cfg):
@@ -58,12 +77,15 @@ def run_case(case, inp):
     if "ntimes" in call:
         out = A.propagate_batch(p, inp["x0"], inp["k0"], inp["erg"], -np.ones(N), np.full(N, -30.0),
                                 np.ones(N, np.int8), **call)
+        PATHS[case] = launch_path.last()
         return {k: v for k, v in out.items() if isinstance(v, np.ndarray)}
     eng = Engine(p)
     dev = lambda a, dt=torch.float64: torch.as_tensor(a, dtype=dt, device=eng.device)  # noqa: E731
     din = {"x0": dev(inp["x0"]), "k0": dev(inp["k0"]), "erg": dev(inp["erg"]), "dw": dev(-np.ones(N)),
            "ln_t0": dev(np.full(N, -30.0)), "species": dev(np.ones(N, np.int8), torch.int8)}
     out = eng.propagate(din, **call)
+    eng.kernel_ms()  # (latches the launch's record)
+    PATHS[case] = launch_path.last()
     torch.cuda.synchronize()
     return {k: v.cpu().numpy() for k, v in out.items() if hasattr(v, "cpu")}
 
@@ -74,6 +96,8 @@ def test_stage_glue_is_bit_exact(case):
         ref = {k: z[k] for k in z.files}
     assert len(str(ref.pop("parent_sha"))) == 40
     got = run_case(case, load_inputs(CASES[case][1]))
+    path = launch_path.expect(PATHS[case], case, build_is=BUILDS[case][0], small_tail=False, streamed=False, **BUILDS[case][1])
+    assert case not in ("gr", "gr_oblique") or path["donated"] > 0, path
     assert sorted(got) == sorted(ref), (case, sorted(got), sorted(ref))
     if "traj" in ref:  # only a ray's first traj_n saved points are written (include/art.h): the rest is not compared
         for d in (ref, got):

@@ -7,16 +7,18 @@ namespace art {
 int persistent_blocks(const void*, int64_t, int, int) { return 1; }
 size_t claim_order_bytes(int64_t) { return 0; }
 hipError_t launch_propagate(const KParams&, int64_t, const SegIn&, const SegOut&, int32_t, unsigned long long*,
-                            unsigned long long*, hipStream_t, int*, hipEvent_t, hipEvent_t, hipStream_t, const HotSide&) {
+                            unsigned long long*, hipStream_t, const LaunchPlanIn&, LaunchPlan*, hipEvent_t, hipEvent_t,
+                            hipStream_t, const HotSide&) {
   return hipErrorNoDevice;
 }
 hipError_t launch_integrator_streamed(const KParams&, int64_t, const SegIn&, const SegOut&, int32_t, unsigned long long*,
-                                      unsigned long long*, int, hipStream_t, int*) { return hipErrorNoDevice; }
+                                      unsigned long long*, int, hipStream_t, LaunchPlan*) { return hipErrorNoDevice; }
 hipError_t launch_helpers(const KParams&, int64_t, const SegIn&, const SegOut&, int, int64_t, int, unsigned long long*,
                           hipStream_t) {
   return hipErrorNoDevice;
 }
 int64_t small_tail_limit() { return 0; }
+int geom_of(const KParams&) { return 0; }  // (GEOM_ANY: the launch plan's input)
 int helper_waves_per_simd(const KParams&) { return 2; }
 HFn pick_helper(const KParams&) { return nullptr; }
 KFn nl_propagate(int, int, bool, int, int) { return nullptr; }
