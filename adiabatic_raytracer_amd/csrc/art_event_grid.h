@@ -3,9 +3,9 @@
 // one scalar per event and does not depend on g, so the power of final record i of event e at cell (kg, kh) is
 //   pw = reweight_power(W[kg, i], B[kg, e], cyclotron, τ, sln_prob) * R[kh, e],
 // the coupling scan's power times the halo scan's ratio, one multiplication rounded on its own. The records counted
-// are event_replicates_kernel's: a final record inside its own tree's range, its bins and its event's values taken
-// once through event_row(row = nullptr) and np_hist_bin; a record in the range of another tree is skipped and
-// counted. Per cell the call adds pw to the flux table and the two species' totals, with n_groups = R the same per
+// are event_replicates_kernel's, by the rule of art_event_record.h: a final record of its own tree's range, its bin
+// and its event's values taken once; a misplaced record is skipped and counted. Per cell the call adds pw to the
+// flux table and the two species' totals, with n_groups = R the same per
 // group g = (event_offset + tree) mod R (and art_event_replicates_device's groups, 3 per group), and with
 // moment_totals art_event_moments_device's 8 totals per cell, from X_{e,s}(kg, kh) = Σ pw over e's final rows of
 // species s in node order (the sum of the per-record products: the first and the second moments are sums of the
@@ -20,8 +20,8 @@
 // and no two lanes of one instruction share an address.
 //
 // The per-cell arithmetic is written once as __host__ __device__ functions: the kernel below and a host build for
-// the CPU tests (tools/eventgrid.cpp) compile the same source. The kernel needs art_kernels.hip's np_hist_bin,
-// EventLoad and event_row and is compiled only there (ART_EVENT_GRID_KERNELS).
+// the CPU tests (tools/eventgrid.cpp) compile the same source. The kernel takes its records through
+// art_event_record.h and is compiled only in art_kernels.hip (ART_EVENT_KERNELS).
 #pragma once
 #include "art_core.h"
 #include "art_event_moments.h"
@@ -80,12 +80,12 @@ __host__ __device__ inline void grid_cell_event(GridCell& c, double ae) {
 
 }  // namespace art
 
-#ifdef ART_EVENT_GRID_KERNELS
+#ifdef ART_EVENT_KERNELS
 namespace art {
 
 // The lanes of a wave cover 64 consecutive CELLS (blockIdx.y picks which 64), not records: a wave takes slices of
 // GRID_EVENTS_PER_WAVE events (grid-stride over the slices) and walks their trees in node order. The records of a
-// tree are prepared 64 at a time, one lane per record -- the own-range test, event_row, the flux bin, τ -- and then
+// tree are prepared 64 at a time, one lane per record (event_record: no sky bin; final only when it names e), and then
 // the final ones are taken one at a time: bins and base factors are broadcast and wave-uniform, every lane forms
 // its own cell's power and the wave adds it to 512 contiguous bytes of the flux table (and of the group's). The
 // sums that take every record of the chunk -- the totals and the moment sums, 6 per cell -- stay in the lane's
@@ -112,12 +112,8 @@ __global__ __launch_bounds__(256) void event_grid_kernel(const EventRowsArgs a, 
     const int64_t e0 = sl * GRID_EVENTS_PER_WAVE;
     const int64_t e1 = e0 + GRID_EVENTS_PER_WAVE < a.n_events ? e0 + GRID_EVENTS_PER_WAVE : a.n_events;
     for (int64_t e = e0; e < e1; ++e) {
-      int64_t s0 = 0, s1 = 0;  // tree e's range, cut to the records there are
-      if (r.node_start) {
-        s0 = r.node_start[e], s1 = r.node_start[e + 1];
-        s0 = s0 < 0 ? 0 : (s0 > a.n_nodes ? a.n_nodes : s0);
-        s1 = s1 < s0 ? s0 : (s1 > a.n_nodes ? a.n_nodes : s1);
-      }
+      int64_t s0;
+      const int64_t s1 = tree_range(r.node_start, a.n_nodes, e, &s0) + s0;
       const int g = R > 0 ? replicate_group(a.event_offset + e, R) : 0;
       const double Bk = live ? r.B[(int64_t)kg * a.n_events + e] : 0.0;
       const double Rk = live ? r.R[(int64_t)kh * a.n_events + e] : 0.0;
@@ -125,30 +121,12 @@ __global__ __launch_bounds__(256) void event_grid_kernel(const EventRowsArgs a, 
       bool any_axion = false, any_photon = false;
       for (int64_t base = s0; base < s1; base += warpSize) {
         const int64_t i = base + lane;
-        bool fin = false, mis = false;
-        int sp = 0, fb = -1;
-        double tau = 0.0, sln = 0.0;
-        if (i < s1) {
-          const art_tree_node& nd = a.nodes[i];
-          const int64_t t = nd.tree;
-          if (!(t >= 0 && t < a.n_events && r.node_start[t] <= i && i < r.node_start[t + 1])) {
-            mis = r.node_start[0] <= i && i < r.node_start[a.n_events];
-            if (mis && first && R > 0)
-              unsafeAtomicAdd(&r.groups[replicate_group(a.event_offset + t, R) * REP_GRP_COUNT + REP_GRP_MISPLACED], 1.0);
-          } else if (t == e && nd.is_final != 0) {
-            fin = true;
-            const EventLoad E{a, e};
-            if (a.cyc_slot) {
-              const int64_t j = a.cyc_slot[i];
-              if (j >= 0 && j < a.cyc_n) tau = a.cyc_tau[j];
-            }
-            const EventRowBins Bn = event_row(nd, E, a.event_offset, a.mass_a, tau, cyclotron, EVENT_COLS_SHORT,
-                                              (double*)nullptr);
-            sp = Bn.species;
-            sln = E.sln_prob();
-            if (r.nbins > 0) fb = np_hist_bin(Bn.phi, r.nbins);
-          }
-        }
+        const EventRecord rec = i < s1 ? event_record(a, r.node_start, i, r.nbins, false, SkyAxes{}, 0) : EventRecord{};
+        const bool mis = rec.state == RECORD_MISPLACED, fin = rec.state == RECORD_FINAL && rec.e == e;
+        const int sp = rec.species, fb = rec.fb;
+        const double tau = rec.tau, sln = rec.sln;
+        if (mis && first && R > 0)
+          unsafeAtomicAdd(&r.groups[replicate_group(a.event_offset + rec.e, R) * REP_GRP_COUNT + REP_GRP_MISPLACED], 1.0);
         bad += (double)__popcll(__ballot(mis));
         unsigned long long todo = __ballot(fin);
         while (todo) {  // the final records of these 64, in node order
@@ -169,7 +147,7 @@ __global__ __launch_bounds__(256) void event_grid_kernel(const EventRowsArgs a, 
           }
         }
       }
-      const double ae = (double)((a.attempts ? (int64_t)a.attempts[e] - 1 : 0) + photons);
+      const double ae = (double)(event_attempts_m1(a, e) + photons);
       if (live) {
         if (R > 0 && any_axion) unsafeAtomicAdd(&r.totals_rep[grid_totals_rep_at(C, g, 0, cell)], c.xa);
         if (R > 0 && any_photon) unsafeAtomicAdd(&r.totals_rep[grid_totals_rep_at(C, g, 1, cell)], c.xp);
@@ -218,4 +196,4 @@ hipError_t launch_event_grid(const EventRowsArgs& a, const EventGridArgs& r, hip
 }
 
 }  // namespace art
-#endif  // ART_EVENT_GRID_KERNELS
+#endif  // ART_EVENT_KERNELS

@@ -10,9 +10,8 @@
 // column 8 * column 7 times R_h of its event, in the run's own bins.
 //
 // Three kernels: the ratios per event and model, the bins, and the second moments per model (pass A
-// and the group-by are art_event_moments.h's). They need art_kernels.hip's np_hist_bin, sky_bin_of,
-// EventLoad and event_row, and art_event_moments.h's entries, and are compiled only there
-// (ART_EVENT_HALOSCAN_KERNELS).
+// and the group-by are art_event_moments.h's). They take their records through art_event_record.h and
+// are compiled only in art_kernels.hip (ART_EVENT_KERNELS).
 #pragma once
 #include "art_core.h"
 #include "art_event_moments.h"
@@ -25,7 +24,7 @@ enum { HS_TOT_SUM_AXION = 0, HS_TOT_SUM_PHOTON, HS_TOT_RATIO, HS_TOT_RATIO_SQ, H
 
 }  // namespace art
 
-#ifdef ART_EVENT_HALOSCAN_KERNELS
+#ifdef ART_EVENT_KERNELS
 namespace art {
 
 // One lane per event: R[k n_events + e] for every model from the event's three vifty components (SoA,
@@ -45,52 +44,24 @@ __global__ __launch_bounds__(256) void event_halo_ratio_kernel(const int64_t n, 
       R = halo_ratio(u, h.base, h.models[k]);
       h.R[k * n + e] = R;
     }
-    double s1 = R, s2 = R * R;
-    for (int off = warpSize / 2; off > 0; off >>= 1) {
-      s1 += __shfl_down(s1, off);
-      s2 += __shfl_down(s2, off);
-    }
-    if ((threadIdx.x & (warpSize - 1)) == 0 && s1 != 0.0) {
-      unsafeAtomicAdd(&h.totals[k * HS_TOT_COUNT + HS_TOT_RATIO], s1);
-      unsafeAtomicAdd(&h.totals[k * HS_TOT_COUNT + HS_TOT_RATIO_SQ], s2);
-    }
+    wave_add(&h.totals[k * HS_TOT_COUNT + HS_TOT_RATIO], R);
+    wave_add(&h.totals[k * HS_TOT_COUNT + HS_TOT_RATIO_SQ], R * R);
   }
 }
 
-// One lane per node record. A final record in its own tree's range takes its bins and its event's
-// values once, by event_row(row = nullptr), np_hist_bin and sky_bin_of, so it falls into the bins
-// event_rows_kernel puts it in; then per model its power, the run's own p_r = column 8 * column 7
-// (exp(-τ) included with the cyclotron fields) times R of its event, goes to flux[k], sky[k] and the
-// totals. A record inside the forest's range whose `tree` is another tree's is counted (misplaced).
+// One lane per node record. A final record of its own tree's range takes its bins and its event's
+// values once (event_record, art_event_record.h); then per model its power, the run's own p_r =
+// column 8 * column 7 (exp(-τ) included with the cyclotron fields) times R of its event, goes to
+// flux[k], sky[k] and the totals. The misplaced records are counted per model.
 __global__ __launch_bounds__(256) void event_halo_bins_kernel(const EventRowsArgs a, const EventHaloScanArgs h,
                                                               const SkyAxes A, const int cos_axis) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool fin = false;
-  int sp = 0, fb = -1, sb = -1;
-  double pr = 0.0, bad = 0.0;
-  int64_t e = 0;
-  if (i < a.n_nodes) {
-    const art_tree_node& nd = a.nodes[i];
-    e = nd.tree;
-    if (!(e >= 0 && e < a.n_events && h.node_start[e] <= i && i < h.node_start[e + 1])) {
-      if (h.node_start[0] <= i && i < h.node_start[a.n_events]) bad = 1.0;
-    } else if (nd.is_final != 0) {
-      fin = true;
-      const EventLoad E{a, e};
-      double tau = 0.0;
-      if (a.cyc_slot) {
-        const int64_t j = a.cyc_slot[i];
-        if (j >= 0 && j < a.cyc_n) tau = a.cyc_tau[j];
-      }
-      const EventRowBins Bn = event_row(nd, E, a.event_offset, a.mass_a, tau, a.cyc_slot != nullptr, EVENT_COLS_SHORT,
-                                        (double*)nullptr);
-      sp = Bn.species;
-      pr = Bn.power;
-      if (h.nbins > 0) fb = np_hist_bin(Bn.phi, h.nbins);
-      if (h.sky) sb = sky_bin_of(A, cos_axis ? Bn.cos_theta : Bn.theta, Bn.phi, Bn.dw, sp);
-    }
-  }
-  for (int off = warpSize / 2; off > 0; off >>= 1) bad += __shfl_down(bad, off);
+  const EventRecord rec = event_record(a, h.node_start, i, h.nbins, h.sky != nullptr, A, cos_axis);
+  const bool fin = rec.state == RECORD_FINAL;
+  const int sp = rec.species, fb = rec.fb, sb = rec.sb;
+  const double pr = rec.power;
+  const int64_t e = rec.e;
+  const double bad = wave_sum(rec.state == RECORD_MISPLACED ? 1.0 : 0.0);
   for (int k = 0; k < h.n_k; ++k) {
     double pw = 0.0;
     if (fin) {
@@ -99,16 +70,9 @@ __global__ __launch_bounds__(256) void event_halo_bins_kernel(const EventRowsArg
       if (sb >= 0) unsafeAtomicAdd(&h.sky[k * h.sky_size + sb], pw);
     }
     if (h.Pw && i < a.n_nodes) h.Pw[k * a.n_nodes + i] = pw;
-    double ta = sp == 0 ? pw : 0.0, tp = sp == 0 ? 0.0 : pw;  // Σ power of axions, of photons
-    for (int off = warpSize / 2; off > 0; off >>= 1) {
-      ta += __shfl_down(ta, off);
-      tp += __shfl_down(tp, off);
-    }
-    if ((threadIdx.x & (warpSize - 1)) == 0) {
-      if (ta != 0.0) unsafeAtomicAdd(&h.totals[k * HS_TOT_COUNT + HS_TOT_SUM_AXION], ta);
-      if (tp != 0.0) unsafeAtomicAdd(&h.totals[k * HS_TOT_COUNT + HS_TOT_SUM_PHOTON], tp);
-      if (bad != 0.0) unsafeAtomicAdd(&h.totals[k * HS_TOT_COUNT + HS_TOT_MISPLACED], bad);
-    }
+    wave_add(&h.totals[k * HS_TOT_COUNT + HS_TOT_SUM_AXION], sp == 0 ? pw : 0.0);
+    wave_add(&h.totals[k * HS_TOT_COUNT + HS_TOT_SUM_PHOTON], sp == 0 ? 0.0 : pw);
+    lane0_add(&h.totals[k * HS_TOT_COUNT + HS_TOT_MISPLACED], bad);
   }
 }
 
@@ -134,4 +98,4 @@ hipError_t launch_event_halo_scan(const EventRowsArgs& a, const EventHaloScanArg
 }
 
 }  // namespace art
-#endif  // ART_EVENT_HALOSCAN_KERNELS
+#endif  // ART_EVENT_KERNELS

@@ -7,8 +7,8 @@
 //
 // The per-tree group-by is written once as __host__ __device__ functions over one tree's list of
 // MomentEntry: the kernels below and a host build for the CPU tests (tools/eventmoments.cpp) compile
-// the same source. The kernels themselves need art_kernels.hip's np_hist_bin, sky_bin_of, EventLoad
-// and event_row and are compiled only there (ART_EVENT_MOMENTS_KERNELS).
+// the same source. The kernels themselves take their records through art_event_record.h and are
+// compiled only in art_kernels.hip (ART_EVENT_KERNELS).
 #pragma once
 #include "art_core.h"
 
@@ -81,60 +81,46 @@ __host__ __device__ inline int64_t moment_photon_rows(const MomentEntry* t, int6
 
 }  // namespace art
 
-#ifdef ART_EVENT_MOMENTS_KERNELS
+#ifdef ART_EVENT_KERNELS
 namespace art {
 
-// record i lies in the range of its own tree: node_start[tree] <= i < node_start[tree + 1]
-__device__ inline bool moment_in_own_range(const EventMomentsArgs& m, int64_t n_events, int64_t i, int64_t tree) {
-  return tree >= 0 && tree < n_events && m.node_start[tree] <= i && i < m.node_start[tree + 1];
+// Pass A, one lane per node record, of the moments, of the scans' moments and (BINS = false: no acos, no atan2, no
+// bin search) of the spectrum: the entry of a final record of its own tree's range (event_record, art_event_record.h),
+// so a row is in the same bin in the first and in the second moments. A misplaced record is counted in *misplaced and
+// gets no entry.
+template <bool BINS>
+__global__ __launch_bounds__(256) void event_entries_kernel(const EventRowsArgs a, const int64_t* node_start,
+                                                            MomentEntry* entries, const int nbins, const int sky,
+                                                            double* misplaced, const SkyAxes A, const int cos_axis) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const EventRecord rec = event_record(a, node_start, i, BINS ? nbins : 0, BINS && sky, A, cos_axis);
+  if (i < a.n_nodes) {
+    MomentEntry t{MOMENT_NONE, -1, 0.0};
+    if (rec.state == RECORD_FINAL) {
+      t.flux = rec.fb >= 0 ? rec.species * nbins + rec.fb : (rec.species ? MOMENT_PHOTON : MOMENT_AXION);
+      t.sky = rec.sb;
+      t.power = rec.power;
+    }
+    entries[i] = t;
+  }
+  wave_add(misplaced, rec.state == RECORD_MISPLACED ? 1.0 : 0.0);
 }
 
-// Pass A, one lane per node record: the entry of a final node that lies in its own tree's range --
-// bins and power by event_row(row = nullptr), np_hist_bin and sky_bin_of, as event_rows_kernel takes
-// them, so a row is in the same bin in the first and in the second moments. A record inside some
-// tree's range whose `tree` is another is counted in totals[7] and gets no entry.
-__global__ __launch_bounds__(256) void event_moments_entries_kernel(const EventRowsArgs a, const EventMomentsArgs m,
-                                                                   const SkyAxes A, const int cos_axis) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  double bad = 0.0;
-  if (i < a.n_nodes) {
-    const art_tree_node& nd = a.nodes[i];
-    const int64_t e = nd.tree;
-    MomentEntry t{MOMENT_NONE, -1, 0.0};
-    if (!moment_in_own_range(m, a.n_events, i, e)) {
-      if (m.node_start[0] <= i && i < m.node_start[a.n_events]) bad = 1.0;
-    } else if (nd.is_final != 0) {
-      const EventLoad E{a, e};
-      double tau = 0.0;
-      if (a.cyc_slot) {
-        const int64_t j = a.cyc_slot[i];
-        if (j >= 0 && j < a.cyc_n) tau = a.cyc_tau[j];
-      }
-      const EventRowBins B = event_row(nd, E, a.event_offset, a.mass_a, tau, a.cyc_slot != nullptr, EVENT_COLS_SHORT,
-                                       (double*)nullptr);
-      const int fb = m.nbins > 0 ? np_hist_bin(B.phi, m.nbins) : -1;
-      t.flux = fb >= 0 ? B.species * m.nbins + fb : (B.species ? MOMENT_PHOTON : MOMENT_AXION);
-      t.sky = m.sky_sq ? sky_bin_of(A, cos_axis ? B.cos_theta : B.theta, B.phi, B.dw, B.species) : -1;
-      t.power = B.power;
-    }
-    m.entries[i] = t;
-  }
-  for (int off = warpSize / 2; off > 0; off >>= 1) bad += __shfl_down(bad, off);
-  if ((threadIdx.x & (warpSize - 1)) == 0 && bad != 0.0) unsafeAtomicAdd(&m.totals[EM_TOT_BAD], bad);
+// pass A's launch (host code): nothing without records
+template <bool BINS>
+hipError_t launch_event_entries(const EventRowsArgs& a, const int64_t* node_start, MomentEntry* entries, int nbins,
+                                bool sky, double* misplaced, const SkyAxes& A, int cos_axis, hipStream_t s) {
+  if (a.n_nodes <= 0) return hipSuccess;
+  hipLaunchKernelGGL(event_entries_kernel<BINS>, dim3((unsigned)((a.n_nodes + 255) / 256)), dim3(256), 0, s, a, node_start,
+                     entries, nbins, (int)sky, misplaced, A, cos_axis);
+  return hipGetLastError();
 }
 
 // the entries of tree e: its range cut to the records there are
 __device__ inline const MomentEntry* moment_tree(const EventMomentsArgs& m, int64_t n_nodes, int64_t e, int64_t* c,
                                                  int64_t* first) {
-  if (!m.node_start) {
-    *c = 0, *first = 0;
-    return m.entries;
-  }
-  int64_t s0 = m.node_start[e], s1 = m.node_start[e + 1];
-  s0 = s0 < 0 ? 0 : (s0 > n_nodes ? n_nodes : s0);
-  s1 = s1 < s0 ? s0 : (s1 > n_nodes ? n_nodes : s1);
-  *c = s1 - s0, *first = s0;
-  return m.entries + s0;
+  *c = tree_range(m.node_start, n_nodes, e, first);
+  return m.entries + *first;
 }
 
 // Pass B, one lane per node record and per event (grid-stride). The lane of the first row of an
@@ -151,7 +137,7 @@ __global__ __launch_bounds__(256) void event_moments_kernel(const EventRowsArgs 
     if (i < a.n_events) {
       int64_t c, first;
       const MomentEntry* t = moment_tree(m, a.n_nodes, i, &c, &first);
-      const double ae = (double)((a.attempts ? (int64_t)a.attempts[i] - 1 : 0) + moment_photon_rows(t, c, m.nbins));
+      const double ae = (double)(event_attempts_m1(a, i) + moment_photon_rows(t, c, m.nbins));
       tot[EM_TOT_EVENTS] += 1.0;
       tot[EM_TOT_A1] += ae;
       tot[EM_TOT_A2] += ae * ae;
@@ -166,7 +152,7 @@ __global__ __launch_bounds__(256) void event_moments_kernel(const EventRowsArgs 
     for (int which = MOMENT_KEY_FLUX; which <= MOMENT_KEY_SPECIES; ++which) {
       const int key = moment_group(t, c, j, which, m.nbins, &X);
       if (key < 0) continue;
-      if (ae < 0.0) ae = (double)((a.attempts ? (int64_t)a.attempts[e] - 1 : 0) + moment_photon_rows(t, c, m.nbins));
+      if (ae < 0.0) ae = (double)(event_attempts_m1(a, e) + moment_photon_rows(t, c, m.nbins));
       if (which == MOMENT_KEY_FLUX) {
         unsafeAtomicAdd(&m.flux_sq[key], X * X);
         unsafeAtomicAdd(&m.flux_xa[key], X * ae);
@@ -179,11 +165,7 @@ __global__ __launch_bounds__(256) void event_moments_kernel(const EventRowsArgs 
       }
     }
   }
-  for (int q = 0; q < EM_TOT_BAD; ++q) {
-    double t = tot[q];
-    for (int off = warpSize / 2; off > 0; off >>= 1) t += __shfl_down(t, off);
-    if ((threadIdx.x & (warpSize - 1)) == 0 && t != 0.0) unsafeAtomicAdd(&m.totals[q], t);
-  }
+  for (int q = 0; q < EM_TOT_BAD; ++q) wave_add(&m.totals[q], tot[q]);
 }
 
 // Pass B of a scan (the coupling scan's and the halo scan's moments kernels), one lane per node
@@ -198,7 +180,7 @@ __device__ inline void moment_scan_tables(const EventRowsArgs& a, const EventMom
   if (i < a.n_events) {
     int64_t c, first;
     const MomentEntry* t = moment_tree(m, a.n_nodes, i, &c, &first);
-    const double ae = (double)((a.attempts ? (int64_t)a.attempts[i] - 1 : 0) + moment_photon_rows(t, c, m.nbins));
+    const double ae = (double)(event_attempts_m1(a, i) + moment_photon_rows(t, c, m.nbins));
     ev[0] = 1.0, ev[1] = ae, ev[2] = ae * ae;
   }
   const MomentEntry* t = nullptr;
@@ -209,7 +191,7 @@ __device__ inline void moment_scan_tables(const EventRowsArgs& a, const EventMom
     t = moment_tree(m, a.n_nodes, e, &c, &first);
     j = i - first;
     if (j < 0 || j >= c) j = -1;
-    else ae = (double)((a.attempts ? (int64_t)a.attempts[e] - 1 : 0) + moment_photon_rows(t, c, m.nbins));
+    else ae = (double)(event_attempts_m1(a, e) + moment_photon_rows(t, c, m.nbins));
   }
   for (int k = 0; k < r.n_k; ++k) {
     double tot[EM_TOT_BAD] = {ev[0], ev[1], ev[2], 0.0, 0.0, 0.0, 0.0};
@@ -231,29 +213,21 @@ __device__ inline void moment_scan_tables(const EventRowsArgs& a, const EventMom
         }
       }
     }
-    for (int q = 0; q < EM_TOT_BAD; ++q) {
-      double v = tot[q];
-      for (int off = warpSize / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
-      if ((threadIdx.x & (warpSize - 1)) == 0 && v != 0.0) unsafeAtomicAdd(&r.mtotals[k * EM_TOT_COUNT + q], v);
-    }
+    for (int q = 0; q < EM_TOT_BAD; ++q) wave_add(&r.mtotals[k * EM_TOT_COUNT + q], tot[q]);
   }
 }
 
 // The moments tail of a scan's launch (host code; launch_event_reweight's and launch_event_halo_scan's): pass A
-// over the run's own records, then `kernel`, the scan's __global__ wrapper of moment_scan_tables.
+// over the run's own records (its misplaced records: slot 7 of the first set), then `kernel`, the scan's __global__
+// wrapper of moment_scan_tables.
 template <class Scan>
 hipError_t launch_scan_moments(void (*kernel)(EventRowsArgs, EventMomentsArgs, Scan), const EventRowsArgs& a, const Scan& r,
                                const SkyAxes& A, int cos_axis, hipStream_t s) {
   EventMomentsArgs m{};
   m.node_start = r.node_start; m.nbins = r.nbins; m.entries = r.entries;
-  m.sky_sq = r.sky_sq;   // (pass A reads it as "there is a sky table" only)
-  m.totals = r.mtotals;  // (pass A's misplaced records: slot 7 of the first set)
-  if (a.n_nodes > 0) {
-    hipLaunchKernelGGL(event_moments_entries_kernel, dim3((unsigned)((a.n_nodes + 255) / 256)), dim3(256), 0, s, a, m, A,
-                       cos_axis);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = launch_event_entries<true>(a, r.node_start, r.entries, r.nbins, r.sky_sq != nullptr,
+                                                  &r.mtotals[EM_TOT_BAD], A, cos_axis, s);
+  if (e != hipSuccess) return e;
   const int64_t n = a.n_nodes > a.n_events ? a.n_nodes : a.n_events;
   hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, m, r);
   return hipGetLastError();
@@ -263,16 +237,13 @@ hipError_t launch_event_moments(const EventRowsArgs& a, const EventMomentsArgs& 
                                 hipStream_t s) {
   const int64_t n = a.n_nodes > a.n_events ? a.n_nodes : a.n_events;
   if (n <= 0) return hipSuccess;
-  if (a.n_nodes > 0) {
-    hipLaunchKernelGGL(event_moments_entries_kernel, dim3((unsigned)((a.n_nodes + 255) / 256)), dim3(256), 0, s, a, m, A,
-                       cos_axis);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = launch_event_entries<true>(a, m.node_start, m.entries, m.nbins, m.sky_sq != nullptr,
+                                                  &m.totals[EM_TOT_BAD], A, cos_axis, s);
+  if (e != hipSuccess) return e;
   const int64_t blocks = (n + 255) / 256;
   hipLaunchKernelGGL(event_moments_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, a, m);
   return hipGetLastError();
 }
 
 }  // namespace art
-#endif  // ART_EVENT_MOMENTS_KERNELS
+#endif  // ART_EVENT_KERNELS

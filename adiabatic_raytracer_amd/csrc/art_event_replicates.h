@@ -10,10 +10,9 @@
 // and per group alone the events n_g, a_g = Σ_e ((attempts[e] - 1) + e's final photon rows), whose sum over the
 // groups is f_inx, and the records that lie in the range of a tree other than their own (skipped, as in the moments).
 //
-// One kernel, one lane per node record and per event. The kernel needs art_kernels.hip's np_hist_bin, sky_bin_of,
-// EventLoad and event_row and art_event_reweight.h's reweight_power, and is compiled only there
-// (ART_EVENT_REPLICATES_KERNELS). No LDS table: R flux tables and R sky maps rarely fit the 8192 doubles a block may
-// take, so every table is added to in HBM.
+// One kernel, one lane per node record and per event. The kernel takes its records through art_event_record.h and
+// is compiled only in art_kernels.hip (ART_EVENT_KERNELS). No LDS table: R flux tables and R sky maps rarely fit the
+// 8192 doubles a block may take, so every table is added to in HBM.
 #pragma once
 #include "art_core.h"
 #include "art_event_reweight.h"
@@ -33,13 +32,27 @@ __host__ __device__ inline int replicate_group(int64_t id, int R) {
 
 }  // namespace art
 
-#ifdef ART_EVENT_REPLICATES_KERNELS
+#ifdef ART_EVENT_KERNELS
 namespace art {
+
+// The power of a final record in set k of a call whose sets are of `kind` (Set: EventReplicatesArgs or
+// EventSpectrumArgs): pr the run's own power, i and e the record and its event, tau and sln read by kind 1 only. The
+// operations, and their order, are reweight_power's and pr * F.
+template <class Set>
+__device__ inline double set_power(const EventRowsArgs& a, const Set& r, int k, int64_t i, int64_t e, double pr, double tau,
+                                   double sln) {
+  if (r.kind == REP_KIND_RUN) return pr;
+  if (r.kind == REP_KIND_COUPLING)  // (each kind loads its own factors: a load shared by two branches stays pending
+                                    // on the way round them, and the wait for it also waits for the set's atomic adds)
+    return reweight_power(r.node_factor[k * a.n_nodes + i], r.event_factor[k * a.n_events + e], a.cyc_slot != nullptr, tau,
+                          sln);
+  return pr * r.event_factor[k * a.n_events + e];
+}
 
 // One lane per node record and per event (n = max(n_nodes, n_events) lanes).
 //   As an event, lane i adds 1 and attempts[i] - 1 to its group's n_g and a_g.
-//   As a record, a final record in its own tree's range takes its bins and its event's values once, by
-//   event_row(row = nullptr), np_hist_bin and sky_bin_of, so it falls into the bins event_rows_kernel puts it in;
+//   As a record, a final record of its own tree's range takes its bins and its event's values once (event_record,
+//   art_event_record.h) and a misplaced one adds 1 to the count of the group its `tree` names;
 //   a photon adds 1 to its group's a_g; then per set its power goes to flux[k][g], sky[k][g] and totals[k][g].
 // The per-group counts go through a block-private LDS table of 3 R doubles, flushed once per block. The totals are
 // summed over the runs of lanes of one group in a wave -- the records of a tree are neighbours, so a wave holds few
@@ -56,36 +69,14 @@ __global__ __launch_bounds__(256) void event_replicates_kernel(const EventRowsAr
     atomicAdd(&sh_grp[ge * REP_GRP_COUNT + REP_GRP_EVENTS], 1.0);
     if (a.attempts) atomicAdd(&sh_grp[ge * REP_GRP_COUNT + REP_GRP_A], (double)((int64_t)a.attempts[i] - 1));
   }
-  bool fin = false;
-  int sp = 0, fb = -1, sb = -1, g = -1;
-  double pr = 0.0, tau = 0.0, sln = 0.0;
-  int64_t e = 0;
-  if (i < a.n_nodes) {
-    const art_tree_node& nd = a.nodes[i];
-    e = nd.tree;
-    if (!(e >= 0 && e < a.n_events && r.node_start[e] <= i && i < r.node_start[e + 1])) {
-      if (r.node_start[0] <= i && i < r.node_start[a.n_events])
-        atomicAdd(&sh_grp[replicate_group(a.event_offset + e, R) * REP_GRP_COUNT + REP_GRP_MISPLACED], 1.0);
-    } else {
-      g = replicate_group(a.event_offset + e, R);
-      if (nd.is_final != 0) {
-        fin = true;
-        const EventLoad E{a, e};
-        if (a.cyc_slot) {
-          const int64_t j = a.cyc_slot[i];
-          if (j >= 0 && j < a.cyc_n) tau = a.cyc_tau[j];
-        }
-        const EventRowBins Bn = event_row(nd, E, a.event_offset, a.mass_a, tau, a.cyc_slot != nullptr, EVENT_COLS_SHORT,
-                                          (double*)nullptr);
-        sp = Bn.species;
-        pr = Bn.power;
-        sln = E.sln_prob();
-        if (r.nbins > 0) fb = np_hist_bin(Bn.phi, r.nbins);
-        if (r.sky) sb = sky_bin_of(A, cos_axis ? Bn.cos_theta : Bn.theta, Bn.phi, Bn.dw, sp);
-        if (sp == 1) atomicAdd(&sh_grp[g * REP_GRP_COUNT + REP_GRP_A], 1.0);
-      }
-    }
-  }
+  const EventRecord rec = event_record(a, r.node_start, i, r.nbins, r.sky != nullptr, A, cos_axis);
+  const bool fin = rec.state == RECORD_FINAL;
+  const int sp = rec.species, fb = rec.fb, sb = rec.sb;
+  const int64_t e = rec.e;
+  const int g = rec.state >= RECORD_OWN ? replicate_group(a.event_offset + e, R) : -1;
+  if (rec.state == RECORD_MISPLACED)
+    atomicAdd(&sh_grp[replicate_group(a.event_offset + e, R) * REP_GRP_COUNT + REP_GRP_MISPLACED], 1.0);
+  if (fin && sp == 1) atomicAdd(&sh_grp[g * REP_GRP_COUNT + REP_GRP_A], 1.0);
   // the runs of one group among a wave's lanes: `seg` counts the run heads up to this lane, so it does not fall
   // along the wave and equal numbers are neighbours, which the segmented sum below needs
   const int lane = threadIdx.x & (warpSize - 1);
@@ -96,11 +87,7 @@ __global__ __launch_bounds__(256) void event_replicates_kernel(const EventRowsAr
   for (int k = 0; k < r.n_k; ++k) {
     double pw = 0.0;
     if (fin) {
-      if (r.kind == REP_KIND_RUN) pw = pr;
-      else if (r.kind == REP_KIND_COUPLING)
-        pw = reweight_power(r.node_factor[k * a.n_nodes + i], r.event_factor[k * a.n_events + e], a.cyc_slot != nullptr,
-                            tau, sln);
-      else pw = pr * r.event_factor[k * a.n_events + e];
+      pw = set_power(a, r, k, i, e, rec.power, rec.tau, rec.sln);
       const int64_t kg = (int64_t)k * R + g;
       if (fb >= 0) unsafeAtomicAdd(&r.flux[kg * 2 * r.nbins + sp * r.nbins + fb], pw);
       if (sb >= 0) unsafeAtomicAdd(&r.sky[kg * r.sky_size + sb], pw);
@@ -134,4 +121,4 @@ hipError_t launch_event_replicates(const EventRowsArgs& a, const EventReplicates
 }
 
 }  // namespace art
-#endif  // ART_EVENT_REPLICATES_KERNELS
+#endif  // ART_EVENT_KERNELS

@@ -30,9 +30,9 @@
 //            exponent x_c is recomputed like a forward one and bweight_k = fexp(-s_k x_c): the stored
 //            factor 1 - P carries an absolute error of u/2, which is large beside a small bweight.
 // Written once as __host__ __device__ functions: the kernels below and a host build for the CPU
-// tests (tools/eventreweight.cpp, x0 through an accessor) compile the same source. The kernels need
-// art_kernels.hip's np_hist_bin, sky_bin_of, EventLoad and event_row, and art_event_moments.h's
-// entries, and are compiled only there (ART_EVENT_REWEIGHT_KERNELS).
+// tests (tools/eventreweight.cpp, x0 through an accessor) compile the same source. The kernels take
+// their records through art_event_record.h and their moments through art_event_moments.h's pass A and
+// entries, and are compiled only in art_kernels.hip (ART_EVENT_KERNELS).
 #pragma once
 #include "art_core.h"
 #include "art_event_moments.h"
@@ -146,19 +146,8 @@ __host__ __device__ inline double reweight_power(double W, double B, int cyclotr
 
 }  // namespace art
 
-#ifdef ART_EVENT_REWEIGHT_KERNELS
+#ifdef ART_EVENT_KERNELS
 namespace art {
-
-// the records of tree e: its range cut to the records there are
-__device__ inline int64_t reweight_range(const EventReweightArgs& r, int64_t n_nodes, int64_t e, int64_t* first) {
-  *first = 0;
-  if (!r.node_start) return 0;
-  int64_t s0 = r.node_start[e], s1 = r.node_start[e + 1];
-  s0 = s0 < 0 ? 0 : (s0 > n_nodes ? n_nodes : s0);
-  s1 = s1 < s0 ? s0 : (s1 > n_nodes ? n_nodes : s1);
-  *first = s0;
-  return s1 - s0;
-}
 
 struct ReweightPhysics {
   const KParams& P;
@@ -177,7 +166,7 @@ __global__ __launch_bounds__(256) void event_reweight_kernel(const KParams P, co
   if (e < a.n_events) {
     const double erg = r.erg[e];
     int64_t first;
-    const int64_t c = reweight_range(r, a.n_nodes, e, &first);
+    const int64_t c = tree_range(r.node_start, a.n_nodes, e, &first);
     if (c > 0) {
       ReweightPhysics x0of{P, erg};
       reweight_tree(a.nodes + first, c, r.mc_nodes, r.n_k, r.s, x0of, r.X0 + first, r.W + first, a.n_nodes, &cnt[1],
@@ -211,38 +200,18 @@ __global__ __launch_bounds__(256) void event_reweight_kernel(const KParams P, co
   }
 }
 
-// One lane per node record. A final record in its own tree's range takes its bins and its event's
-// values once, by event_row(row = nullptr), np_hist_bin and sky_bin_of, so it falls into the bins
-// event_rows_kernel puts it in; then per coupling its power goes to flux[k], sky[k] and the totals,
-// and every record that added to tot_prob adds W_k to the coverage.
+// One lane per node record. A final record of its own tree's range takes its bins and its event's
+// values once (event_record, art_event_record.h); then per coupling its power goes to flux[k], sky[k]
+// and the totals, and every record of its own range that added to tot_prob, final or not, adds W_k to
+// the coverage. Misplaced records are not counted here (the moments' pass A counts them).
 __global__ __launch_bounds__(256) void event_reweight_bins_kernel(const EventRowsArgs a, const EventReweightArgs r,
                                                                   const SkyAxes A, const int cos_axis) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool fin = false, cov = false;
-  int sp = 0, fb = -1, sb = -1;
-  double tau = 0.0, sln = 0.0;
-  int64_t e = 0;
-  if (i < a.n_nodes) {
-    const art_tree_node& nd = a.nodes[i];
-    e = nd.tree;
-    if (e >= 0 && e < a.n_events && r.node_start[e] <= i && i < r.node_start[e + 1]) {
-      cov = reweight_in_coverage(nd);
-      if (nd.is_final != 0) {
-        fin = true;
-        const EventLoad E{a, e};
-        if (a.cyc_slot) {
-          const int64_t j = a.cyc_slot[i];
-          if (j >= 0 && j < a.cyc_n) tau = a.cyc_tau[j];
-        }
-        const EventRowBins Bn = event_row(nd, E, a.event_offset, a.mass_a, tau, a.cyc_slot != nullptr, EVENT_COLS_SHORT,
-                                          (double*)nullptr);
-        sp = Bn.species;
-        sln = E.sln_prob();
-        if (r.nbins > 0) fb = np_hist_bin(Bn.phi, r.nbins);
-        if (r.sky) sb = sky_bin_of(A, cos_axis ? Bn.cos_theta : Bn.theta, Bn.phi, Bn.dw, sp);
-      }
-    }
-  }
+  const EventRecord rec = event_record(a, r.node_start, i, r.nbins, r.sky != nullptr, A, cos_axis);
+  const bool fin = rec.state == RECORD_FINAL, cov = rec.state >= RECORD_OWN && reweight_in_coverage(a.nodes[i]);
+  const int sp = rec.species, fb = rec.fb, sb = rec.sb;
+  const double tau = rec.tau, sln = rec.sln;
+  const int64_t e = rec.e;
   for (int k = 0; k < r.n_k; ++k) {
     double tot[3] = {0.0, 0.0, 0.0};  // Σ power of axions, of photons, coverage
     double pw = 0.0;
@@ -257,16 +226,12 @@ __global__ __launch_bounds__(256) void event_reweight_bins_kernel(const EventRow
       }
     }
     if (r.Pw && i < a.n_nodes) r.Pw[k * a.n_nodes + i] = pw;
-    for (int q = 0; q < 3; ++q) {
-      double t = tot[q];
-      for (int off = warpSize / 2; off > 0; off >>= 1) t += __shfl_down(t, off);
-      if ((threadIdx.x & (warpSize - 1)) == 0 && t != 0.0) unsafeAtomicAdd(&r.totals[k * RW_TOT_COUNT + q], t);
-    }
+    for (int q = 0; q < 3; ++q) wave_add(&r.totals[k * RW_TOT_COUNT + q], tot[q]);
   }
 }
 
 // The second moments per coupling, one lane per node record and per event: event_moments_kernel's
-// group-by over the entries of event_moments_entries_kernel (bins and a_e are those of the g0 forest
+// group-by over the entries of pass A, event_entries_kernel (bins and a_e are those of the g0 forest
 // for every k), with the powers of coupling k (Pw) in the place of the entries' own
 // (moment_scan_tables, art_event_moments.h).
 __global__ __launch_bounds__(256) void event_reweight_moments_kernel(const EventRowsArgs a, const EventMomentsArgs m,
@@ -290,4 +255,4 @@ hipError_t launch_event_reweight(const KParams& P, const KParams& Pb, const Even
 }
 
 }  // namespace art
-#endif  // ART_EVENT_REWEIGHT_KERNELS
+#endif  // ART_EVENT_KERNELS

@@ -13,8 +13,8 @@
 // X_{e,s} is the moments' (art_event_moments.h): the powers of e's final rows of species s summed in node order, the
 // double moment_group(..., MOMENT_KEY_SPECIES) and moment_group_scaled return. The bin rule, the order of the list,
 // the merge and the per-tree sum are __host__ __device__ functions: the kernels below and a host build for the CPU
-// tests (tools/eventspectrum.cpp) compile the same source. The kernels need art_kernels.hip's EventLoad and event_row
-// and art_event_reweight.h's reweight_power and are compiled only there (ART_EVENT_SPECTRUM_KERNELS).
+// tests (tools/eventspectrum.cpp) compile the same source. The kernels take their records through art_event_record.h
+// (pass A is the moments', without the bins) and are compiled only in art_kernels.hip (ART_EVENT_KERNELS).
 #pragma once
 #include "art_core.h"
 #include "art_event_moments.h"
@@ -105,40 +105,14 @@ __host__ __device__ inline void spectrum_event_power(const MomentEntry* t, int64
 
 }  // namespace art
 
-#ifdef ART_EVENT_SPECTRUM_KERNELS
+#ifdef ART_EVENT_KERNELS
 namespace art {
 
-// Pass A, one lane per node record: event_moments_entries_kernel without the bins. The entry of a final record in its
-// own tree's range holds its species (MOMENT_AXION / MOMENT_PHOTON) and the run's power, event_row's; a record inside
-// some tree's range whose `tree` is another is counted (totals[6] of the first set's first entry) and gets no entry.
-__global__ __launch_bounds__(256) void event_spectrum_entries_kernel(const EventRowsArgs a, const EventSpectrumArgs r) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  double bad = 0.0;
-  if (i < a.n_nodes) {
-    const art_tree_node& nd = a.nodes[i];
-    const int64_t e = nd.tree;
-    MomentEntry t{MOMENT_NONE, -1, 0.0};
-    if (!(e >= 0 && e < a.n_events && r.node_start[e] <= i && i < r.node_start[e + 1])) {
-      if (r.node_start[0] <= i && i < r.node_start[a.n_events]) bad = 1.0;
-    } else if (nd.is_final != 0) {
-      const EventLoad E{a, e};
-      double tau = 0.0;
-      if (a.cyc_slot) {
-        const int64_t j = a.cyc_slot[i];
-        if (j >= 0 && j < a.cyc_n) tau = a.cyc_tau[j];
-      }
-      const EventRowBins B = event_row(nd, E, a.event_offset, a.mass_a, tau, a.cyc_slot != nullptr, EVENT_COLS_SHORT,
-                                       (double*)nullptr);
-      t.flux = B.species ? MOMENT_PHOTON : MOMENT_AXION;
-      t.power = B.power;
-    }
-    r.entries[i] = t;
-  }
-  for (int off = warpSize / 2; off > 0; off >>= 1) bad += __shfl_down(bad, off);
-  if ((threadIdx.x & (warpSize - 1)) == 0 && bad != 0.0) unsafeAtomicAdd(&r.totals[SP_TOT_MISPLACED], bad);
-}
+// Pass A is art_event_moments.h's without the bins (event_entries_kernel<false>): the entry of a final record of its
+// own tree's range holds its species (MOMENT_AXION / MOMENT_PHOTON) and the run's power; the misplaced records are
+// counted in totals[6] of the first set's first entry.
 
-// the power of record j of the tree at `first` in set k, by kind: art_event_replicates.h's
+// the power of record j of the tree at `first` in set k, by kind (set_power, art_event_replicates.h)
 struct SpectrumPower {
   const EventRowsArgs& a;
   const EventSpectrumArgs& r;
@@ -147,15 +121,8 @@ struct SpectrumPower {
   int k;
   double sln;
   __device__ double operator()(int64_t j) const {
-    if (r.kind == REP_KIND_RUN) return t[j].power;
-    if (r.kind == REP_KIND_HALO) return t[j].power * r.event_factor[k * a.n_events + e];
-    double tau = 0.0;
-    if (a.cyc_slot) {
-      const int64_t q = a.cyc_slot[first + j];
-      if (q >= 0 && q < a.cyc_n) tau = a.cyc_tau[q];
-    }
-    return reweight_power(r.node_factor[k * a.n_nodes + first + j], r.event_factor[k * a.n_events + e],
-                          a.cyc_slot != nullptr, tau, sln);
+    const int64_t i = first + j;
+    return set_power(a, r, k, i, e, t[j].power, r.kind == REP_KIND_COUPLING ? event_tau(a, i) : 0.0, sln);
   }
 };
 
@@ -169,10 +136,7 @@ __global__ __launch_bounds__(256) void event_spectrum_tables_kernel(const EventR
   int64_t c = 0, first = 0;
   double sln = 0.0;
   if (live && r.node_start) {
-    int64_t s0 = r.node_start[e], s1 = r.node_start[e + 1];
-    s0 = s0 < 0 ? 0 : (s0 > a.n_nodes ? a.n_nodes : s0);
-    s1 = s1 < s0 ? s0 : (s1 > a.n_nodes ? a.n_nodes : s1);
-    first = s0, c = s1 - s0;
+    c = tree_range(r.node_start, a.n_nodes, e, &first);
     t = r.entries + first;
     if (r.kind == REP_KIND_COUPLING) sln = a.weight5[2 * a.n_events + e];
   }
@@ -200,11 +164,7 @@ __global__ __launch_bounds__(256) void event_spectrum_tables_kernel(const EventR
           v[SP_TOT_BAD] = 1.0;
         }
       }
-      for (int q = 0; q < SP_TOT_MISPLACED; ++q) {
-        double w = v[q];
-        for (int off = warpSize / 2; off > 0; off >>= 1) w += __shfl_down(w, off);
-        if ((threadIdx.x & (warpSize - 1)) == 0 && w != 0.0) unsafeAtomicAdd(&r.totals[ks * SP_TOT_COUNT + q], w);
-      }
+      for (int q = 0; q < SP_TOT_MISPLACED; ++q) wave_add(&r.totals[ks * SP_TOT_COUNT + q], v[q]);
     }
   }
 }
@@ -301,13 +261,10 @@ __global__ __launch_bounds__(SPECTRUM_BLOCK) void event_spectrum_top_kernel(cons
 
 hipError_t launch_event_spectrum(const EventRowsArgs& a, const EventSpectrumArgs& r, hipStream_t s) {
   if (a.n_events <= 0) return hipSuccess;
-  if (a.n_nodes > 0) {
-    hipLaunchKernelGGL(event_spectrum_entries_kernel, dim3((unsigned)((a.n_nodes + 255) / 256)), dim3(256), 0, s, a, r);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
+  hipError_t e = launch_event_entries<false>(a, r.node_start, r.entries, 0, false, &r.totals[SP_TOT_MISPLACED], SkyAxes{}, 0, s);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(event_spectrum_tables_kernel, dim3((unsigned)((a.n_events + 255) / 256)), dim3(256), 0, s, a, r);
-  const hipError_t e = hipGetLastError();
+  e = hipGetLastError();
   if (e != hipSuccess || r.top <= 0) return e;
   hipLaunchKernelGGL(event_spectrum_top_kernel, dim3((unsigned)(2 * r.n_k)), dim3(SPECTRUM_BLOCK), 0, s, a.n_events,
                      a.event_offset, r);
@@ -315,4 +272,4 @@ hipError_t launch_event_spectrum(const EventRowsArgs& a, const EventSpectrumArgs
 }
 
 }  // namespace art
-#endif  // ART_EVENT_SPECTRUM_KERNELS
+#endif  // ART_EVENT_KERNELS

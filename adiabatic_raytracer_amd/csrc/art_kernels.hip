@@ -2,6 +2,8 @@
 // flat's integrator instantiations (art_propagate.h), the small non-template kernels (fresh-record packing,
 // post-processing, the pointwise probes) and every host-side launcher (art_internal.h). Every other
 // integrator, the tail kernel, the helper kernel and the sampler are built in art_kernels_nolicm.hip.
+// The event kernels come last: art_event_record.h (the record rule they share) before event_rows_kernel,
+// then, under ART_EVENT_KERNELS, the kernels of the six art_event_*.h headers.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -1017,25 +1019,18 @@ hipError_t launch_event_gather(int64_t n_nodes, const art_tree_node* nodes, cons
   return hipGetLastError();
 }
 
-// event_row's source of its event's values: each is loaded from HBM where its column is written
-struct EventLoad {
-  const EventRowsArgs& a;
-  const int64_t e;
-  __device__ double x(int c) const { return a.x[c * a.n_events + e]; }
-  __device__ double k(int c) const { return a.k_init[c * a.n_events + e]; }
-  __device__ double cos_w() const { return a.weight5[e]; }
-  __device__ double sln_prob() const { return a.weight5[2 * a.n_events + e]; }
-  __device__ double vel_eng() const { return a.weight5[4 * a.n_events + e]; }
-  __device__ double back_prob() const { return a.back[e].prob; }
-  __device__ double back_weight() const { return a.back[e].weight; }
-  __device__ double back_count() const { return (double)a.back_counts[e]; }
-  __device__ double count() const { return (double)a.counts[e]; }
-  __device__ double info() const { return (double)a.infos[e]; }
-};
+}  // namespace art
+
+// EventLoad and what the event kernels at the end of this file share: the record rule, a tree's range, the wave add
+#include "art_event_record.h"
+
+namespace art {
 
 // One lane per node record (grid-stride). LDS holds [the flux table, 2 nbins | the sky table when
 // LDS]; the sky map goes through sky_accumulate, the flux table is block-private beside it and
 // flushed like it, the totals are summed per lane, then per wave, and added once per wave.
+// Its rule is not event_record's: a row needs no tree range, so every final record with a `tree` in
+// [0, n_events) gives one, wherever it lies, and the re-run's slot j is kept for the mismatch count.
 template <bool LDS>
 __global__ __launch_bounds__(1024) void event_rows_kernel(const EventRowsArgs a, const SkyAxes A, const int cos_axis,
                                                            const int sky_table) {
@@ -1113,32 +1108,16 @@ hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_a
 
 }  // namespace art
 
-// Event moments (art_event_moments_device): the header's kernels, which bin through np_hist_bin,
-// sky_bin_of, EventLoad and event_row above
-#define ART_EVENT_MOMENTS_KERNELS
+// The kernels and launchers of the six event headers (ART_EVENT_KERNELS; without it a header is its
+// __host__ __device__ functions alone, which the host builds of the CPU tests include): the event moments
+// (art_event_moments_device), the coupling scan (art_event_reweight_device), the halo scan
+// (art_event_halo_scan_device), the jackknife replicates (art_event_replicates_device), the coupling x halo grid
+// (art_event_grid_device) and the event power spectrum (art_event_spectrum_device). All take their records through
+// art_event_record.h above.
+#define ART_EVENT_KERNELS
 #include "art_event_moments.h"
-
-// The coupling scan (art_event_reweight_device): the header's kernels, which bin as the event rows do
-// and group as the event moments do
-#define ART_EVENT_REWEIGHT_KERNELS
 #include "art_event_reweight.h"
-
-// The halo scan (art_event_halo_scan_device): the header's kernels, which bin as the event rows do
-// and group as the event moments do
-#define ART_EVENT_HALOSCAN_KERNELS
 #include "art_event_haloscan.h"
-
-// The jackknife replicates (art_event_replicates_device): the header's kernel, which bins as the event rows do and
-// takes the scans' powers as the scans do
-#define ART_EVENT_REPLICATES_KERNELS
 #include "art_event_replicates.h"
-
-// The coupling x halo grid (art_event_grid_device): the header's kernel, which bins as the event rows do and takes
-// the two scans' factors
-#define ART_EVENT_GRID_KERNELS
 #include "art_event_grid.h"
-
-// The event power spectrum (art_event_spectrum_device): the header's kernels, which take the powers as the event
-// rows and the scans do and sum them per event as the event moments do
-#define ART_EVENT_SPECTRUM_KERNELS
 #include "art_event_spectrum.h"
