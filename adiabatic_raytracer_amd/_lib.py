@@ -118,6 +118,18 @@ class EventSpectrumOut(C.Structure):  # include/art.h art_event_spectrum_out
 SPECTRUM_TOTALS = ("events", "positive", "zeros", "bad", "sum", "sum_sq", "misplaced", "reserved")
 SPECTRUM_MAX_SUB_BITS, SPECTRUM_MAX_TOP = 4, 256
 
+class EventExactOut(C.Structure):  # include/art.h art_event_exact_out
+    _fields_ = [("kind", C.c_int32), ("n_sets", C.c_int32), ("nbins", C.c_int32), ("mode", C.c_int32),
+                ("node_factor", C.c_void_p), ("event_factor", C.c_void_p), ("flux_acc", C.c_void_p),
+                ("sky", C.POINTER(SkySpec)), ("sky_acc", C.c_void_p), ("totals_acc", C.c_void_p),
+                ("nonfinite", C.c_void_p), ("misplaced", C.c_void_p)]
+
+
+# the exact tables: ART_EXACT_LIMBS, the modes of their accumulation paths, the bins the LDS paths hold
+EXACT_LIMBS = 66
+EXACT_MODES = {"auto": 0, "lds": 1, "global": 2}
+EXACT_LDS_BINS, EXACT_LDS_FLUX_BINS = 124, 56
+
 EVENT_TOTALS = ("rows", "photon_rows", "sum_axion", "sum_photon", "attempts_minus_1", "cyclotron_mismatches")
 # art_event_moments_out::totals
 MOMENT_TOTALS = ("events", "A1", "A2", "Q_axion", "Q_photon", "C_axion", "C_photon", "bad_nodes")
@@ -207,6 +219,12 @@ SIGNATURES = {
     "art_event_replicates_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventReplicatesOut), _v]),
     "art_event_grid_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventGridOut), _v]),
     "art_event_spectrum_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventSpectrumOut), _v]),
+    "art_exact_histogram_device": (C.c_int, [_i64, _v, _v, _i32, _v, _v, _i32, _v]),
+    "art_exact_finish_device": (C.c_int, [_i64, _v, _v, _v]),
+    "art_exact_add_host": (C.c_int, [_i64, _v, _v, _i32, _v, _v]),
+    "art_exact_normalize_host": (C.c_int, [_i64, _v]),
+    "art_exact_round_host": (C.c_int, [_i64, _v, _v]),
+    "art_event_exact_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventExactOut), _v]),
     "art_comm_unique_id": (C.c_int, [_v]),
     "art_comm_init": (C.c_int, [_i32, _i32, _v]),
     "art_flux_allreduce": (C.c_int, [_v, _i64, _v]),

@@ -436,4 +436,22 @@ struct EventSpectrumArgs {
   double* X;
 };
 hipError_t launch_event_spectrum(const EventRowsArgs& a, const EventSpectrumArgs& r, hipStream_t s);
+// The exact tables (art_exact_histogram_device, art_exact_finish_device, art_event_exact_device; the kernels of
+// art_exact.h). An accumulator is ART_EXACT_LIMBS int64 limbs per bin. EventExactArgs: kind, node_factor and
+// event_factor as EventReplicatesArgs'; flux (n_k 2 nbins bins), sky (n_k sky_size bins; null: none) and totals
+// (n_k 2 bins) hold set k at k times the usual size; nonfinite is one float64 count per set, misplaced one in all.
+// Every launch leaves the accumulators it added to normalised.
+struct EventExactArgs {
+  const int64_t* node_start;
+  int32_t kind, n_k, nbins;
+  int64_t sky_size;
+  const double *node_factor, *event_factor;
+  int64_t *flux, *sky, *totals;
+  double *nonfinite, *misplaced;
+};
+hipError_t launch_exact_histogram(int64_t n, const int32_t* bins, const double* values, int n_bins, int64_t* acc,
+                                  double* nonfinite, bool lds, hipStream_t s);
+hipError_t launch_exact_finish(int64_t n_bins, const int64_t* acc, double* out, hipStream_t s);
+hipError_t launch_event_exact(const EventRowsArgs& a, const EventExactArgs& r, const SkyAxes& A, int cos_axis, int path,
+                              hipStream_t s);
 }  // namespace art

@@ -1,6 +1,6 @@
 // art_post.cpp -- the entry points around the propagate calls (declared in include/art.h): the
 // non-adiabatic probability, the sampler, event weights, flux histograms, sky maps, event rows, event moments, the coupling
-// scan, the halo scan, the jackknife replicates, the coupling x halo grid, the event power spectrum and the eval entry points the tests compare against the oracle. Each checks its arguments, then
+// scan, the halo scan, the jackknife replicates, the coupling x halo grid, the event power spectrum, the exact tables and the eval entry points the tests compare against the oracle. Each checks its arguments, then
 // launches on the caller's stream (or stages through the context's pool, the *_host ones).
 #include <algorithm>
 #include <cmath>
@@ -13,6 +13,7 @@
 #include "art_event_reweight.h"
 #include "art_event_rows.h"
 #include "art_event_spectrum.h"
+#include "art_exact.h"
 #include "art_host.h"
 
 namespace art {
@@ -849,6 +850,113 @@ int art_event_spectrum_device(const art_params* p, const art_event_rows_in* in, 
   const hipError_t e = art::launch_event_spectrum(a, r, s);
   (void)hipFreeAsync(block, s);
   HIP_OK(e);
+  return ART_OK;
+}
+
+// The exact tables (include/art.h; art_exact.h): values into fixed-point accumulators, one per bin, which every call
+// leaves normalised.
+int art_exact_histogram_device(int64_t n, const int32_t* bins, const double* values, int32_t n_bins, int64_t* acc,
+                               double* nonfinite, int32_t mode, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (n < 0) return fail(ART_E_INVALID, "n must be >= 0");
+  if (n_bins < 1 || n_bins > (1 << 24)) return fail(ART_E_INVALID, "n_bins must be in [1, 2^24]");
+  if (mode < 0 || mode > 2) return fail(ART_E_INVALID, "exact mode must be 0 (auto), 1 (LDS accumulators) or 2 (global adds)");
+  if (mode == 1 && n_bins > art::EXACT_LDS_BINS)
+    return fail(ART_E_INVALID, "exact mode 1: more than the 124 accumulators that fit the LDS budget");
+  if (n == 0) return ART_OK;
+  if (!bins || !values || !acc || !nonfinite) return fail(ART_E_INVALID, "NULL buffer");
+  int rc;
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  const bool lds = mode == 1 || (mode == 0 && n_bins <= art::EXACT_LDS_BINS);
+  HIP_OK(art::launch_exact_histogram(n, bins, values, n_bins, acc, nonfinite, lds, (hipStream_t)stream));
+  return ART_OK;
+}
+
+int art_exact_finish_device(int64_t n_bins, const int64_t* acc, double* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (n_bins < 0) return fail(ART_E_INVALID, "n_bins must be >= 0");
+  if (n_bins == 0) return ART_OK;
+  if (!acc || !out) return fail(ART_E_INVALID, "NULL buffer");
+  int rc;
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  HIP_OK(art::launch_exact_finish(n_bins, acc, out, (hipStream_t)stream));
+  return ART_OK;
+}
+
+// the host twins: art_exact.h's functions on host arrays of limbs; no device is touched
+int art_exact_add_host(int64_t n, const int32_t* bins, const double* values, int32_t n_bins, int64_t* acc,
+                       int64_t* nonfinite) {
+  if (n < 0 || n_bins < 1) return fail(ART_E_INVALID, "n must be >= 0 and n_bins >= 1");
+  if (n > 0 && (!values || !acc)) return fail(ART_E_INVALID, "NULL buffer");
+  int64_t since = 0, bad = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t b = bins ? bins[i] : 0;
+    if (b < 0 || b >= n_bins) continue;
+    if (!art::exact_add(acc + (int64_t)b * art::EXACT_LIMBS, values[i])) ++bad;
+    if (++since == art::EXACT_MAX_ADDS) {  // (the headroom rule)
+      for (int32_t q = 0; q < n_bins; ++q) art::exact_normalize(acc + (int64_t)q * art::EXACT_LIMBS);
+      since = 0;
+    }
+  }
+  if (n > 0)
+    for (int32_t q = 0; q < n_bins; ++q) art::exact_normalize(acc + (int64_t)q * art::EXACT_LIMBS);
+  if (nonfinite) *nonfinite += bad;
+  return ART_OK;
+}
+
+int art_exact_normalize_host(int64_t n_bins, int64_t* acc) {
+  if (n_bins < 0 || (n_bins > 0 && !acc)) return fail(ART_E_INVALID, "n_bins must be >= 0 and acc given");
+  for (int64_t q = 0; q < n_bins; ++q) art::exact_normalize(acc + q * art::EXACT_LIMBS);
+  return ART_OK;
+}
+
+int art_exact_round_host(int64_t n_bins, const int64_t* acc, double* out) {
+  if (n_bins < 0 || (n_bins > 0 && (!acc || !out))) return fail(ART_E_INVALID, "n_bins must be >= 0, acc and out given");
+  for (int64_t q = 0; q < n_bins; ++q) out[q] = art::exact_round(acc + q * art::EXACT_LIMBS);
+  return ART_OK;
+}
+
+// The exact tables of a chunk (include/art.h): the run's, a coupling scan's or a halo scan's powers into fixed-point
+// accumulators (art_exact.h), one kernel per set and the normalisation on `stream`.
+int art_event_exact_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                           const art_event_exact_out* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out) return fail(ART_E_INVALID, "NULL in or out");
+  if (out->kind < 0 || out->kind >= art::REP_KIND_COUNT)
+    return fail(ART_E_INVALID, "kind must be 0 (the run), 1 (a coupling scan) or 2 (a halo scan)");
+  if (out->n_sets < 1 || out->n_sets > art::REPLICATES_MAX_SETS) return fail(ART_E_INVALID, "n_sets must be in [1, 32]");
+  if (out->kind == art::REP_KIND_RUN && out->n_sets != 1) return fail(ART_E_INVALID, "n_sets must be 1 with kind 0");
+  if (out->kind == art::REP_KIND_COUPLING && in->n_nodes > 0 && !out->node_factor)
+    return fail(ART_E_INVALID, "node_factor is NULL (kind 1: the coupling scan's weights)");
+  if (out->kind != art::REP_KIND_RUN && !out->event_factor)
+    return fail(ART_E_INVALID, "event_factor is NULL (kind 1: the coupling scan's back, kind 2: the halo scan's ratio)");
+  if (out->mode < 0 || out->mode > 2) return fail(ART_E_INVALID, "exact mode must be 0 (auto), 1 (LDS accumulators) or 2 (global adds)");
+  if ((rc = event_in_ranges(in)) || (rc = event_out_ranges(0, out->nbins))) return rc;  // (no reserved field)
+  constexpr int lds_nbins = art::EXACT_LDS_FLUX_BINS;
+  if (out->mode == 1 && out->nbins > lds_nbins)
+    return fail(ART_E_INVALID, "exact mode 1: a flux table of more than 56 bins exceeds the LDS budget");
+  EventSky S;
+  if ((rc = event_sky(out->sky, /*honour_mode=*/false, out->nbins, &S))) return rc;  // (the sky accumulators stay in HBM)
+  if (in->n_events == 0) return ART_OK;
+  if (!out->totals_acc || !out->nonfinite || !out->misplaced) return fail(ART_E_INVALID, "totals_acc, nonfinite or misplaced is NULL");
+  if (out->nbins > 0 && !out->flux_acc) return fail(ART_E_INVALID, "flux_acc is NULL");
+  if (out->sky && !out->sky_acc) return fail(ART_E_INVALID, "sky_acc is NULL");
+  // IN_NODE_START_LATE and IN_CYC_END_STATES: the replicates call's checks
+  if ((rc = event_in_buffers(in, node_start, IN_NODE_START_LATE | IN_CYC_END_STATES))) return rc;
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  const art::EventRowsArgs a = event_args(p, in, /*end_states=*/false);
+  art::EventExactArgs r{};
+  r.node_start = node_start; r.kind = out->kind; r.n_k = out->n_sets; r.nbins = out->nbins; r.sky_size = S.size;
+  r.node_factor = out->node_factor; r.event_factor = out->event_factor;
+  r.flux = out->flux_acc; r.sky = out->sky ? out->sky_acc : nullptr; r.totals = out->totals_acc;
+  r.nonfinite = out->nonfinite; r.misplaced = out->misplaced;
+  const int path = out->mode == 2 ? 0 : (out->mode == 1 || out->nbins <= lds_nbins) ? 2 : 1;
+  HIP_OK(art::launch_event_exact(a, r, S.A, S.cos_axis, path, (hipStream_t)stream));
   return ART_OK;
 }
 

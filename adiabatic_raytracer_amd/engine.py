@@ -528,6 +528,118 @@ class Engine:
                                                    _stream()))
         return rep
 
+    # The most bytes the exact accumulators of one set of tables (the run's, a coupling scan's or a halo scan's) may take
+    EXACT_MAX_BYTES = 1 << 30
+
+    @classmethod
+    def _exact_fit(cls, what, K, nbins, shape):
+        """ValueError when the exact accumulators of K sets exceed EXACT_MAX_BYTES"""
+        sky = 1
+        for d in shape or (0,):
+            sky *= d
+        size = 8 * _lib.EXACT_LIMBS * K * (2 * nbins + sky + 2)
+        if size > cls.EXACT_MAX_BYTES:
+            raise ValueError(f"exact: the accumulators of {what} ({K} sets of {_lib.EXACT_LIMBS} limbs per bin) would take "
+                             f"{size} bytes, more than {cls.EXACT_MAX_BYTES}: drop the sky map from the scan, coarsen it or "
+                             "scan fewer values")
+
+    def _zero_exact(self, kind, K, nbins, shape):
+        z = lambda *d: torch.zeros(*d, _lib.EXACT_LIMBS, dtype=torch.int64, device=self.device)  # noqa: E731
+        return {"kind": kind, "flux": z(K, 2 * nbins), "sky": z(K, *shape) if shape else None, "totals": z(K, 2),
+                "nonfinite": torch.zeros(K, dtype=F64, device=self.device),
+                "misplaced": torch.zeros(1, dtype=F64, device=self.device)}
+
+    def exact_histogram(self, bins, values, n_bins, *, acc=None, nonfinite=None, mode="auto"):
+        """values[i] added exactly to accumulator bins[i] of n_bins (art_exact_histogram_device; DESIGN.md §3, "Exact
+        tables"), on the current stream: bins an int32 and values a float64 device tensor of one length; a bin < 0 or
+        >= n_bins is skipped, a NaN or an infinity is counted and not added. Returns (acc, nonfinite): acc
+        (n_bins, 66) int64, normalised limbs, and nonfinite (1) float64; both are ACCUMULATED into when given.
+        mode: "auto", "lds" (n_bins <= 124) or "global"; the limbs do not depend on it. exact_round gives the sums."""
+        n_bins = int(n_bins)
+        if bins.dtype != torch.int32 or values.dtype != F64 or bins.numel() != values.numel():
+            raise ValueError("exact_histogram: bins must be int32 and values float64, of one length")
+        if acc is None:
+            acc = torch.zeros(n_bins, _lib.EXACT_LIMBS, dtype=torch.int64, device=self.device)
+        if nonfinite is None:
+            nonfinite = torch.zeros(1, dtype=F64, device=self.device)
+        if tuple(acc.shape) != (n_bins, _lib.EXACT_LIMBS) or acc.dtype != torch.int64 or not acc.is_contiguous():
+            raise ValueError("exact_histogram: acc must be a contiguous int64 (n_bins, 66) tensor")
+        check(self.lib.art_exact_histogram_device(values.numel(), _p(bins.contiguous()), _p(values.contiguous()), n_bins,
+                                                  _p(acc), _p(nonfinite), _lib.EXACT_MODES[mode], _stream()))
+        return acc, nonfinite
+
+    def exact_round(self, acc):
+        """The correctly rounded float64 sums of accumulators (..., 66) (art_exact_finish_device), on the current
+        stream; the accumulators are only read"""
+        if acc.dtype != torch.int64 or acc.shape[-1] != _lib.EXACT_LIMBS or not acc.is_contiguous():
+            raise ValueError("exact_round: acc must be a contiguous int64 (..., 66) tensor")
+        out = self.empty(*acc.shape[:-1]) if acc.numel() else torch.zeros(*acc.shape[:-1], dtype=F64, device=self.device)
+        check(self.lib.art_exact_finish_device(out.numel(), _p(acc), _p(out), _stream()))
+        return out
+
+    def event_exact(self, sample, weight5, back, forward, *, event_offset=0, nbins=50, sky=None, cyclotron_rerun=None,
+                    acc=None, kind="run", node_factor=None, event_factor=None, mode="auto") -> dict:
+        """The exact tables of one chunk (art_event_exact_device; DESIGN.md §3, "Exact tables"), on the current stream
+        and without a synchronisation: event_replicates' arguments without the groups, and its kinds -- "run", one
+        set; "coupling" from node_factor = event_reweight(return_weights=True)'s "weights" and event_factor = its
+        "back"; "halo" from event_factor = event_halo_scan(return_ratio=True)'s "ratio". The powers of the chunk's
+        final rows are added to fixed-point accumulators of 66 int64 limbs per bin, so the tables are sums that do not
+        depend on the order of the adds. Returns a dict of device tensors: flux (K, 2 nbins, 66), sky (K, the map's
+        shape, 66; None without sky) and totals (K, 2, 66), int64 and normalised, nonfinite (K: powers that were NaN or
+        infinite and were not added) and misplaced (1), float64, with kind. acc: such a dict of an earlier chunk,
+        ACCUMULATED into and returned. mode: "auto", "lds" (totals and flux block-private in LDS; nbins <= 56) or
+        "global" (every add to HBM); the limbs do not depend on it. exact_finish gives the rounded tables."""
+        nbins = int(nbins)
+        if kind not in _lib.REPLICATE_KINDS:
+            raise ValueError(f"event_exact: kind must be one of {sorted(_lib.REPLICATE_KINDS)}, not {kind!r}")
+        if mode not in _lib.EXACT_MODES:
+            raise ValueError(f"event_exact: mode must be one of {sorted(_lib.EXACT_MODES)}, not {mode!r}")
+        if (kind == "coupling" and node_factor is None) or (kind != "run" and event_factor is None):
+            raise ValueError(f"event_exact: kind {kind!r} needs its factor arrays")
+        K = 1 if kind == "run" else int(event_factor.shape[0])
+        spec, shape, _ = self._sky_spec(sky)
+        if acc is None:
+            acc = self._zero_exact(kind, K, nbins, shape)
+        if (acc["kind"] != kind or tuple(acc["flux"].shape) != (K, 2 * nbins, _lib.EXACT_LIMBS) or
+                (None if acc["sky"] is None else tuple(acc["sky"].shape[1:-1])) != shape):
+            raise ValueError("event_exact: `acc` was made for another kind, other sets or other tables")
+        n, nn = sample["erg"].numel(), int(forward["n_nodes"])
+        if kind != "run" and (tuple(event_factor.shape) != (K, n) or not event_factor.is_contiguous()):
+            raise ValueError("event_exact: event_factor must be a contiguous (K, n_events) tensor")
+        if kind == "coupling" and (tuple(node_factor.shape) != (K, nn) or (nn > 0 and not node_factor.is_contiguous())):
+            raise ValueError("event_exact: node_factor must be a contiguous (K, n_nodes) tensor")
+        ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
+        eo = _lib.EventExactOut(_lib.REPLICATE_KINDS[kind], K, nbins, _lib.EXACT_MODES[mode],
+                                _p(node_factor) if kind == "coupling" else None, _p(event_factor) if kind != "run" else None,
+                                _p(acc["flux"]), C.pointer(spec) if spec is not None else None,
+                                _p(acc["sky"]) if shape else None, _p(acc["totals"]), _p(acc["nonfinite"]),
+                                _p(acc["misplaced"]))
+        check(self.lib.art_event_exact_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]), C.byref(eo),
+                                              _stream()))
+        return acc
+
+    def exact_finish(self, acc, f_inx=None) -> dict:
+        """The rounded tables of event_exact's accumulators, on the device (art_exact_finish_device): flux_raw
+        (K, 2, nbins), sky_raw (K, the map's shape; with a map) and totals_raw (K, 2), each entry the correctly rounded
+        exact sum of its rows' powers, with nonfinite (K) and acc (the accumulators, for trees.exact_merge); kind
+        "run": without the leading axis. f_inx: also flux, sky_map and sum_weight_sln_prob, the raw tables divided by
+        it (by 1 when it is 0) with the one IEEE division the float tables get."""
+        K = acc["flux"].shape[0]
+        out = {"flux_raw": self.exact_round(acc["flux"]).view(K, 2, -1), "totals_raw": self.exact_round(acc["totals"])}
+        if acc["sky"] is not None:
+            out["sky_raw"] = self.exact_round(acc["sky"])
+        out["nonfinite"] = acc["nonfinite"]
+        if acc["kind"] == "run":
+            out = {k: v[0] for k, v in out.items()}
+        if f_inx is not None:
+            # (a device tensor: torch turns a division by a host scalar into a multiplication by its reciprocal)
+            div = torch.full((), float(f_inx) if f_inx > 0 else 1.0, dtype=F64, device=self.device)
+            out.update(flux=out["flux_raw"] / div, sum_weight_sln_prob=out["totals_raw"] / div)
+            if "sky_raw" in out:
+                out["sky_map"] = out["sky_raw"] / div
+        out["acc"] = acc
+        return out
+
     # The most bytes the spectrum tables of one set of tables (the run's, a coupling scan's or a halo scan's) may take
     SPECTRUM_MAX_BYTES = 64 << 20
 
@@ -681,14 +793,15 @@ class Engine:
     def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
                    max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
                    cyclotron=False, rows=True, halo=None, errors=False, couplings=None, halos=None, replicates=None,
-                   grid=False, spectrum=None) -> dict:
+                   grid=False, spectrum=None, exact=False) -> dict:
         """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
         n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
         event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
         tree_offset = lo), the forward forest (tree_offset = lo) and event_rows (event_offset = lo); flux,
         sky map and totals accumulate on the device and the rows are collected there. The sampler and the
         Monte-Carlo draws are keyed by global ids, so the chunking does not change the rows (the weighted
-        tables differ by the order of their adds only). It blocks, because grow_trees does.
+        tables differ by the order of their adds only; exact=True adds tables that do not). It blocks,
+        because grow_trees does.
 
         chunk: events per chunk (None: one chunk). A chunk of c events holds at most c (max_nodes + 2)
         node records of 264 B for the forward forest (3.4 MB per 250 events at the defaults, 1.8 GB per
@@ -765,6 +878,18 @@ class Engine:
         of more than Engine.SPECTRUM_MAX_BYTES (64 MiB) per set of tables are a ValueError before any work is done.
         None (the default): exactly the keys below.
 
+        exact ("Exact tables"): beside the float tables, whose last bits depend on the order of their
+        adds, the same tables as the correctly rounded EXACT sums of the same row powers (event_exact per chunk, into
+        fixed-point accumulators of 66 int64 limbs per bin), which are identical across runs, chunk sizes,
+        event_offset splits and rank counts. The result gets "exact", exact_finish's dict of device tensors: flux
+        (2, nbins), sky_map and sum_weight_sln_prob (2), divided by f_inx with the one IEEE division the float tables
+        get, the undivided flux_raw, sky_raw and totals_raw, nonfinite (powers that were NaN or infinite: not added)
+        and acc, the normalised accumulators, which trees.exact_merge adds over runs. With couplings= or halos= the
+        scan's dict gets "exact" too, with the scan's leading axis (the scans are then called with return_weights /
+        return_ratio). Not covered: the grid, the second moments and σ, the replicate tables and the spectrum, which
+        are what they are without it. Accumulators of more than Engine.EXACT_MAX_BYTES (1 GiB) per set of tables are
+        a ValueError before any work is done. False (the default): exactly the keys below.
+
         Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
         or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
         f_inx, sum_weight_sln_prob, n_rows, n_photon_rows, and the raw, undivided parts for a caller that
@@ -799,6 +924,11 @@ class Engine:
                             ("the halo scan", halos and len(halos))):
                 if K:
                     self._replicates_fit(what, K, replicates, int(nbins), shape)
+        if exact:  # (before any work is done)
+            for what, K in (("the run", 1), ("the coupling scan", couplings and len(couplings)),
+                            ("the halo scan", halos and len(halos))):
+                if K:
+                    self._exact_fit(what, K, int(nbins), shape)
         if spectrum is not None:  # (before any work is done)
             for what, K in (("the run", 1), ("the coupling scan", couplings and len(couplings)),
                             ("the halo scan", halos and len(halos))):
@@ -812,9 +942,9 @@ class Engine:
         flux = torch.zeros(2 * int(nbins), dtype=F64, device=self.device)
         totals = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
         parts = []
-        moments = scan = hscan = rep = crep = hrep = cells = spec = cspec = hspec = None
+        moments = scan = hscan = rep = crep = hrep = cells = spec = cspec = hspec = xacc = cxacc = hxacc = None
         want = replicates is not None
-        factors = want or bool(grid) or spectrum is not None  # the scans hand out their factors
+        factors = want or bool(grid) or spectrum is not None or bool(exact)  # the scans hand out their factors
         for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
             c = min(chunk, int(event_offset) + n_events - lo)
             s = self.sample(c, seed=seed, ray_offset=lo, max_r=max_r, halo=halo)
@@ -858,6 +988,14 @@ class Engine:
                                                 event_factor=scan["back"], **kw)
                 if halos is not None:
                     hspec = self.event_spectrum(s, w5, back, fwd, spec=hspec, kind="halo", event_factor=hscan["ratio"], **kw)
+            if exact:
+                kw = dict(event_offset=lo, nbins=nbins, sky=sky_map, cyclotron_rerun=r["cyclotron_rerun"])
+                xacc = self.event_exact(s, w5, back, fwd, acc=xacc, **kw)
+                if couplings is not None:
+                    cxacc = self.event_exact(s, w5, back, fwd, acc=cxacc, kind="coupling", node_factor=scan["weights"],
+                                             event_factor=scan["back"], **kw)
+                if halos is not None:
+                    hxacc = self.event_exact(s, w5, back, fwd, acc=hxacc, kind="halo", event_factor=hscan["ratio"], **kw)
             if factors:  # (this chunk's factors are not part of the scans' tables)
                 for d, keys in ((scan, ("weights", "back", "back_prob")), (hscan, ("ratio",))):
                     for k in keys if d is not None else ():
@@ -934,6 +1072,16 @@ class Engine:
                 out["spectrum"] = spectrum_result(spectrum_raw(have), f_inx)
                 if out["spectrum"]["misplaced"] != 0:
                     raise _lib.ArtError(f"run_events: {out['spectrum']['misplaced']} node records lie in the range of "
+                                        "another tree")
+        if exact:
+            for out, have, kind, K in ((res, xacc, "run", 1), (res.get("coupling_scan"), cxacc, "coupling", len(couplings or ())),
+                                       (res.get("halo_scan"), hxacc, "halo", len(halos or ()))):
+                if out is None:
+                    continue
+                have = self._zero_exact(kind, K, int(nbins), shape) if have is None else have  # (no events)
+                out["exact"] = self.exact_finish(have, f_inx)
+                if float(have["misplaced"].item()) != 0:
+                    raise _lib.ArtError(f"run_events: {int(have['misplaced'].item())} node records lie in the range of "
                                         "another tree")
         if grid:
             from .trees import grid_raw, grid_result

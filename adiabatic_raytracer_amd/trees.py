@@ -198,7 +198,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
                      sky_map=None, device_trees=False, device_events=False, halo=None, errors=False,
-                     couplings=None, halos=None, replicates=None, grid=False, spectrum=None):
+                     couplings=None, halos=None, replicates=None, grid=False, spectrum=None, exact=False):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -298,7 +298,19 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     power they carry, and the Hill tail index α -- from the tables summed over the ranks and the ranks' lists merged,
     the last parts of the vector of the same all-reduce. The host paths take the tables from the rank's rows
     (rows_spectrum); device_events takes them from art_event_spectrum_device, and there the scans' dicts get
-    "spectrum" too. With the default None every row, file, run_info key and the reduced vector are unchanged."""
+    "spectrum" too. With the default None every row, file, run_info key and the reduced vector are unchanged.
+
+    exact (beyond the reference; needs device_events=True; DESIGN.md §3, "Exact tables"): the flux table, the sky map
+    and the totals also as the correctly rounded exact sums of the same row powers (Engine.run_events(exact=True)),
+    which do not depend on the order of the adds, the chunks or the number of ranks. The ranks' normalised limbs are
+    integers below 2^32, which float64 holds exactly, and their sums over the ranks too: they ride as the LAST part of
+    the vector of the same all-reduce and are converted back and rounded after it. run_info["exact"] is exact_result's
+    dict of host arrays, and the scans' dicts get "exact" too. On the other two paths the tables are built on the host
+    and exact=True is a ValueError: rows_exact gives the same tables from their rows. With the default False every
+    row, file, run_info key and the reduced vector are unchanged."""
+    if exact and not device_events:
+        raise ValueError("exact: the exact tables are accumulated from forests held in HBM and need device_events=True "
+                         "(trees.rows_exact gives the same tables from the rows of the other paths)")
     if spectrum is not None:
         spectrum_keywords(spectrum)  # (before any work is done)
     if grid and not device_events:
@@ -324,7 +336,8 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                                         cyclotron=cyclotron, sky_map=sky_map, halo=halo, errors=errors,
                                         couplings=couplings, halos=halos, replicates=replicates,
                                         **({"grid": True} if grid else {}),
-                                        **({} if spectrum is None else {"spectrum": spectrum}))
+                                        **({} if spectrum is None else {"spectrum": spectrum}),
+                                        **({"exact": True} if exact else {}))
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -422,7 +435,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
                              saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map,
                              halo=None, errors=False, couplings=None, halos=None, replicates=None, grid=False,
-                             spectrum=None):
+                             spectrum=None, exact=False):
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
@@ -440,7 +453,12 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                                   **({} if halos is None else {"halos": halos}),
                                   **({} if replicates is None else {"replicates": replicates}),
                                   **({"grid": True} if grid else {}),
-                                  **({} if spectrum is None else {"spectrum": spectrum}))
+                                  **({} if spectrum is None else {"spectrum": spectrum}),
+                                  **({"exact": True} if exact else {}))
+    xa = None
+    if exact:
+        xa = {"run": exact_raw(r["exact"]["acc"])}
+        xa.update({k: exact_raw(r[k + "_scan"]["exact"]["acc"]) for k in ("coupling", "halo") if k + "_scan" in r})
     spec = None
     if spectrum is not None:
         spec = {"run": r["spectrum"]["raw"]}
@@ -460,7 +478,7 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                        None if halos is None else r["halo_scan"]["raw"], nbins=nbins, sky_kw=sky_kw, errors=errors,
                        world=world, run_info=run_info, events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path,
                        **({} if rep is None else {"replicates": rep}), **({"grid": r["grid"]["raw"]} if grid else {}),
-                       **({} if spec is None else {"spectrum": spec, "rank": rank}))
+                       **({} if spec is None else {"spectrum": spec, "rank": rank}), **({} if xa is None else {"exact": xa}))
 
 
 def cyclotron_optical_depth(params: Params, fin, erg) -> np.ndarray:
@@ -1113,6 +1131,189 @@ def replicates_result(raw, f_inx) -> dict:
     return res
 
 
+EXACT_KEYS = ("flux", "sky", "totals")  # the accumulator tables of an exact dict, each (K, ..., 66) int64
+EXACT_PARTS = ("run", "coupling", "halo")  # the order of the exact parts of a rank's vector
+
+
+def _exact_host(fn, *args):
+    lib = _lib.load()
+    rc = getattr(lib, fn)(*args)
+    if rc != 0:
+        raise _lib.ArtError(f"{fn}: {lib.art_last_error().decode()}")
+
+
+def exact_add(values, bins=None, n_bins=1, acc=None):
+    """values added exactly to the accumulators bins[i] of n_bins (art_exact_add_host, the host twin of the device
+    adds; bins None: all to bin 0; a bin < 0 or >= n_bins is skipped). Returns (acc, nonfinite): acc (n_bins, 66)
+    int64, normalised, ACCUMULATED into when given, and the number of NaNs and infinities, which are not added."""
+    import ctypes as C
+    values = np.ascontiguousarray(values, np.float64)
+    if bins is not None:
+        bins = np.ascontiguousarray(bins, np.int32)
+        if bins.shape != values.shape:
+            raise ValueError("exact_add: bins and values must have one length")
+    if acc is None:
+        acc = np.zeros((int(n_bins), _lib.EXACT_LIMBS), np.int64)
+    if acc.shape != (int(n_bins), _lib.EXACT_LIMBS) or acc.dtype != np.int64 or not acc.flags.c_contiguous:
+        raise ValueError("exact_add: acc must be a contiguous int64 (n_bins, 66) array")
+    bad = C.c_int64(0)
+    _exact_host("art_exact_add_host", values.size, None if bins is None else bins.ctypes.data, values.ctypes.data, int(n_bins),
+                acc.ctypes.data, C.addressof(bad))
+    return acc, int(bad.value)
+
+
+def exact_normalize(acc):
+    """Accumulators (..., 66) int64 carry-propagated in place (art_exact_normalize_host): every limb but the top one in
+    [0, 2^32). The value does not change. Returns acc."""
+    if acc.dtype != np.int64 or acc.shape[-1] != _lib.EXACT_LIMBS or not acc.flags.c_contiguous:
+        raise ValueError("exact_normalize: acc must be a contiguous int64 (..., 66) array")
+    _exact_host("art_exact_normalize_host", acc.size // _lib.EXACT_LIMBS, acc.ctypes.data)
+    return acc
+
+
+def exact_round(acc) -> np.ndarray:
+    """The correctly rounded float64 sums of accumulators (..., 66) int64 (art_exact_round_host, the host twin of
+    art_exact_finish_device): round-to-nearest-even of the exact sum. The accumulators are only read."""
+    acc = np.ascontiguousarray(acc, np.int64)
+    if acc.shape[-1] != _lib.EXACT_LIMBS:
+        raise ValueError("exact_round: acc must be an int64 (..., 66) array")
+    out = np.zeros(acc.shape[:-1])
+    _exact_host("art_exact_round_host", out.size, acc.ctypes.data, out.ctypes.data)
+    return out
+
+
+def exact_raw(acc) -> dict:
+    """Engine.event_exact's dict with its tensors on the host (numpy): what exact_merge adds over chunks and ranks"""
+    host = lambda v: None if v is None else (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v))  # noqa: E731
+    out = {k: host(acc.get(k)) for k in EXACT_KEYS + ("nonfinite", "misplaced")}
+    out["kind"] = acc["kind"]
+    return out
+
+
+def exact_merge(accs) -> dict:
+    """The accumulator dicts (Engine.event_exact's, run_events' res["exact"]["acc"], rows_exact(acc=True)'s "acc") of
+    chunks, ranks or files added limb by limb, in any order, and normalised: the accumulators of all their rows
+    together. The dicts must be of one kind and one set of tables. Returns a host dict (exact_raw's)."""
+    accs = [exact_raw(a) for a in accs]
+    if not accs:
+        raise ValueError("exact_merge: nothing to merge")
+    first = accs[0]
+    out = {"kind": first["kind"]}
+    for a in accs[1:]:
+        if a["kind"] != first["kind"] or any((a[k] is None) != (first[k] is None) or
+                                             (a[k] is not None and a[k].shape != first[k].shape) for k in EXACT_KEYS):
+            raise ValueError("exact_merge: the accumulators were made for another kind, other sets or other tables")
+    for k in EXACT_KEYS:
+        out[k] = None
+        if first[k] is not None:
+            total = np.zeros(first[k].shape, np.int64)
+            for j, a in enumerate(accs):
+                total += a[k]  # (normalised limbs: below 2^32 each)
+                if j % (1 << 20) == (1 << 20) - 1:
+                    exact_normalize(total)
+            out[k] = exact_normalize(total)
+    for k in ("nonfinite", "misplaced"):
+        out[k] = np.sum([np.asarray(a[k], np.float64) for a in accs], axis=0)
+    return out
+
+
+def exact_finish(acc) -> dict:
+    """The rounded tables of an accumulator dict on the host, the twin of Engine.exact_finish: flux_raw (K, 2, nbins),
+    sky_raw (K, the map's shape; with a map) and totals_raw (K, 2), each entry the correctly rounded exact sum of its
+    rows' powers, and nonfinite (K); kind "run": without the leading axis."""
+    acc = exact_raw(acc)
+    K = acc["flux"].shape[0]
+    out = {"flux_raw": exact_round(acc["flux"]).reshape(K, 2, -1), "totals_raw": exact_round(acc["totals"])}
+    if acc["sky"] is not None:
+        out["sky_raw"] = exact_round(acc["sky"])
+    out["nonfinite"] = np.asarray(acc["nonfinite"], np.float64).copy()
+    return {k: v[0] for k, v in out.items()} if acc["kind"] == "run" else out
+
+
+def exact_result(acc, f_inx) -> dict:
+    """run_info["exact"]: exact_finish's tables with flux, sky_map and sum_weight_sln_prob, the raw ones divided by
+    f_inx (by 1 when it is 0) with one IEEE division each, and acc, the accumulators themselves (exact_raw's dict).
+    A misplaced record is an ArtError, as in the replicates."""
+    acc = exact_raw(acc)
+    if float(np.sum(acc["misplaced"])) != 0:
+        raise _lib.ArtError(f"exact: {int(np.sum(acc['misplaced']))} node records lie in the range of another tree")
+    out = exact_finish(acc)
+    div = float(f_inx) if f_inx > 0 else 1.0
+    out.update(flux=out["flux_raw"] / div, sum_weight_sln_prob=out["totals_raw"] / div)
+    if "sky_raw" in out:
+        out["sky_map"] = out["sky_raw"] / div
+    out["acc"] = acc
+    return out
+
+
+def exact_pack(acc) -> np.ndarray:
+    """A rank's exact accumulators (exact_raw's dict, normalised) as float64 for the run's all-reduce: the limbs of the
+    tables there are, in EXACT_KEYS' order, then nonfinite and misplaced. A normalised limb is an integer below 2^32
+    (the top one a small signed one), which float64 holds exactly, as it does their sums over up to 2^21 ranks."""
+    limbs = [acc[k].reshape(-1) for k in EXACT_KEYS if acc.get(k) is not None]
+    if any(np.abs(v).max(initial=0) >= 2 ** 32 for v in limbs):
+        raise ValueError("exact_pack: the accumulators are not normalised, or a sum exceeds 2^1038")
+    return np.concatenate([v.astype(np.float64) for v in limbs] + [np.asarray(acc[k], np.float64).reshape(-1)
+                                                                   for k in ("nonfinite", "misplaced")])
+
+
+def exact_unpack(vec, like) -> dict:
+    """exact_pack's vector, summed over the ranks, back into a dict shaped like `like` (the rank's own), normalised"""
+    out, at = {"kind": like["kind"]}, 0
+    for k in EXACT_KEYS:
+        out[k] = None
+        if like.get(k) is not None:
+            out[k] = exact_normalize(np.rint(vec[at:at + like[k].size]).astype(np.int64).reshape(like[k].shape))
+            at += like[k].size
+    for k in ("nonfinite", "misplaced"):
+        n = np.asarray(like[k]).size
+        out[k] = np.asarray(vec[at:at + n], np.float64).copy()
+        at += n
+    return out
+
+
+def rows_exact(rows, nbins, sky_kw=None, f_inx=None, acc=False) -> dict:
+    """The exact tables from npy rows (column 7 raw or divided alike: the tables are in the powers' own units): the
+    host oracle of art_event_exact_device, and the exact tables of row files written earlier. Per bin of the flux
+    table (hist_bins of column 3 per species), of the sky map (sky_bins, with sky_kw) and per species, math.fsum of
+    the rows' powers column 8 * column 7, which is the correctly rounded exact sum. Returns flux_raw (2, nbins),
+    sky_raw (2, n_theta, n_phi, n_dw; with sky_kw), totals_raw (2) and nonfinite, the rows whose power is NaN or
+    infinite (not added anywhere); with f_inx also flux, sky_map and sum_weight_sln_prob, divided by it; with
+    acc=True also "acc", the same sums as accumulators (exact_add), which exact_merge adds to those of other files."""
+    import math
+    rows = np.asarray(rows, np.float64)
+    nbins = int(nbins)
+    sp = (rows[:, 1] != 0).astype(np.int64)
+    p = rows[:, 8] * rows[:, 7]
+    ok = np.isfinite(p)
+    fb = hist_bins(rows[:, 3], nbins) if nbins > 0 else np.full(len(rows), -1)
+    labels = [("flux", np.where(fb >= 0, sp * nbins + fb, -1), (2, nbins)), ("totals", sp, (2,))]
+    if sky_kw is not None:
+        kw = {k: sky_kw[k] for k in ("n_theta", "n_phi", "n_dw", "theta_axis", "dw_range") if k in sky_kw}
+        shape = (2, kw.get("n_theta", 32), kw.get("n_phi", 64), kw.get("n_dw", 1))
+        labels.append(("sky", sky_bins(rows[:, 2], rows[:, 3], rows[:, 12], rows[:, 1], **kw), shape))
+    out, accs = {"nonfinite": float(np.count_nonzero(~ok))}, {"kind": "run", "sky": None}
+    for name, lab, shape in labels:
+        lab = np.where(ok, lab, -1)
+        size = int(np.prod(shape))
+        keep = lab >= 0
+        order = np.argsort(lab[keep], kind="stable")
+        cut = np.searchsorted(lab[keep][order], np.arange(size + 1))
+        vals = p[keep][order]
+        out[name + "_raw"] = np.array([math.fsum(vals[cut[b]:cut[b + 1]]) for b in range(size)]).reshape(shape)
+        if acc:
+            accs[name] = exact_add(p, lab, size)[0].reshape(1, *(shape if name != "flux" else (2 * nbins,)), _lib.EXACT_LIMBS)
+    if f_inx is not None:
+        div = float(f_inx) if f_inx > 0 else 1.0
+        out.update(flux=out["flux_raw"] / div, sum_weight_sln_prob=out["totals_raw"] / div)
+        if "sky_raw" in out:
+            out["sky_map"] = out["sky_raw"] / div
+    if acc:
+        accs.update(nonfinite=np.array([out["nonfinite"]]), misplaced=np.zeros(1))
+        out["acc"] = accs
+    return out
+
+
 def jackknife(rep, fn, cov=False) -> dict:
     """The delete-a-group jackknife of fn over a run's replicates (replicates_result's dict: run_events' or run_info's
     "replicates", or a scan's). fn gets a dict of normalised tables -- flux (2, nbins), sky_map (2, n_theta, n_phi,
@@ -1678,25 +1879,28 @@ REPLICATE_PARTS = ("run", "coupling", "halo")  # the order of the replicate part
 SPECTRUM_PARTS = ("run", "coupling", "halo")  # the order of the spectrum parts of a rank's vector
 
 
-def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None, grid=None, spectrum=None, rank=0, world=1):
+def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None, grid=None, spectrum=None, rank=0, world=1,
+                exact=None):
     """A rank's vector for main_runner_tree's single all-reduce, [pack_totals | coupling scan | halo scan |
     replicates... | grid]: the rank's pack_totals vector, then scan_pack of its coupling scan's raw tables and
     halo_scan_pack of its halo scan's, each only when there is one, then replicates_pack of each raw dict of
     `replicates` (a dict with the keys "run", "coupling", "halo" there are, in that order; None: none), then grid_pack
     of `grid` (the rank's grid_raw; None: none), so every earlier part keeps its place and its end, and LAST
     spectrum_pack(raw, rank, world) of each raw dict of `spectrum` (a dict with the keys "run", "coupling", "halo"
-    there are, in that order; None: none, and the vector is what it is without the keyword). Returns (the vector,
-    where each of its parts ends)."""
+    there are, in that order; None: none, and the vector is what it is without the keyword); after them exact_pack of
+    each raw dict of `exact` (the same keys and order; None: none, and the vector is what it is without the keyword).
+    Returns (the vector, where each of its parts ends)."""
     parts = [totals] + [pack(raw) for pack, raw in ((scan_pack, coupling_raw), (halo_scan_pack, halo_raw)) if raw is not None]
     parts += [replicates_pack(replicates[k]) for k in REPLICATE_PARTS if replicates and replicates.get(k) is not None]
     if grid is not None:
         parts.append(grid_pack(grid))
     parts += [spectrum_pack(spectrum[k], rank, world) for k in SPECTRUM_PARTS if spectrum and spectrum.get(k) is not None]
+    parts += [exact_pack(exact[k]) for k in EXACT_PARTS if exact and exact.get(k) is not None]
     return (np.concatenate(parts) if len(parts) > 1 else totals), np.cumsum([len(v) for v in parts])
 
 
 def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw, errors, world, run_info, events, n_events,
-                g0, path, replicates=None, grid=None, spectrum=None, rank=0):
+                g0, path, replicates=None, grid=None, spectrum=None, rank=0, exact=None):
     """The end of main_runner_tree on every path: the rank's vector (rank_vector of its pack_totals vector and its
     scans' raw tables) summed over the ranks in ONE all-reduce, σ from the reduced tables, column 8 of the rank's
     rows divided by the global f_inx, run_info (a dict or None; events: the rank's (lo, hi), n_events: the run's),
@@ -1705,10 +1909,13 @@ def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw
     and come back as run_info["replicates"] and as "replicates" in the scans' dicts. grid: the rank's grid_raw, the
     vector's part after them, which comes back as run_info["grid"] (grid_result). spectrum: the rank's raw spectra
     (rank_vector's keyword; rank: this rank's slot for its lists), the vector's last parts, which come back merged
-    over the ranks as run_info["spectrum"] and as "spectrum" in the scans' dicts (spectrum_result). Returns the rows."""
+    over the ranks as run_info["spectrum"] and as "spectrum" in the scans' dicts (spectrum_result). exact: the rank's
+    raw exact accumulators (rank_vector's keyword), the parts after those, which come back summed over the ranks as
+    run_info["exact"] and as "exact" in the scans' dicts (exact_result). Returns the rows."""
     from .shard import allreduce_sum
     tot, ends = rank_vector(totals, coupling_raw, halo_raw, replicates=replicates, **({} if grid is None else {"grid": grid}),
-                            **({} if spectrum is None else {"spectrum": spectrum, "rank": rank, "world": world}))
+                            **({} if spectrum is None else {"spectrum": spectrum, "rank": rank, "world": world}),
+                            **({} if exact is None else {"exact": exact}))
     n_scans = (coupling_raw is not None) + (halo_raw is not None)
     if world > 1:
         tot = allreduce_sum(tot)
@@ -1745,6 +1952,11 @@ def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw
             raw = spectrum_unpack(tot[ends[at + j]:ends[at + j + 1]], spectrum[k], world)
             where = run_info if k == "run" else run_info[k + "_scan"]
             where["spectrum"] = spectrum_result(raw, int(round(f_glob)))
+        at += sum(1 for k in SPECTRUM_PARTS if spectrum and spectrum.get(k) is not None)
+        for j, k in enumerate(k for k in EXACT_PARTS if exact and exact.get(k) is not None):
+            raw = exact_unpack(tot[ends[at + j]:ends[at + j + 1]], exact[k])
+            where = run_info if k == "run" else run_info[k + "_scan"]
+            where["exact"] = exact_result(raw, int(round(f_glob)))
     if path is not None:
         os.makedirs(os.path.dirname(path), exist_ok=True)
         np.save(path, rows)

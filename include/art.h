@@ -919,6 +919,73 @@ typedef struct art_event_spectrum_out {
 int art_event_spectrum_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
                               const art_event_spectrum_out* out, void* stream);
 
+/* ---- exact tables: sums that do not depend on the order of the adds, the chunks or the ranks ----
+ * The float tables above are sums of per-row powers with float64 hardware adds, so their last bits depend on the
+ * order the adds arrive in. These calls keep the SAME sums exactly, in a fixed-point accumulator per bin, and round
+ * once at the end: the result is round-to-nearest-even of the infinitely precise sum, a function of the multiset of
+ * the powers alone, equal to float(sum(Fraction(v) for v in powers)) on the host.
+ *   A finite double is ± m 2^q 2^-1074 with an integer m < 2^53 and q = max(e, 1) - 1 in 0 .. 2045 (e the biased
+ *   exponent; a subnormal takes q = 0 without the implicit bit). A bin is ART_EXACT_LIMBS int64 limbs (528 bytes),
+ *   limb j carrying the bits [32 j, 32 j + 32) above 2^-1074. Adding a value is at most three 64-bit integer adds:
+ *   m << (q & 31), cut into 32-bit pieces, goes to the limbs q >> 5, + 1 and + 2, negated for a negative value.
+ *   NORMALISED: every limb but the top one lies in [0, 2^32); the top one is signed and carries the sign and the
+ *   headroom. Normalising changes the representation and never the value; normalised accumulators of the same
+ *   multiset of values are equal limb by limb, and normalised accumulators add limb by limb (chunks, ranks, files),
+ *   the sum to be normalised again before 2^30 of them are added.
+ *   THE HEADROOM RULE: every entry point below LEAVES THE ACCUMULATORS IT ADDED TO NORMALISED and expects them
+ *   normalised (zeros are), and normalises at least every 2^30 values inside a call, so no limb below the top one can
+ *   overflow whatever the number of calls and rows. The top limb wraps only when the magnitude of a running sum
+ *   reaches 2^1069, 2^45 times the largest double (a sum beyond the largest double finishes as ±inf long before).
+ *   A NaN or an infinity is not added; it is counted in `nonfinite` (float64, ADDED to, one vector add per wave).
+ * acc: n_bins * ART_EXACT_LIMBS int64, ACCUMULATED into (zero it first), ordinary device memory.
+ * mode: 0 picks the path by the size, 1 forces the block-private LDS accumulators (n_bins <= 124, what 64 KiB hold)
+ * flushed once per block, 2 forces adds to device memory; the limbs are the same on both. A bin < 0 or >= n_bins
+ * is skipped. ART_E_INVALID before any device is touched: n < 0, n_bins < 1 or > 2^24, an unknown mode, mode 1 with
+ * n_bins > 124, a NULL buffer that the call needs. n == 0: ART_OK, nothing touched. */
+#define ART_EXACT_LIMBS 66
+int art_exact_histogram_device(int64_t n, const int32_t* bins, const double* values, int32_t n_bins, int64_t* acc,
+                               double* nonfinite, int32_t mode, void* stream);
+/* out[b] = the correctly rounded double of bin b, one lane per bin: carry-propagate, take the sign from the top,
+ * negate if negative, find the leading bit, take 53 bits with guard and sticky, round to nearest even, assemble the
+ * pattern. A sum below 2^-1022 is exact; one that rounds to 2^1024 or beyond is ±inf; a sum of zero is +0.0. The
+ * accumulator is only read: more can be added afterwards. */
+int art_exact_finish_device(int64_t n_bins, const int64_t* acc, double* out, void* stream);
+/* The host twins, the same functions compiled for the host (art_exact.h): add n values to the bins named (bins NULL:
+ * all to bin 0) and leave every bin normalised, *nonfinite += the NaNs and infinities skipped (may be NULL);
+ * normalise n_bins bins; round n_bins bins. They touch no device. */
+int art_exact_add_host(int64_t n, const int32_t* bins, const double* values, int32_t n_bins, int64_t* acc,
+                       int64_t* nonfinite);
+int art_exact_normalize_host(int64_t n_bins, int64_t* acc);
+int art_exact_round_host(int64_t n_bins, const int64_t* acc, double* out);
+
+/* The exact tables of a chunk: art_event_replicates_device's contract without the groups. Per set k (kind 0 the
+ * run's own powers, n_sets = 1; 1 a coupling scan's from node_factor and event_factor; 2 a halo scan's from
+ * event_factor) the power of every final record inside its own tree's range -- formed by the same products in the
+ * same order as the float kernels form it -- is added to totals_acc[k][species], to flux_acc[k] in
+ * art_event_rows_device's flux bin and to sky_acc[k] in its sky bin. A record in the range of a tree other than its
+ * own is skipped and counted in *misplaced (must stay 0). */
+typedef struct art_event_exact_out {
+  int32_t kind;                /* art_event_replicates_out's: 0 the run, 1 a coupling scan, 2 a halo scan */
+  int32_t n_sets;              /* K, 1 .. 32; 1 with kind 0                                           */
+  int32_t nbins;               /* flux bins over [-π, π], 0 .. 4096 (0: no flux table)               */
+  int32_t mode;                /* 0 auto: totals, and the flux table when nbins <= 56, block-private in LDS;
+                                  1 forces both into LDS (nbins <= 56); 2 forces every add to device memory */
+  const double* node_factor;   /* K * n_nodes  INPUT, kind 1: W_k of every record                    */
+  const double* event_factor;  /* K * n_events INPUT, kind 1: B_k; kind 2: R_k of every event         */
+  int64_t* flux_acc;           /* K * 2 nbins * ART_EXACT_LIMBS                                       */
+  const art_sky_spec* sky;     /* NULL: no sky map; its mode is ignored (the sky accumulators stay in HBM) */
+  int64_t* sky_acc;            /* K * 2 n_theta n_phi n_dw * ART_EXACT_LIMBS                          */
+  int64_t* totals_acc;         /* K * 2 * ART_EXACT_LIMBS: all final axion rows, all final photon rows */
+  double* nonfinite;           /* K: powers that were NaN or infinite (not added anywhere)            */
+  double* misplaced;           /* 1: records in the range of a tree other than their own              */
+} art_event_exact_out;
+/* Asynchronous on `stream`, no host read and no scratch: one launch per set and one normalisation of the tables, by
+ * the headroom rule above. ART_E_INVALID before any device is touched: art_event_replicates_device's faults on p, in,
+ * kind, n_sets, the factor arrays, nbins, the sky spec and node_start; an unknown mode, mode 1 with nbins > 56; a
+ * NULL table or count that the call needs. n_events == 0: ART_OK, nothing touched. */
+int art_event_exact_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                           const art_event_exact_out* out, void* stream);
+
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the
  * other ranks (a file, MPI, the launcher); every rank then calls art_comm_init on its device.

@@ -324,6 +324,53 @@ int main() {
     so.top = 0; so.top_power = nullptr;  // no list: its buffers are not asked for
     ei.n_events = ei.n_nodes = 0;
     CHECK(art_event_spectrum_device(&p, &ei, nullptr, &so, nullptr) == ART_OK);
+    // the exact tables: the host twins on limbs, then the device calls' checks, all before the device
+    {
+      std::vector<int64_t> acc(3 * ART_EXACT_LIMBS, 0);
+      const double v[6] = {1e308, 1.0, -1e308, std::nan(""), 5e-324, -1.5};
+      const int32_t b[6] = {0, 0, 0, 1, 1, 7};  // (bin 7 of 3: skipped)
+      int64_t bad = 0;
+      double out[3];
+      CHECK(art_exact_add_host(6, b, v, 3, acc.data(), &bad) == ART_OK && bad == 1);
+      CHECK(art_exact_normalize_host(3, acc.data()) == ART_OK && art_exact_round_host(3, acc.data(), out) == ART_OK);
+      CHECK(out[0] == 1.0 && out[1] == 5e-324 && out[2] == 0.0);
+      CHECK(art_exact_add_host(1, nullptr, v, 3, acc.data(), nullptr) == ART_OK);  // (bins NULL: bin 0; no count asked for)
+      CHECK(art_exact_add_host(-1, b, v, 3, acc.data(), &bad) == ART_E_INVALID);
+      CHECK(art_exact_add_host(1, b, nullptr, 3, acc.data(), &bad) == ART_E_INVALID);
+      CHECK(art_exact_round_host(1, nullptr, out) == ART_E_INVALID && art_exact_normalize_host(-1, acc.data()) == ART_E_INVALID);
+      CHECK(art_exact_histogram_device(-1, b, v, 3, acc.data(), out, 0, nullptr) == ART_E_INVALID);
+      CHECK(art_exact_histogram_device(6, b, v, 0, acc.data(), out, 0, nullptr) == ART_E_INVALID);
+      CHECK(art_exact_histogram_device(6, b, v, 3, acc.data(), out, 3, nullptr) == ART_E_INVALID);
+      CHECK(art_exact_histogram_device(6, b, v, 125, acc.data(), out, 1, nullptr) == ART_E_INVALID);
+      CHECK(art_exact_histogram_device(6, b, v, 3, acc.data(), nullptr, 0, nullptr) == ART_E_INVALID);
+      CHECK(art_exact_histogram_device(0, nullptr, nullptr, 3, nullptr, nullptr, 0, nullptr) == ART_OK);
+      CHECK(art_exact_finish_device(-1, acc.data(), out, nullptr) == ART_E_INVALID);
+      CHECK(art_exact_finish_device(3, nullptr, out, nullptr) == ART_E_INVALID);
+      art_event_exact_out xo{};
+      xo.kind = 0; xo.n_sets = 1; xo.nbins = 50; xo.flux_acc = xo.totals_acc = acc.data(); xo.nonfinite = xo.misplaced = d;
+      ei.n_events = ei.n_nodes = 4;
+      CHECK(art_event_exact_device(nullptr, &ei, ns, &xo, nullptr) == ART_E_INVALID);
+      CHECK(art_event_exact_device(&p, nullptr, ns, &xo, nullptr) == ART_E_INVALID);
+      CHECK(art_event_exact_device(&p, &ei, ns, nullptr, nullptr) == ART_E_INVALID);
+      xo.kind = 3;
+      CHECK(art_event_exact_device(&p, &ei, ns, &xo, nullptr) == ART_E_INVALID);
+      xo.kind = 0; xo.n_sets = 2;  // the run has one set
+      CHECK(art_event_exact_device(&p, &ei, ns, &xo, nullptr) == ART_E_INVALID);
+      xo.kind = 1; xo.n_sets = 32;  // a coupling scan without its factors
+      CHECK(art_event_exact_device(&p, &ei, ns, &xo, nullptr) == ART_E_INVALID);
+      xo.kind = 0; xo.n_sets = 1; xo.mode = 3;
+      CHECK(art_event_exact_device(&p, &ei, ns, &xo, nullptr) == ART_E_INVALID);
+      xo.mode = 1; xo.nbins = 57;  // the LDS path holds 56 flux bins
+      CHECK(art_event_exact_device(&p, &ei, ns, &xo, nullptr) == ART_E_INVALID);
+      xo.mode = 0; xo.nbins = 50;
+      CHECK(art_event_exact_device(&p, &ei, nullptr, &xo, nullptr) == ART_E_INVALID);  // node_start
+      xo.sky = &full;  // a good spec without its accumulators
+      CHECK(art_event_exact_device(&p, &ei, ns, &xo, nullptr) == ART_E_INVALID);
+      xo.sky = nullptr; xo.nonfinite = nullptr;
+      CHECK(art_event_exact_device(&p, &ei, ns, &xo, nullptr) == ART_E_INVALID);
+      ei.n_events = ei.n_nodes = 0;
+      CHECK(art_event_exact_device(&p, &ei, nullptr, &xo, nullptr) == ART_OK);
+    }
     // where the four event calls differ on purpose (art_post.cpp's front-end flags). A call that passes its
     // argument checks goes on to the device, which this container does not have.
     auto went_on = [](int r) { return r == ART_E_HIP || r == ART_E_NOMEM || r == ART_OK; };

@@ -91,6 +91,13 @@ hipError_t launch_event_replicates(const EventRowsArgs&, const EventReplicatesAr
 }
 hipError_t launch_event_grid(const EventRowsArgs&, const EventGridArgs&, hipStream_t) { return hipErrorNoDevice; }
 hipError_t launch_event_spectrum(const EventRowsArgs&, const EventSpectrumArgs&, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_exact_histogram(int64_t, const int32_t*, const double*, int, int64_t*, double*, bool, hipStream_t) {
+  return hipErrorNoDevice;
+}
+hipError_t launch_exact_finish(int64_t, const int64_t*, double*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_event_exact(const EventRowsArgs&, const EventExactArgs&, const SkyAxes&, int, int, hipStream_t) {
+  return hipErrorNoDevice;
+}
 MFn nl_eval_math(int) { return nullptr; }
 hipError_t launch_eval_math(int, int, int64_t, const double*, const double*, double*, double*, hipStream_t) {
   return hipErrorNoDevice;
