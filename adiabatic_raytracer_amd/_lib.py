@@ -130,6 +130,20 @@ EXACT_LIMBS = 66
 EXACT_MODES = {"auto": 0, "lds": 1, "global": 2}
 EXACT_LDS_BINS, EXACT_LDS_FLUX_BINS = 124, 56
 
+class OriginSpec(C.Structure):  # include/art.h art_origin_spec
+    _fields_ = [("n_r", C.c_int32), ("n_theta", C.c_int32), ("n_phi", C.c_int32), ("theta_axis", C.c_int32),
+                ("mode", C.c_int32), ("r_lo", C.c_double), ("r_hi", C.c_double), ("cm", C.c_double), ("sm", C.c_double)]
+
+
+class EventOriginOut(C.Structure):  # include/art.h art_event_origin_out
+    _fields_ = [("origin", C.POINTER(OriginSpec)), ("observer", C.POINTER(SkySpec)), ("groups", C.c_int32),
+                ("hist", C.c_void_p), ("bin_out", C.c_void_p), ("power_out", C.c_void_p), ("misplaced", C.c_void_p)]
+
+
+# the emission maps: the modes of art_origin_spec, the doubles a block-private table may hold
+ORIGIN_MODES = {"auto": 0, "lds": 1, "global": 2}
+ORIGIN_LDS_DOUBLES = 8192
+
 EVENT_TOTALS = ("rows", "photon_rows", "sum_axion", "sum_photon", "attempts_minus_1", "cyclotron_mismatches")
 # art_event_moments_out::totals
 MOMENT_TOTALS = ("events", "A1", "A2", "Q_axion", "Q_photon", "C_axion", "C_photon", "bad_nodes")
@@ -225,6 +239,7 @@ SIGNATURES = {
     "art_exact_normalize_host": (C.c_int, [_i64, _v]),
     "art_exact_round_host": (C.c_int, [_i64, _v, _v]),
     "art_event_exact_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventExactOut), _v]),
+    "art_event_origin_device": (C.c_int, [_P, C.POINTER(EventRowsIn), _v, C.POINTER(EventOriginOut), _v]),
     "art_comm_unique_id": (C.c_int, [_v]),
     "art_comm_init": (C.c_int, [_i32, _i32, _v]),
     "art_flux_allreduce": (C.c_int, [_v, _i64, _v]),

@@ -257,6 +257,14 @@ struct SkyAxes {
   int32_t c_all;
   double lo[3], hi[3];
 };
+// The origin axes of an emission map (origin_bin_of, art_event_origin.h): n the bins of r, θ and φ of the event's
+// sampled point turned about y by (cm, sm); theta_axis 0 θ over [0, π], 1 cos θ over [-1, 1]; r over [r_lo, r_hi],
+// or r_all: one bin holding every finite r (n[0] = 1).
+struct OriginAxes {
+  int32_t n[3];
+  int32_t r_all, theta_axis;
+  double r_lo, r_hi, cm, sm;
+};
 // The largest table (2 n[0] n[1] n[2] doubles) a block keeps in LDS: 64 KiB, which leaves two
 // blocks on a CU's 160 KiB; larger tables are added to in HBM.
 constexpr int64_t SKY_LDS_DOUBLES = 8192;
@@ -409,6 +417,21 @@ struct EventReplicatesArgs {
 };
 hipError_t launch_event_replicates(const EventRowsArgs& a, const EventReplicatesArgs& r, const SkyAxes& A, int cos_axis,
                                    hipStream_t s);
+// The emission maps (art_event_origin_device; the kernel of art_event_origin.h): the inputs are an EventRowsArgs (its
+// outputs unused) and the forest's node_start. One table is `table` = 2 n_obs n_origin doubles, n_origin the origin
+// bins n_r n_theta n_phi; hist holds max(n_groups, 1) of them, group g at g table. bin_out and power_out (n_nodes,
+// either may be null) and misplaced (1) as art_event_origin_out's. A, cos_axis: the observer axes (c_all); mode as
+// launch_sky_map's, for the whole of hist.
+struct EventOriginArgs {
+  const int64_t* node_start;
+  int32_t n_groups, n_origin;
+  int64_t table;
+  double* hist;
+  int32_t* bin_out;
+  double *power_out, *misplaced;
+};
+hipError_t launch_event_origin(const EventRowsArgs& a, const EventOriginArgs& r, const SkyAxes& A, int cos_axis,
+                               const OriginAxes& O, int mode, hipStream_t s);
 // The coupling x halo grid (art_event_grid_device; the kernel of art_event_grid.h): the inputs are an EventRowsArgs
 // (its outputs unused), the forest's node_start and the factors of the two scans of the same chunk, W (n_g n_nodes),
 // B (n_g n_events) and R (n_h n_events). The tables are cell-minor (art_event_grid.h): flux (2 nbins x C), totals

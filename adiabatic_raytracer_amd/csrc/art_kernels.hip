@@ -1121,6 +1121,9 @@ hipError_t launch_event_rows(const EventRowsArgs& a, const SkyAxes& A, int cos_a
 #include "art_event_replicates.h"
 #include "art_event_grid.h"
 #include "art_event_spectrum.h"
+// the emission maps (art_event_origin_device): the power over its origin and observer, through event_record and
+// sky_accumulate
+#include "art_event_origin.h"
 // the exact tables (art_exact_histogram_device, art_exact_finish_device, art_event_exact_device): a seventh kernel of
 // the family, on integer limbs
 #include "art_exact.h"

@@ -853,6 +853,56 @@ int art_event_spectrum_device(const art_params* p, const art_event_rows_in* in, 
   return ART_OK;
 }
 
+// The emission map of a chunk (include/art.h): the powers of its final rows over their event's conversion point and,
+// with an observer, jointly over their direction (art_event_origin.h), one kernel on `stream`.
+int art_event_origin_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                            const art_event_origin_out* out, void* stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  int rc = validate(p);
+  if (rc) return rc;
+  if (!in || !out || !out->origin) return fail(ART_E_INVALID, "NULL in, out or origin");
+  const art_origin_spec* og = out->origin;
+  if (og->n_r < 1 || og->n_theta < 1 || og->n_phi < 1) return fail(ART_E_INVALID, "origin bin counts must be >= 1");
+  if (og->theta_axis != 0 && og->theta_axis != 1) return fail(ART_E_INVALID, "theta_axis must be 0 (theta) or 1 (cos theta)");
+  if (og->mode < 0 || og->mode > 2) return fail(ART_E_INVALID, "origin mode must be 0 (auto), 1 (LDS table) or 2 (global adds)");
+  if (!std::isfinite(og->cm) || !std::isfinite(og->sm) || !std::isfinite(og->r_lo) || !std::isfinite(og->r_hi))
+    return fail(ART_E_INVALID, "origin: cm, sm and the range of r must be finite");
+  const bool r_all = og->n_r == 1 && og->r_lo == 0.0 && og->r_hi == 0.0;
+  if (!r_all && !(og->r_lo < og->r_hi)) return fail(ART_E_INVALID, "origin: the range of r needs r_lo < r_hi");
+  if (out->groups != 0 && (out->groups < art::REPLICATES_MIN_GROUPS || out->groups > art::REPLICATES_MAX_GROUPS))
+    return fail(ART_E_INVALID, "groups must be 0 (one table) or in [2, 64]");
+  if (out->observer && out->observer->n_dw != 1) return fail(ART_E_INVALID, "origin: the observer axes need n_dw == 1");
+  if ((rc = event_in_ranges(in))) return rc;
+  // the observer axes: the sky map's of (n_theta, n_phi, 1) with c_all; without an observer one bin per species over
+  // the whole sphere
+  const art_sky_spec whole{1, 1, 1, 1, 0, 0.0, 0.0};
+  EventSky S;
+  if ((rc = event_sky(out->observer ? out->observer : &whole, /*honour_mode=*/false, 0, &S))) return rc;
+  int64_t total = (out->groups > 0 ? out->groups : 1) * S.size;  // (S.size <= 2^26, groups <= 64)
+  for (const int32_t nb : {og->n_r, og->n_theta, og->n_phi}) {
+    if (nb > 2147483647LL / total) return fail(ART_E_INVALID, "origin: the table has 2^31 doubles or more");
+    total *= nb;
+  }
+  if (og->mode == 1 && total > art::SKY_LDS_DOUBLES)
+    return fail(ART_E_INVALID, "origin mode 1: the table exceeds the LDS budget of 8192 doubles");
+  if (!out->hist || !out->misplaced) return fail(ART_E_INVALID, "hist or misplaced is NULL");
+  if (in->n_events == 0) return ART_OK;
+  // IN_NODE_START_LATE and IN_CYC_END_STATES: the moments call's checks, whose chunk and re-run this call is handed;
+  // the kernel reads cyc_tau alone.
+  if ((rc = event_in_buffers(in, node_start, IN_NODE_START_LATE | IN_CYC_END_STATES))) return rc;
+  DeviceCtx* ctx;
+  if ((rc = current_ctx(&ctx))) return rc;
+  const art::EventRowsArgs a = event_args(p, in, /*end_states=*/false);
+  const art::OriginAxes O{{og->n_r, og->n_theta, og->n_phi}, r_all ? 1 : 0, og->theta_axis, og->r_lo, og->r_hi, og->cm,
+                          og->sm};
+  art::EventOriginArgs r{};
+  r.node_start = node_start; r.n_groups = out->groups; r.n_origin = og->n_r * og->n_theta * og->n_phi;
+  r.table = S.size * r.n_origin;
+  r.hist = out->hist; r.bin_out = out->bin_out; r.power_out = out->power_out; r.misplaced = out->misplaced;
+  HIP_OK(art::launch_event_origin(a, r, S.A, S.cos_axis, O, og->mode, (hipStream_t)stream));
+  return ART_OK;
+}
+
 // The exact tables (include/art.h; art_exact.h): values into fixed-point accumulators, one per bin, which every call
 // leaves normalised.
 int art_exact_histogram_device(int64_t n, const int32_t* bins, const double* values, int32_t n_bins, int64_t* acc,

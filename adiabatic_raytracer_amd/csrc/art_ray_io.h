@@ -146,7 +146,7 @@ __device__ inline unsigned init_one(const KParams& P, int64_t n, int64_t i, cons
 // with the same roundings: no contraction into FMAs. -1 outside [lo, hi] (and for NaN).
 // The range defaults to flux_kernel's fixed [-π, π]; flux_phi_kernel also takes a data-dependent
 // one (np.histogram(a, bins) without `range` bins over [a.min(), a.max()], plot/flux.py:43-47).
-__device__ inline int np_hist_bin(double x, int nbins, double lo = -PI, double hi = PI) {
+__host__ __device__ inline int np_hist_bin(double x, int nbins, double lo = -PI, double hi = PI) {
 #pragma clang fp contract(off)  // numpy rounds every product and sum (HIP's __dmul_rn would still fuse)
   if (!(x >= lo && x <= hi)) return -1;
   const double span = hi - lo;

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -628,6 +629,8 @@ class Engine:
         out = {"flux_raw": self.exact_round(acc["flux"]).view(K, 2, -1), "totals_raw": self.exact_round(acc["totals"])}
         if acc["sky"] is not None:
             out["sky_raw"] = self.exact_round(acc["sky"])
+        if acc.get("origin") is not None:  # (the emission map's, with run_events(origin_map=, exact=True))
+            out["origin_raw"] = self.exact_round(acc["origin"])
         out["nonfinite"] = acc["nonfinite"]
         if acc["kind"] == "run":
             out = {k: v[0] for k, v in out.items()}
@@ -637,8 +640,73 @@ class Engine:
             out.update(flux=out["flux_raw"] / div, sum_weight_sln_prob=out["totals_raw"] / div)
             if "sky_raw" in out:
                 out["sky_map"] = out["sky_raw"] / div
+            if "origin_raw" in out:
+                out["origin_map"] = out["origin_raw"] / div
         out["acc"] = acc
         return out
+
+    # The most bytes an emission map may take, the R copies of its replicates included
+    ORIGIN_MAX_BYTES = 1 << 30
+
+    @classmethod
+    def _origin_fit(cls, spec, R, exact):
+        """ValueError when an emission map (with R group copies; R None: none) exceeds ORIGIN_MAX_BYTES, or its exact
+        accumulators EXACT_MAX_BYTES or art_exact_histogram_device's 2^24 bins"""
+        bins = 1
+        for d in spec["shape"]:
+            bins *= d
+        size = 8 * bins * max(int(R or 1), 1)
+        if size > cls.ORIGIN_MAX_BYTES:
+            raise ValueError(f"origin_map: the table{' of ' + str(R) + ' groups' if R else ''} would take {size} bytes, more "
+                             f"than {cls.ORIGIN_MAX_BYTES}: coarsen it or lower R")
+        if exact and (bins > 1 << 24 or 8 * _lib.EXACT_LIMBS * bins > cls.EXACT_MAX_BYTES):
+            raise ValueError(f"origin_map: the exact accumulators of {bins} bins ({_lib.EXACT_LIMBS} limbs each) exceed 2^24 "
+                             f"bins or {cls.EXACT_MAX_BYTES} bytes: coarsen the map")
+
+    def event_origin(self, sample, weight5, back, forward, origin, *, observer=None, groups=None, event_offset=0, hist=None,
+                     cyclotron_rerun=None, return_bins=False) -> dict:
+        """The emission map of one chunk (art_event_origin_device; DESIGN.md §3, "Emission maps"), on the current
+        stream and without a synchronisation: the arguments of event_rows for the same chunk, whose powers (column
+        8 * column 7) it bins per species over WHERE the row's event converted -- (r, cos θ or θ, φ) of the sampled
+        point, columns 9 to 11, in the magnetic or the rotation frame -- and, with observer, jointly over the row's
+        direction (θf or cos θf, φf), the sky map's bins. origin: a dict of n_r, n_theta, n_phi, theta_axis, r_range,
+        frame and mode ({}: 1 x 16 x 32, "cos", "magnetic"), or trees.origin_spec's dict; observer: None or a dict of
+        n_theta, n_phi, theta_axis. groups (R, 2 to 64): the table gets a leading group axis and a row goes to group
+        (event_offset + tree) mod R. Returns a dict: hist (the spec's shape (2, obs_theta, obs_phi, n_r, n_theta,
+        n_phi), or (R, ...)), misplaced (1; must stay 0), spec, groups, and with return_bins bins (n_nodes int32: per
+        node record the flat bin without the group, -1 where not counted) and power (n_nodes: the power, 0 where not
+        final). hist: such a dict of an earlier chunk, ACCUMULATED into and returned (made for other axes or groups:
+        ValueError). cyclotron_rerun: event_rows' "cyclotron_rerun" of this chunk, so exp(-τ) is in the powers."""
+        from .trees import origin_spec
+        spec = origin_spec(origin, observer, self.params)
+        R = None if groups is None else self._replicates_groups(groups)
+        shape = spec["shape"] if R is None else (R,) + tuple(spec["shape"])
+        self._origin_fit(spec, R, False)
+        if hist is None:
+            hist = {"hist": torch.zeros(*shape, dtype=F64, device=self.device),
+                    "misplaced": torch.zeros(1, dtype=F64, device=self.device), "groups": R}
+        keys = ("n_r", "n_theta", "n_phi", "theta_axis", "r_range", "cm", "sm", "observer")
+        if (tuple(hist["hist"].shape) != tuple(shape) or hist.get("groups") != R or
+                ("spec" in hist and any(hist["spec"][k] != spec[k] for k in keys))):
+            raise ValueError("event_origin: `hist` was made for other axes or other groups")
+        hist["spec"] = spec
+        nn = int(forward["n_nodes"])
+        bins = self.empty(max(nn, 1), dtype=torch.int32) if return_bins else None
+        power = self.empty(max(nn, 1)) if return_bins else None
+        lo, hi = spec["r_range"] or (0.0, 0.0)
+        og = _lib.OriginSpec(spec["n_r"], spec["n_theta"], spec["n_phi"], _lib.THETA_AXIS[spec["theta_axis"]], spec["mode"],
+                             lo, hi, spec["cm"], spec["sm"])
+        obs = spec["observer"]
+        sk = None if obs is None else _lib.SkySpec(obs["n_theta"], obs["n_phi"], 1, _lib.THETA_AXIS[obs["theta_axis"]], 0,
+                                                   0.0, 0.0)
+        ei = self._event_rows_in(sample, weight5, back, forward, event_offset, cyclotron_rerun)
+        oo = _lib.EventOriginOut(C.pointer(og), C.pointer(sk) if sk is not None else None, R or 0, _p(hist["hist"]),
+                                 _p(bins), _p(power), _p(hist["misplaced"]))
+        check(self.lib.art_event_origin_device(C.byref(self.cp), C.byref(ei), _p(forward["node_start"]), C.byref(oo),
+                                               _stream()))
+        if return_bins:
+            hist.update(bins=bins[:nn], power=power[:nn])
+        return hist
 
     # The most bytes the spectrum tables of one set of tables (the run's, a coupling scan's or a halo scan's) may take
     SPECTRUM_MAX_BYTES = 64 << 20
@@ -793,7 +861,7 @@ class Engine:
     def run_events(self, n_events, *, seed=1769, event_offset=0, chunk=None, saveMode=0, num_cutoff=5, MC_nodes=5,
                    max_nodes=50, prob_cutoff=1e-10, backtrace_cap=256, rho_DM=0.45, n_maxSample=6, nbins=50, sky_map=None,
                    cyclotron=False, rows=True, halo=None, errors=False, couplings=None, halos=None, replicates=None,
-                   grid=False, spectrum=None, exact=False) -> dict:
+                   grid=False, spectrum=None, exact=False, origin_map=None) -> dict:
         """One main_runner_tree run of n_events events (global ids event_offset .. event_offset +
         n_events) with everything in HBM: per chunk of events [lo, hi) the sampler (ray_offset = lo), the
         event weights, the backtrace forest (-k, -B0, axion, num_cutoff = 0, splittings_cutoff = 100000,
@@ -890,6 +958,21 @@ class Engine:
         are what they are without it. Accumulators of more than Engine.EXACT_MAX_BYTES (1 GiB) per set of tables are
         a ValueError before any work is done. False (the default): exactly the keys below.
 
+        origin_map ("Emission maps"; {} or a dict of event_origin's origin keys n_r, n_theta, n_phi,
+        theta_axis, r_range, frame, mode, plus an optional observer=dict(n_theta, n_phi, theta_axis)): the power per
+        species binned over WHERE its event converted -- the sampled point of columns 9 to 11 in the magnetic or the
+        rotation frame -- and with observer jointly over the direction it left in (event_origin per chunk; it needs no
+        rows and takes the cyclotron re-run's τ as the other tables do). The result gets "origin", a dict of host
+        arrays: map (2, obs_theta, obs_phi, n_r, n_theta, n_phi), divided by f_inx, with size-1 observer axes kept;
+        raw, the undivided table; edges (trees.origin_map_edges); spec; misplaced. With replicates=R also
+        "replicates": raw (R, ...), the per-group tables of a second launch, with the run's own n_g, a_g, R and f_inx
+        (the same events, the same groups), for trees.origin_jackknife. With exact=True "exact" gets origin_map,
+        origin_raw and acc["origin"], from the labels and powers the origin kernel hands out through
+        exact_histogram. trees.emission_profile and trees.observer_view read the map. The scans (couplings=, halos=),
+        grid=, errors=True and spectrum= get NO origin table: the jackknife is its error path. Tables of more than
+        Engine.ORIGIN_MAX_BYTES (1 GiB, the R copies included), or exact accumulators of more than EXACT_MAX_BYTES
+        or 2^24 bins, are a ValueError before any work is done. None (the default): exactly the keys below.
+
         Returns a dict of device tensors and numbers: rows ((n_rows, ncols) with column 7 divided by f_inx,
         or None), flux ((2, nbins), divided by f_inx), sky_map and sky_map_edges (numpy) when asked for,
         f_inx, sum_weight_sln_prob, n_rows, n_photon_rows, and the raw, undivided parts for a caller that
@@ -907,6 +990,12 @@ class Engine:
             spectrum = spectrum_keywords(spectrum)  # (before any work is done)
         if halos is not None:
             halos = halo_scan_models(halo, halos)  # (before any work is done)
+        ospec = None
+        if origin_map is not None:  # (before any work is done)
+            from .trees import origin_spec
+            ospec = origin_spec({k: v for k, v in origin_map.items() if k != "observer"}, origin_map.get("observer"),
+                                self.params)
+            self._origin_fit(ospec, replicates, exact)
         n_events = int(n_events)
         if n_events < 0:
             raise ValueError("run_events: n_events must be >= 0")
@@ -943,6 +1032,7 @@ class Engine:
         totals = torch.zeros(len(_lib.EVENT_TOTALS), dtype=F64, device=self.device)
         parts = []
         moments = scan = hscan = rep = crep = hrep = cells = spec = cspec = hspec = xacc = cxacc = hxacc = None
+        omap = orep = oacc = None
         want = replicates is not None
         factors = want or bool(grid) or spectrum is not None or bool(exact)  # the scans hand out their factors
         for lo in range(int(event_offset), int(event_offset) + n_events, chunk):
@@ -996,6 +1086,14 @@ class Engine:
                                              event_factor=scan["back"], **kw)
                 if halos is not None:
                     hxacc = self.event_exact(s, w5, back, fwd, acc=hxacc, kind="halo", event_factor=hscan["ratio"], **kw)
+            if ospec is not None:
+                kw = dict(event_offset=lo, cyclotron_rerun=r["cyclotron_rerun"])
+                omap = self.event_origin(s, w5, back, fwd, ospec, hist=omap, return_bins=bool(exact), **kw)
+                if want:
+                    orep = self.event_origin(s, w5, back, fwd, ospec, groups=replicates, hist=orep, **kw)
+                if exact:  # (the labels and powers the kernel handed out: no exact kernel of its own)
+                    # (its non-finite count is not kept: the run's own exact tables count the same powers in nonfinite)
+                    oacc, _ = self.exact_histogram(omap.pop("bins"), omap.pop("power"), omap["hist"].numel(), acc=oacc)
             if factors:  # (this chunk's factors are not part of the scans' tables)
                 for d, keys in ((scan, ("weights", "back", "back_prob")), (hscan, ("ratio",))):
                     for k in keys if d is not None else ():
@@ -1073,6 +1171,22 @@ class Engine:
                 if out["spectrum"]["misplaced"] != 0:
                     raise _lib.ArtError(f"run_events: {out['spectrum']['misplaced']} node records lie in the range of "
                                         "another tree")
+        if ospec is not None:
+            from .trees import origin_result
+            zero = np.zeros(ospec["shape"])  # (no events)
+            res["origin"] = origin_result(zero if omap is None else omap["hist"].cpu().numpy(), ospec, f_inx,
+                                          0.0 if omap is None else float(omap["misplaced"].item()))
+            if want:
+                rr = res["replicates"]
+                res["origin"]["replicates"] = {
+                    "raw": np.zeros((replicates,) + ospec["shape"]) if orep is None else orep["hist"].cpu().numpy(),
+                    "n_g": rr["n_g"], "a_g": rr["a_g"], "R": replicates, "f_inx": f_inx}
+            if exact:
+                if xacc is None:  # (no events)
+                    xacc = self._zero_exact("run", 1, int(nbins), shape)
+                if oacc is None:
+                    oacc = torch.zeros(zero.size, _lib.EXACT_LIMBS, dtype=torch.int64, device=self.device)
+                xacc["origin"] = oacc.view(1, *ospec["shape"], _lib.EXACT_LIMBS)
         if exact:
             for out, have, kind, K in ((res, xacc, "run", 1), (res.get("coupling_scan"), cxacc, "coupling", len(couplings or ())),
                                        (res.get("halo_scan"), hxacc, "halo", len(halos or ()))):

@@ -198,7 +198,7 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                      num_cutoff=5, MC_nodes=5, max_nodes=50, prob_cutoff=1e-10, saveMode=0, dir_tag=None,
                      file_tag="", backtrace_cap=256, rank=0, world=1, nbins=50, run_info=None, cyclotron=False,
                      sky_map=None, device_trees=False, device_events=False, halo=None, errors=False,
-                     couplings=None, halos=None, replicates=None, grid=False, spectrum=None, exact=False):
+                     couplings=None, halos=None, replicates=None, grid=False, spectrum=None, exact=False, origin_map=None):
     """main_runner_tree (MainRunner.jl:354-763) for Ntajs - 1 events (the reference's
     `while photon_trajs < desired_trajs` loop), all events batched on the GPU. Returns the
     row matrix (13 columns, 29 with saveMode > 0) after the final division of column 8 by
@@ -307,7 +307,19 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     the vector of the same all-reduce and are converted back and rounded after it. run_info["exact"] is exact_result's
     dict of host arrays, and the scans' dicts get "exact" too. On the other two paths the tables are built on the host
     and exact=True is a ValueError: rows_exact gives the same tables from their rows. With the default False every
+    row, file, run_info key and the reduced vector are unchanged.
+
+    origin_map (beyond the reference; {} or a dict of origin_spec's origin keys plus an optional observer=dict(n_theta,
+    n_phi, theta_axis); DESIGN.md §3, "Emission maps"): the power per species over where its event converted (columns 9
+    to 11, in the magnetic or the rotation frame) and, with observer, jointly over the direction it left in, on all
+    three paths: device_events takes Engine.run_events' table (art_event_origin_device), the other two bin their rows
+    with rows_origin. The rank's raw table rides as the LAST part of the vector of the same all-reduce, after `exact`,
+    and run_info["origin"] is origin_result's dict of the reduced table: map (divided by the global f_inx), raw, edges,
+    spec, misplaced. The scans, the grid, errors and the spectrum get no origin table. With the default None every
     row, file, run_info key and the reduced vector are unchanged."""
+    ospec = None
+    if origin_map is not None:  # (before any work is done)
+        ospec = origin_spec({k: v for k, v in origin_map.items() if k != "observer"}, origin_map.get("observer"), params)
     if exact and not device_events:
         raise ValueError("exact: the exact tables are accumulated from forests held in HBM and need device_events=True "
                          "(trees.rows_exact gives the same tables from the rows of the other paths)")
@@ -337,7 +349,8 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
                                         couplings=couplings, halos=halos, replicates=replicates,
                                         **({"grid": True} if grid else {}),
                                         **({} if spectrum is None else {"spectrum": spectrum}),
-                                        **({"exact": True} if exact else {}))
+                                        **({"exact": True} if exact else {}),
+                                        **({} if origin_map is None else {"origin_map": origin_map}))
     if device_trees and saveMode > 2 and dir_tag is not None:
         raise ValueError("device_trees: tree dumps (saveMode > 2 with dir_tag) need the host forest's trajectories")
     if saveMode < 3:
@@ -429,13 +442,14 @@ def main_runner_tree(params: Params, Ntajs: int, *, seed=1769, ntimes=1000, rho_
     spec = None if spectrum is None else {"run": rows_spectrum(rows, *spectrum_keywords(spectrum), event_lo=lo, n_events=n_ev)}
     return _finish_run(rows, tot, nbins=nbins, sky_kw=sky_kw, errors=errors, world=world, run_info=run_info,
                        events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path, **({} if rep is None else {"replicates": rep}),
-                       **({} if spec is None else {"spectrum": spec, "rank": rank}))
+                       **({} if spec is None else {"spectrum": spec, "rank": rank}),
+                       **({} if ospec is None else {"origin": (rows_origin(rows, ospec), ospec)}))
 
 
 def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cutoff, MC_nodes, max_nodes, prob_cutoff,
                              saveMode, dir_tag, file_tag, backtrace_cap, rank, world, nbins, run_info, cyclotron, sky_map,
                              halo=None, errors=False, couplings=None, halos=None, replicates=None, grid=False,
-                             spectrum=None, exact=False):
+                             spectrum=None, exact=False, origin_map=None):
     """main_runner_tree(device_events=True): the rank's events through Engine.run_events, then the same
     totals vector, all-reduce, division, run_info and files as the host assembly."""
     from .engine import Engine
@@ -454,7 +468,8 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                                   **({} if replicates is None else {"replicates": replicates}),
                                   **({"grid": True} if grid else {}),
                                   **({} if spectrum is None else {"spectrum": spectrum}),
-                                  **({"exact": True} if exact else {}))
+                                  **({"exact": True} if exact else {}),
+                                  **({} if origin_map is None else {"origin_map": origin_map}))
     xa = None
     if exact:
         xa = {"run": exact_raw(r["exact"]["acc"])}
@@ -478,7 +493,8 @@ def _main_runner_tree_device(params, Ntajs, *, seed, rho_DM, n_maxSample, num_cu
                        None if halos is None else r["halo_scan"]["raw"], nbins=nbins, sky_kw=sky_kw, errors=errors,
                        world=world, run_info=run_info, events=(lo, hi), n_events=n_glob, g0=params.g_agg, path=path,
                        **({} if rep is None else {"replicates": rep}), **({"grid": r["grid"]["raw"]} if grid else {}),
-                       **({} if spec is None else {"spectrum": spec, "rank": rank}), **({} if xa is None else {"exact": xa}))
+                       **({} if spec is None else {"spectrum": spec, "rank": rank}), **({} if xa is None else {"exact": xa}),
+                       **({} if origin_map is None else {"origin": (r["origin"]["raw"], r["origin"]["spec"])}))
 
 
 def cyclotron_optical_depth(params: Params, fin, erg) -> np.ndarray:
@@ -1131,7 +1147,8 @@ def replicates_result(raw, f_inx) -> dict:
     return res
 
 
-EXACT_KEYS = ("flux", "sky", "totals")  # the accumulator tables of an exact dict, each (K, ..., 66) int64
+EXACT_KEYS = ("flux", "sky", "totals", "origin")  # the accumulator tables of an exact dict, each (K, ..., 66) int64
+# ("origin": the emission map's, with run_events(origin_map=, exact=True) only; a dict without it packs as before)
 EXACT_PARTS = ("run", "coupling", "halo")  # the order of the exact parts of a rank's vector
 
 
@@ -1226,6 +1243,8 @@ def exact_finish(acc) -> dict:
     out = {"flux_raw": exact_round(acc["flux"]).reshape(K, 2, -1), "totals_raw": exact_round(acc["totals"])}
     if acc["sky"] is not None:
         out["sky_raw"] = exact_round(acc["sky"])
+    if acc.get("origin") is not None:  # (the emission map's, with run_events(origin_map=, exact=True))
+        out["origin_raw"] = exact_round(acc["origin"])
     out["nonfinite"] = np.asarray(acc["nonfinite"], np.float64).copy()
     return {k: v[0] for k, v in out.items()} if acc["kind"] == "run" else out
 
@@ -1242,6 +1261,8 @@ def exact_result(acc, f_inx) -> dict:
     out.update(flux=out["flux_raw"] / div, sum_weight_sln_prob=out["totals_raw"] / div)
     if "sky_raw" in out:
         out["sky_map"] = out["sky_raw"] / div
+    if "origin_raw" in out:
+        out["origin_map"] = out["origin_raw"] / div
     out["acc"] = acc
     return out
 
@@ -1355,6 +1376,203 @@ def jackknife(rep, fn, cov=False) -> dict:
     if cov:
         out["cov"] = c * (d.T @ d)
     return out
+
+
+# ---- emission maps: the power over where its event converted, and jointly over where it goes
+ORIGIN_KEYS = ("n_r", "n_theta", "n_phi", "theta_axis", "r_range", "frame", "mode")
+ORIGIN_FRAMES = ("magnetic", "rotation")
+
+
+def origin_spec(origin, observer=None, params=None) -> dict:
+    """An emission map's keywords completed and checked, the dict Engine.event_origin and the numpy oracle both use:
+    origin a dict of n_r, n_theta, n_phi, theta_axis ("cos" | "theta"), r_range, frame ("magnetic" | "rotation") and
+    mode (0 or "auto", 1 or "lds", 2 or "global"); {}: 1 x 16 x 32, "cos", "magnetic". observer: None, or a dict of
+    n_theta, n_phi, theta_axis ({}: 32 x 64, "cos"), the sky map's first two axes. The spec also holds cm and sm, the
+    rotation about y that origin_bins applies: math.cos / math.sin of params.theta_m in frame "magnetic" (params is
+    needed there), (1, 0) in frame "rotation"; "shape", the table's (2, obs_theta, obs_phi, n_r, n_theta, n_phi), and
+    "observer", the completed dict or None. A dict that origin_spec made (it is marked) is returned after a check that
+    its shape still follows from its axes and its mode is 0, 1 or 2; observer= beside it is a ValueError. Unknown keys, an axis
+    below 1, n_r > 1 without an r_range and a bad range are a ValueError."""
+    if isinstance(origin, dict) and origin.get("_origin_spec") is True:  # (completed here: checked again, cheaply)
+        if observer is not None:
+            raise ValueError("origin_map: a completed spec holds its observer axes; observer= beside it is refused")
+        obs = origin["observer"]
+        shape = (2, obs["n_theta"] if obs else 1, obs["n_phi"] if obs else 1, origin["n_r"], origin["n_theta"], origin["n_phi"])
+        if tuple(origin["shape"]) != shape or origin["mode"] not in (0, 1, 2) or min(shape) < 1:
+            raise ValueError("origin_map: the spec was changed after origin_spec completed it (use origin_spec again)")
+        return origin
+    kw = {"n_r": 1, "n_theta": 16, "n_phi": 32, "theta_axis": "cos", "r_range": None, "frame": "magnetic", "mode": 0}
+    if set(origin) - set(kw):
+        raise ValueError(f"origin_map: unknown keys {sorted(set(origin) - set(kw))}")
+    kw.update(origin)
+    _theta_range(kw["theta_axis"])
+    if kw["frame"] not in ORIGIN_FRAMES:
+        raise ValueError(f"origin_map: frame must be 'magnetic' or 'rotation', not {kw['frame']!r}")
+    kw["mode"] = _lib.ORIGIN_MODES.get(kw["mode"], kw["mode"])
+    if kw["mode"] not in (0, 1, 2):
+        raise ValueError(f"origin_map: mode must be 0 / 'auto', 1 / 'lds' or 2 / 'global', not {kw['mode']!r}")
+    for k in ("n_r", "n_theta", "n_phi"):
+        if int(kw[k]) != kw[k] or int(kw[k]) < 1:
+            raise ValueError(f"origin_map: {k} must be an integer >= 1, not {kw[k]!r}")
+        kw[k] = int(kw[k])
+    if kw["r_range"] is None:
+        if kw["n_r"] > 1:
+            raise ValueError("origin_map: n_r > 1 needs an r_range (a data-dependent range cannot be binned chunk by chunk)")
+    else:
+        lo, hi = float(kw["r_range"][0]), float(kw["r_range"][1])
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError("origin_map: r_range needs finite lo < hi")
+        kw["r_range"] = (lo, hi)
+    if kw["frame"] == "magnetic":
+        if params is None:
+            raise ValueError("origin_map: frame 'magnetic' needs the run's params (theta_m)")
+        kw["cm"], kw["sm"] = math.cos(params.theta_m), math.sin(params.theta_m)
+    else:
+        kw["cm"], kw["sm"] = 1.0, 0.0
+    obs = None
+    if observer is not None:
+        obs = {"n_theta": 32, "n_phi": 64, "theta_axis": "cos"}
+        if set(observer) - set(obs):
+            raise ValueError(f"origin_map: unknown observer keys {sorted(set(observer) - set(obs))}")
+        obs.update(observer)
+        _theta_range(obs["theta_axis"])
+        for k in ("n_theta", "n_phi"):
+            if int(obs[k]) != obs[k] or int(obs[k]) < 1:
+                raise ValueError(f"origin_map: the observer's {k} must be an integer >= 1, not {obs[k]!r}")
+            obs[k] = int(obs[k])
+    kw["observer"] = obs
+    kw["_origin_spec"] = True
+    kw["shape"] = (2, obs["n_theta"] if obs else 1, obs["n_phi"] if obs else 1, kw["n_r"], kw["n_theta"], kw["n_phi"])
+    if int(np.prod(kw["shape"], dtype=np.int64)) >= 2 ** 31:
+        raise ValueError("origin_map: the table has 2^31 bins or more")
+    return kw
+
+
+def origin_map_edges(spec) -> tuple:
+    """The bin edges of an emission map's five axes after the species (np.linspace, as np.histogramdd returns them):
+    the observer's cos θf or θf and φf (the whole range in one bin without observer axes), then the origin's r (one
+    bin for every finite r without an r_range: edges (0, inf)), cos θ or θ, and φ."""
+    obs = spec["observer"] or {"n_theta": 1, "n_phi": 1, "theta_axis": "cos"}
+    r_edges = np.array([0.0, np.inf]) if spec["r_range"] is None else np.linspace(*spec["r_range"], spec["n_r"] + 1)
+    return (np.linspace(*_theta_range(obs["theta_axis"]), obs["n_theta"] + 1), np.linspace(-np.pi, np.pi, obs["n_phi"] + 1),
+            r_edges, np.linspace(*_theta_range(spec["theta_axis"]), spec["n_theta"] + 1),
+            np.linspace(-np.pi, np.pi, spec["n_phi"] + 1))
+
+
+def origin_coordinates(x, y, z, spec) -> tuple:
+    """(r, cos θ or θ by the spec's theta_axis, φ) of the points (x, y, z) in the spec's frame, rounded as
+    origin_bin_of (art_event_origin.h) rounds them: v = (x cm - z sm, y, x sm + z cm), then _angles' (θ, φ, |v|) and
+    cos θ = v_z / |v|."""
+    x, y, z = (np.asarray(v, np.float64) for v in (x, y, z))
+    cm, sm = spec["cm"], spec["sm"]
+    v = np.stack([x * cm - z * sm, y, x * sm + z * cm], axis=-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        th, ph, r = _angles(v)
+        return r, (v[..., 2] / r if spec["theta_axis"] == "cos" else th), ph
+
+
+def origin_bins(x, y, z, spec) -> np.ndarray:
+    """The flat origin label (ir n_theta + iθ) n_phi + iφ of each point (x, y, z) -- a row's columns 9 to 11 -- in
+    numpy: the oracle of the device's origin_bin_of. Each axis is np.histogram's bin of its closed range (hist_bins);
+    without an r_range every finite r is in the one r bin; -1 for a point that a range, or a NaN, drops."""
+    r, a, ph = origin_coordinates(x, y, z, spec)
+    ia = hist_bins(a, spec["n_theta"], *_theta_range(spec["theta_axis"]))
+    ib = hist_bins(ph, spec["n_phi"])
+    ir = np.where(np.isfinite(r), 0, -1) if spec["r_range"] is None else hist_bins(r, spec["n_r"], *spec["r_range"])
+    flat = (ir * spec["n_theta"] + ia) * spec["n_phi"] + ib
+    return np.where((ia >= 0) & (ib >= 0) & (ir >= 0), flat, -1)
+
+
+def rows_origin(rows, spec, R=None) -> np.ndarray:
+    """art_event_origin_device's table in numpy from npy rows (column 7 raw or divided alike: the table is in the
+    powers' own units): the oracle of the device table, and the path for row files written earlier. Per row the
+    species (column 1), the observer bin of columns 2 and 3 (sky_bins with n_dw = 1: a row with a non-finite column 12
+    is dropped, as from the sky map), the origin bin of columns 9 to 11 (origin_bins) and the power column 8 * column
+    7. Returns the spec's "shape"; with R (2 to 64) an (R, ...) array, a row in group (column 0 - 1) mod R."""
+    rows = np.asarray(rows, np.float64)
+    shape = spec["shape"]
+    n_origin = shape[3] * shape[4] * shape[5]
+    obs = spec["observer"] or {"n_theta": 1, "n_phi": 1, "theta_axis": "cos"}
+    sb = sky_bins(rows[:, 2], rows[:, 3], rows[:, 12], rows[:, 1], n_theta=obs["n_theta"], n_phi=obs["n_phi"], n_dw=1,
+                  theta_axis=obs["theta_axis"])
+    ob = origin_bins(rows[:, 9], rows[:, 10], rows[:, 11], spec)
+    keep = (sb >= 0) & (ob >= 0)
+    lab = sb[keep] * n_origin + ob[keep]
+    size = int(np.prod(shape))
+    p = (rows[:, 8] * rows[:, 7])[keep]
+    if R is None:
+        return np.bincount(lab, weights=p, minlength=size).reshape(shape)
+    R = int(R)
+    if not _lib.REPLICATES_MIN_GROUPS <= R <= _lib.REPLICATES_MAX_GROUPS:
+        raise ValueError(f"replicates: {_lib.REPLICATES_MIN_GROUPS} to {_lib.REPLICATES_MAX_GROUPS} groups, not {R}")
+    g = ((np.rint(rows[:, 0]).astype(np.int64) - 1) % R)[keep]
+    return np.bincount(g * size + lab, weights=p, minlength=R * size).reshape(R, *shape)
+
+
+def origin_result(raw, spec, f_inx, misplaced=0.0) -> dict:
+    """run_events' and run_info's "origin": map (the raw table divided by f_inx, by 1 when it is 0), raw, edges
+    (origin_map_edges), spec and misplaced (records outside their tree's range, which must be 0: an ArtError)."""
+    raw = np.asarray(raw, np.float64).reshape(spec["shape"])
+    if misplaced != 0:
+        raise _lib.ArtError(f"origin_map: {int(misplaced)} node records lie in the range of another tree")
+    return {"map": raw / (float(f_inx) if f_inx > 0 else 1.0), "raw": raw, "edges": origin_map_edges(spec), "spec": spec,
+            "misplaced": int(misplaced)}
+
+
+def _origin_solid_angles(n_theta, n_phi, theta_axis):
+    """The solid angle of each (θ, φ) bin of a pair of axes, (n_theta, 1): equal with "cos", 2π (cos θ_lo - cos θ_hi) /
+    n_phi per row with "theta" (line_profile's ring)"""
+    edges = np.linspace(*_theta_range(theta_axis), n_theta + 1)
+    ring = 2.0 * np.pi * ((edges[1:] - edges[:-1]) if theta_axis == "cos" else (np.cos(edges[:-1]) - np.cos(edges[1:])))
+    return (ring / n_phi)[:, None]
+
+
+def emission_profile(origin_map, spec, species=PHOTON):
+    """Where on the conversion surface the power comes from: the emission map of one species summed over r and the
+    observer axes, as power per steradian of ORIGIN direction in the spec's frame (each bin divided by its solid
+    angle, as pulse_profile divides). Returns (profile (n_theta, n_phi), the θ-axis bin centres, the φ bin centres)."""
+    m = np.asarray(origin_map, np.float64).reshape(spec["shape"])[species].sum(axis=(0, 1, 2))
+    e = origin_map_edges(spec)
+    return (m / _origin_solid_angles(spec["n_theta"], spec["n_phi"], spec["theta_axis"]), 0.5 * (e[3][:-1] + e[3][1:]),
+            0.5 * (e[4][:-1] + e[4][1:]))
+
+
+def observer_view(origin_map, spec, theta_obs, phase=None, species=PHOTON) -> np.ndarray:
+    """What an observer at inclination theta_obs [rad] sees lit up: the origin table (n_r, n_theta, n_phi) of one
+    species in the observer row that holds theta_obs (pulse_profile's bin rule), as power per steradian of OBSERVER
+    direction: summed over the observer's φ and divided by the row's whole ring (the average over the rotation), or,
+    with phase [rad, in [-π, π]], taken in the φ bin that holds it and divided by that bin's solid angle. The map
+    needs observer axes."""
+    obs = spec["observer"]
+    if obs is None:
+        raise ValueError("observer_view: the emission map has no observer axes")
+    m = np.asarray(origin_map, np.float64).reshape(spec["shape"])[species]
+    x = math.cos(theta_obs) if obs["theta_axis"] == "cos" else float(theta_obs)
+    row = int(hist_bins(np.array([x]), obs["n_theta"], *_theta_range(obs["theta_axis"]))[0])
+    if row < 0:
+        raise ValueError(f"theta_obs = {theta_obs} lies outside the map")
+    omega = _origin_solid_angles(obs["n_theta"], obs["n_phi"], obs["theta_axis"])[row, 0]
+    if phase is None:
+        return m[row].sum(axis=0) / (omega * obs["n_phi"])
+    col = int(hist_bins(np.array([float(phase)]), obs["n_phi"])[0])
+    if col < 0:
+        raise ValueError(f"phase = {phase} lies outside [-π, π]")
+    return m[row, col] / omega
+
+
+def origin_jackknife(origin, fn, cov=False) -> dict:
+    """The delete-a-group jackknife (jackknife's rule and result) of fn over an emission map's replicates: origin is
+    run_events' "origin" dict of a run with replicates=R, and fn gets the NORMALISED map (the spec's shape: the groups'
+    sum, or the sum without one group, divided by its part of f_inx) and returns a number or an array, such as
+    emission_profile's or observer_view's."""
+    rep = origin.get("replicates")
+    if rep is None:
+        raise ValueError("origin_jackknife: the emission map has no replicates (run_events(replicates=R))")
+    T = np.asarray(rep["raw"], np.float64)
+    R = T.shape[0]
+    groups = np.stack([np.asarray(rep["n_g"], np.float64), np.asarray(rep["a_g"], np.float64), np.zeros(R)], axis=1)
+    raw = {"kind": "run", "R": R, "groups": groups, "flux": np.zeros((1, R, 2)), "totals": np.zeros((1, R, 2)), "sky": T[None]}
+    return jackknife({"raw": raw, "f_inx": rep["f_inx"]}, lambda t: fn(t["sky_map"]), cov=cov)
 
 
 def _loglog_crossing(g, P, power):
@@ -1880,7 +2098,7 @@ SPECTRUM_PARTS = ("run", "coupling", "halo")  # the order of the spectrum parts 
 
 
 def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None, grid=None, spectrum=None, rank=0, world=1,
-                exact=None):
+                exact=None, origin=None):
     """A rank's vector for main_runner_tree's single all-reduce, [pack_totals | coupling scan | halo scan |
     replicates... | grid]: the rank's pack_totals vector, then scan_pack of its coupling scan's raw tables and
     halo_scan_pack of its halo scan's, each only when there is one, then replicates_pack of each raw dict of
@@ -1888,7 +2106,8 @@ def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None, gr
     of `grid` (the rank's grid_raw; None: none), so every earlier part keeps its place and its end, and LAST
     spectrum_pack(raw, rank, world) of each raw dict of `spectrum` (a dict with the keys "run", "coupling", "halo"
     there are, in that order; None: none, and the vector is what it is without the keyword); after them exact_pack of
-    each raw dict of `exact` (the same keys and order; None: none, and the vector is what it is without the keyword).
+    each raw dict of `exact` (the same keys and order; None: none, and the vector is what it is without the keyword);
+    LAST of all `origin`, the rank's raw emission map (an array; None: none, and the vector is what it is without it).
     Returns (the vector, where each of its parts ends)."""
     parts = [totals] + [pack(raw) for pack, raw in ((scan_pack, coupling_raw), (halo_scan_pack, halo_raw)) if raw is not None]
     parts += [replicates_pack(replicates[k]) for k in REPLICATE_PARTS if replicates and replicates.get(k) is not None]
@@ -1896,11 +2115,13 @@ def rank_vector(totals, coupling_raw=None, halo_raw=None, *, replicates=None, gr
         parts.append(grid_pack(grid))
     parts += [spectrum_pack(spectrum[k], rank, world) for k in SPECTRUM_PARTS if spectrum and spectrum.get(k) is not None]
     parts += [exact_pack(exact[k]) for k in EXACT_PARTS if exact and exact.get(k) is not None]
+    if origin is not None:
+        parts.append(np.asarray(origin, np.float64).reshape(-1))
     return (np.concatenate(parts) if len(parts) > 1 else totals), np.cumsum([len(v) for v in parts])
 
 
 def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw, errors, world, run_info, events, n_events,
-                g0, path, replicates=None, grid=None, spectrum=None, rank=0, exact=None):
+                g0, path, replicates=None, grid=None, spectrum=None, rank=0, exact=None, origin=None):
     """The end of main_runner_tree on every path: the rank's vector (rank_vector of its pack_totals vector and its
     scans' raw tables) summed over the ranks in ONE all-reduce, σ from the reduced tables, column 8 of the rank's
     rows divided by the global f_inx, run_info (a dict or None; events: the rank's (lo, hi), n_events: the run's),
@@ -1911,11 +2132,14 @@ def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw
     (rank_vector's keyword; rank: this rank's slot for its lists), the vector's last parts, which come back merged
     over the ranks as run_info["spectrum"] and as "spectrum" in the scans' dicts (spectrum_result). exact: the rank's
     raw exact accumulators (rank_vector's keyword), the parts after those, which come back summed over the ranks as
-    run_info["exact"] and as "exact" in the scans' dicts (exact_result). Returns the rows."""
+    run_info["exact"] and as "exact" in the scans' dicts (exact_result). origin: (the rank's raw emission map, its
+    origin_spec), the vector's LAST part, which comes back summed over the ranks as run_info["origin"] (origin_result).
+    Returns the rows."""
     from .shard import allreduce_sum
     tot, ends = rank_vector(totals, coupling_raw, halo_raw, replicates=replicates, **({} if grid is None else {"grid": grid}),
                             **({} if spectrum is None else {"spectrum": spectrum, "rank": rank, "world": world}),
-                            **({} if exact is None else {"exact": exact}))
+                            **({} if exact is None else {"exact": exact}),
+                            **({} if origin is None else {"origin": origin[0]}))
     n_scans = (coupling_raw is not None) + (halo_raw is not None)
     if world > 1:
         tot = allreduce_sum(tot)
@@ -1957,6 +2181,8 @@ def _finish_run(rows, totals, coupling_raw=None, halo_raw=None, *, nbins, sky_kw
             raw = exact_unpack(tot[ends[at + j]:ends[at + j + 1]], exact[k])
             where = run_info if k == "run" else run_info[k + "_scan"]
             where["exact"] = exact_result(raw, int(round(f_glob)))
+        if origin is not None:  # (the vector's last part)
+            run_info["origin"] = origin_result(tot[len(tot) - origin[0].size:], origin[1], int(round(f_glob)))
     if path is not None:
         os.makedirs(os.path.dirname(path), exist_ok=True)
         np.save(path, rows)

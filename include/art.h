@@ -986,6 +986,46 @@ typedef struct art_event_exact_out {
 int art_event_exact_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
                            const art_event_exact_out* out, void* stream);
 
+/* ---- emission maps: the power over WHERE it was produced, and optionally jointly over where it goes ----
+ * Per species the powers of a chunk's final rows (column 8 * column 7, what every other table adds) binned over the
+ * conversion point of their event, the sampled x of columns 9 to 11, and with `observer` jointly over the direction
+ * the row left in, C order:
+ *   hist[species][obs_theta][obs_phi][r][origin_theta][origin_phi]     (no observer: the two observer extents are 1).
+ * The origin: v = (x cm - z sm, y, x sm + z cm), each product and the add or subtract rounded on its own; r = |v| as
+ * np.linalg.norm sums it, θ = acos(v_z / r), φ = atan2(v_y, v_x); the θ axis is θ over [0, π] or cos θ = v_z / r over
+ * [-1, 1], φ is over [-π, π], r over [r_lo, r_hi], every axis binned as np.histogram bins its closed range. (cm, sm) =
+ * (cos θm, sin θm) makes the magnetic axis the pole, (1, 0) leaves x as it is. A NaN or a value outside a range on any
+ * axis drops the row from this table only. The observer bin and the species are art_event_rows_device's sky map's
+ * for (n_theta, n_phi, n_dw = 1) of `observer`, so the table summed over its origin axes is that sky map. The
+ * records counted are art_event_replicates_device's: a final record inside its own tree's range; a record in the
+ * range of another tree is skipped and counted in misplaced. With groups = R the table has a leading group axis and a
+ * row goes to group (event_offset + tree) mod R: R tables and no ungrouped one. */
+typedef struct art_origin_spec {
+  int32_t n_r, n_theta, n_phi;   /* each >= 1 */
+  int32_t theta_axis;            /* 0: θ over [0, π]; 1: cos θ over [-1, 1] */
+  int32_t mode;                  /* 0 auto, 1 LDS, 2 global */
+  double  r_lo, r_hi;            /* ignored when n_r == 1 and r_lo == r_hi == 0: one bin, every finite r */
+  double  cm, sm;                /* the rotation about y; (1, 0) leaves x as it is */
+} art_origin_spec;
+typedef struct art_event_origin_out {
+  const art_origin_spec* origin;
+  const art_sky_spec* observer;  /* NULL: no observer axes; n_dw must be 1; its mode is ignored */
+  int32_t groups;                /* 0, or 2 .. 64 */
+  double* hist;                  /* max(groups,1) * 2 * n_obs * n_r n_theta n_phi, ADDED to */
+  int32_t* bin_out;              /* n_nodes, may be NULL: per record the flat bin without the group, -1: not counted */
+  double* power_out;             /* n_nodes, may be NULL: per record the power, 0 where not final */
+  double* misplaced;             /* 1, ADDED to; must stay 0 */
+} art_event_origin_out;
+/* Asynchronous on `stream`, no host read and no scratch. mode: a table (all groups) of at most 8192 doubles is
+ * block-private in LDS and flushed once per block, a larger one takes float64 hardware adds in HBM; 1 and 2 force
+ * either. ART_E_INVALID before any device is touched: art_event_replicates_device's faults on p, in and node_start;
+ * a NULL out or origin; an axis below 1; an unknown theta_axis or mode; mode 1 with a table over 8192 doubles;
+ * r_lo >= r_hi unless n_r == 1 and both are 0; a non-finite cm, sm or range; an observer with n_dw != 1 or a bad
+ * axis; groups of 1, below 0 or above 64; a flat size of 2^31 or more; a NULL hist or misplaced.
+ * n_events == 0: ART_OK, nothing touched. */
+int art_event_origin_device(const art_params* p, const art_event_rows_in* in, const int64_t* node_start,
+                            const art_event_origin_out* out, void* stream);
+
 /* ---- reduction over the GPUs of a node (RCCL over xGMI) ----
  * One process per GPU. Rank 0 calls art_comm_unique_id and shares the 128 bytes with the
  * other ranks (a file, MPI, the launcher); every rank then calls art_comm_init on its device.

@@ -98,6 +98,9 @@ hipError_t launch_exact_finish(int64_t, const int64_t*, double*, hipStream_t) { 
 hipError_t launch_event_exact(const EventRowsArgs&, const EventExactArgs&, const SkyAxes&, int, int, hipStream_t) {
   return hipErrorNoDevice;
 }
+hipError_t launch_event_origin(const EventRowsArgs&, const EventOriginArgs&, const SkyAxes&, int, const OriginAxes&, int, hipStream_t) {
+  return hipErrorNoDevice;
+}
 MFn nl_eval_math(int) { return nullptr; }
 hipError_t launch_eval_math(int, int, int64_t, const double*, const double*, double*, double*, hipStream_t) {
   return hipErrorNoDevice;
